@@ -9,6 +9,11 @@ One process per GPU, one sample (100 M reads) per GPU (weak scaling).  Rank 0 pr
   python bench.py --gpus 1 --steps 3 --warmup 1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus 8 --steps 3 --warmup 1
+
+A plain run sets up, warms up, times the steps and prints the line (value, ms_per_step, the per-kernel times and rooflines of the
+timed steps, the stages, the exchanges).  --full adds what takes runs of its own or is not about this workload: the `cli`, `end_to_end*`
+lines, the `cpu_baseline` and the committed profiles of other shapes (`roofline_hash_count.other_shapes`, `extension_k63`).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; _dump_outputs), after the clock has stopped.
 """
 import argparse
 import json
@@ -25,6 +30,122 @@ import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is what a copy achieves
 SEED = 0x4D45544146415354      # "METAFAST"
+DUMP_SEED = 0x44554D50         # "DUMP": the fixed samples --dump-outputs takes of large outputs
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+NUC = np.full(256, 255, dtype=np.uint8)
+NUC[np.frombuffer(b"AGCT", dtype=np.uint8)] = np.arange(4, dtype=np.uint8)      # the k-mer coding of the tables (A=0 G=1 C=2 T=3)
+
+
+TOTALS = ("n_reads", "n_bases", "n_occ", "n_distinct", "n_good", "n_unitigs", "n_cutter", "n_cutter_occ", "n_components", "n_component_kmers",
+          "n_singletons")
+
+
+def _pick(n, cap, salt):
+    """a fixed, seeded choice of at most `cap` of the indices 0 .. n-1, ascending (all of them when there are no more)"""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, size=cap, replace=False))
+
+
+def _sample_rows(a, cap, salt):
+    """a fixed, seeded sample of at most `cap` rows of `a`, kept in their order"""
+    return a if len(a) <= cap else a[_pick(len(a), cap, salt)]
+
+
+def _kmer_columns(hi, lo):
+    """2k-bit k-mers as (hi, lo) uint64 words -> float64 columns of 32 bits each (exact): hi >> 32, hi & M, lo >> 32, lo & M"""
+    cols = []
+    for w in (hi, lo):
+        w = np.asarray(w, dtype=np.uint64)
+        cols += [(w >> np.uint64(32)).astype(np.float64), (w & np.uint64(0xFFFFFFFF)).astype(np.float64)]
+    return np.stack(cols, axis=1)
+
+
+def _read_kmers(bases, n_reads, rl, k, m, salt):
+    """m k-mers at fixed, seeded places of the reads in HBM (n_reads reads of rl bases) -> canonical (hi, lo) uint64 words, first base
+    highest (hi = 0 for k <= 32); k-mers with a base other than ACGT are left out"""
+    rng = np.random.default_rng([DUMP_SEED, salt])
+    start = rng.integers(0, n_reads, m, dtype=np.int64) * rl + rng.integers(0, rl - k + 1, m, dtype=np.int64)
+    idx = torch.from_numpy(start).to(bases.device)[:, None] + torch.arange(k, device=bases.device)
+    c = NUC[bases[idx].cpu().numpy()]
+    c = c[(c < 4).all(axis=1)].astype(np.uint64)
+
+    def pack(cols):
+        v = np.zeros(len(cols), dtype=np.uint64)
+        for j in range(cols.shape[1]):
+            v = (v << np.uint64(2)) | cols[:, j]
+        return v
+    rc = np.uint64(3) - c[:, ::-1]
+    s = max(0, k - 32)
+    fh, fl, rh, rlo = pack(c[:, :s]), pack(c[:, s:]), pack(rc[:, :s]), pack(rc[:, s:])
+    fw = (fh < rh) | ((fh == rh) & (fl <= rlo))
+    return np.where(fw, fh, rh), np.where(fw, fl, rlo)
+
+
+def _unitig_rows(seqss, device):
+    """every sample's unitigs as (length, avg, min, max) rows, sorted: the multiset, whatever order the walks emitted them in"""
+    from metafast_amd import pipeline as P
+    parts = []
+    for sq in seqss:
+        v = sq.device_view()
+        n = v["n"]
+        if not n:
+            continue
+        off = P.device_tensor(v["offsets"], (n + 1) * 8, device).view(torch.int64)
+        cov = [P.device_tensor(v[f], n * 4, device).view(torch.int32).cpu().numpy() if v[f] else np.zeros(n, dtype=np.int32)
+               for f in ("avg", "min", "max")]
+        parts.append(np.stack([(off[1:] - off[:-1]).cpu().numpy()] + cov, axis=1).astype(np.float64))
+    rows = np.concatenate(parts) if parts else np.zeros((0, 4))
+    return rows[np.lexsort(rows.T[::-1])]
+
+
+def _dump_outputs(path, r, stats, bases, n_reads, rl, k, wide, device):
+    """What the timed path handed its caller in the last step, as DIR/<name>.npy in float64 (k-mers split into exact 32-bit columns):
+      matrix               the Bray-Curtis matrix of all samples
+      features             the samples' feature vectors (one row per sample, one column per component)
+      totals               the step's counts in `stats`, those of TOTALS it has, in that order
+      count_histogram      distinct k-mers per count over all counted k-mers, one row per sample of this rank (k <= 31)
+      components           (size, weight, threshold) per component, in the library's order
+      component_kmers      (component, k-mer columns) of a fixed, seeded sample of the components' k-mers
+      kmer_counts          (k-mer columns, count; -1: not kept) of the last sample's table at a fixed, seeded sample of read positions
+      unitigs              (length, avg, min, max) per unitig of this rank's samples, sorted
+    Larger outputs are fixed, seeded samples of rows (_pick); together the files stay under DUMP_MAX_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    out = {"matrix": np.asarray(r["matrix"], dtype=np.float64),
+           "totals": np.array([float(stats[key]) for key in TOTALS if key in stats], dtype=np.float64)}
+    vecs = np.asarray(r["vecs"], dtype=np.float64)
+    if vecs.size > (1 << 20):                 # (a fixed sample of the components, the same columns for every sample)
+        vecs = vecs[:, _pick(vecs.shape[1], max(1, (1 << 20) // len(vecs)), 1)]
+    out["features"] = vecs
+    if not wide:
+        out["count_histogram"] = _sample_rows(np.stack(r["hists"]).astype(np.float64), 32, 2)
+        comps = r["comps"].export()
+        out["components"] = np.array([c[:3] for c in comps], dtype=np.float64).reshape(-1, 3)
+        ends = np.cumsum([len(c[3]) for c in comps], dtype=np.int64)
+        pick = _pick(int(ends[-1]) if len(ends) else 0, 1 << 17, 3)
+        which = np.searchsorted(ends, pick, side="right")
+        starts = ends - np.array([len(c[3]) for c in comps], dtype=np.int64)
+        lo = np.array([comps[c][3][i - starts[c]] for c, i in zip(which.tolist(), pick.tolist())], dtype=np.uint64)
+        hi = np.zeros(len(lo), dtype=np.uint64)
+    else:
+        e = r["comps"].export()
+        out["components"] = np.stack([e["sizes"], e["weights"], e["thr"]], axis=1).astype(np.float64).reshape(-1, 3)
+        ends = e["offsets"][1:].astype(np.int64)
+        pick = _pick(int(ends[-1]) if len(ends) else 0, 1 << 17, 3)
+        which = np.searchsorted(ends, pick, side="right")
+        hi, lo = e["hi"][pick], e["lo"][pick]
+    out["components"] = _sample_rows(out["components"], 1 << 18, 6)
+    out["component_kmers"] = np.column_stack([which.astype(np.float64), _kmer_columns(hi, lo)])
+    khi, klo = _read_kmers(bases, n_reads, rl, k, 1 << 17, 4)
+    good = r["goods"][-1]                     # (the reads in `bases` are the last sample's)
+    cnt = good.lookup([(int(h) << 64) | int(l) for h, l in zip(khi, klo)]) if wide else good.lookup(klo)
+    out["kmer_counts"] = np.column_stack([_kmer_columns(khi, klo), cnt.astype(np.float64)])
+    out["unitigs"] = _sample_rows(_unitig_rows(r["seqss"], device), 1 << 19, 5)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes" % total
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return total
 
 
 def _load_traffic():
@@ -88,16 +209,20 @@ def main_wide(args, ctx, device, rank, world, use_dist=False):
                 gen_s[0] += time.perf_counter() - g0
             yield bases, offsets, n_reads, n_bases
 
-    def step(timings=None):
+    def step(timings=None, keep=False):
         r = P.run_samples_wide(ctx, samples(), k=k, b=args.bad_freq, l=args.min_len, b1=args.b1, b2=args.b2, device=device, timings=timings)
         stats = dict(n_occ=r["n_occ"], n_distinct=int(sum(r["n_distinct"])), n_good=int(sum(g.stats()[0] for g in r["goods"])),
                      n_unitigs=int(sum(len(q) for q in r["seqss"])), n_cutter=int(r["cutter"].stats()[0]), n_components=len(r["comps"]),
                      n_component_kmers=int(r["comps"].stats()[1]), n_reads=n_reads * spg, n_bases=n_bases * spg, n_samples=spg,
                      matrix_checksum=float(np.nansum(r["matrix"])))
+        if not keep:
+            close(r)
+        comm_kind[0] = (r.get("comm") or {}).get("kind")
+        return stats, (r if keep else None)
+
+    def close(r):
         for x in r["goods"] + r["seqss"] + [r["cutter"], r["comps"]]:
             x.close()
-        comm_kind[0] = (r.get("comm") or {}).get("kind")
-        return stats
 
     comm_kind = [None]
 
@@ -108,14 +233,14 @@ def main_wide(args, ctx, device, rank, world, use_dist=False):
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        stats = step()
+        stats, _r = step()
     ctx.reset_timers()
     stage_t = {}
     barrier()
     gen_s[0] = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        stats = step(stage_t)
+    for i in range(args.steps):
+        stats, last = step(stage_t, keep=bool(args.dump_outputs) and i == args.steps - 1)
     barrier()
     elapsed = time.perf_counter() - t0 - gen_s[0]
     if use_dist:
@@ -153,6 +278,10 @@ def main_wide(args, ctx, device, rank, world, use_dist=False):
         "stage_ms_per_step": {kk: round(v / max(args.steps, 1) * 1e3, 3) for kk, v in stage_t.items()},
         "kernels": kern,
     }
+    if last is not None:
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, last, stats, bases, n_reads, rl, k, True, device)
+        close(last)
     return out
 
 
@@ -210,6 +339,21 @@ def _cpu_model():
     return "unknown"
 
 
+def _host_threads():
+    """threads for the CPU baseline: the CPUs this process may use -- OMP_NUM_THREADS when it is set (a share of a shared host), else
+    the CPUs of its affinity mask"""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        n = 0
+    if n > 0:
+        return n
+    try:
+        return len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        return os.cpu_count() or 1
+
+
 def _reference_java(hb, ho, k, cores):
     """the real reference, only if this box has a JVM and $METAFAST_JAR points at an upstream metafast.jar
     (neither ships with this repository); timed on the same sample written out as FASTA, file reading included."""
@@ -241,7 +385,7 @@ def cpu_baseline(bases, offsets, n_reads, rl, k, args):
     are already parsed in memory.  `value` is the with_reader figure."""
     import tempfile
     from oracle import oracle as O          # checker only: CPU baseline leg
-    cores = os.cpu_count() or 1
+    cores = _host_threads()
     m = min(args.cpu_sample_reads, n_reads)
     hb = bases[: m * rl].cpu().numpy()
     td = tempfile.mkdtemp(prefix="mf_cpu_")
@@ -261,7 +405,7 @@ def cpu_baseline(bases, offsets, n_reads, rl, k, args):
     c0 = time.perf_counter()
     d2, o2 = O.cpu_baseline_count(hb[: m2 * rl], ho, k, cores)
     cdt = time.perf_counter() - c0
-    # ("cores" is the contract's key; what it holds is the number of THREADS used = the box's hardware threads, os.cpu_count())
+    # ("cores" is the contract's key; what it holds is the number of THREADS used = the CPUs this process may use, _host_threads())
     return dict(value=round(r["n_occ"] / wr_s, 1), unit="k-mers/s", cores=cores, threads=cores, kind="port", cpu_model=_cpu_model(),
                 sample=f"with_reader: k-mer counter end to end on a FASTA file of the first {m} reads of the same sample "
                        f"({r['n_occ']} k-mer occurrences, {r['distinct']} distinct, {r['written']} written): serial reader + "
@@ -447,7 +591,12 @@ def main():
     ap.add_argument("-l", dest="min_len", type=int, default=100, help="minimal sequence length (100: default; 1200: the CAMI example)")
     ap.add_argument("--b1", type=int, default=1000)
     ap.add_argument("--b2", type=int, default=10000)
+    ap.add_argument("--full", action="store_true", help="also the cli / end_to_end lines, the CPU baseline and the committed profiles of other "
+                                                        "shapes (--no-end-to-end, --no-cpu-baseline leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries ONE line, the JSON; anything libraries print there on the way (RCCL's version banner ...) goes to stderr
     sys.stdout.flush()
@@ -490,7 +639,7 @@ def main():
         return
     spg = max(1, args.samples_per_gpu)
     e2e = {}
-    if not args.no_end_to_end and world == 1:
+    if args.full and not args.no_end_to_end and world == 1:
         try:
             e2e = end_to_end_and_cli(ctx, n_reads, rl, k, args, device, rank * spg)
         except Exception as ex:                       # (never costs the headline line)
@@ -526,29 +675,34 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def step(timings=None):
+    def step(timings=None, keep=False):
+        """keep: hand the step's results back open (the last timed step of a run with --dump-outputs), closed by the caller"""
         r = P.run_samples(ctx, samples(), k=k, b=args.bad_freq, l=args.min_len, b1=args.b1, b2=args.b2, device=device, timings=timings)
         nrec, rbytes = r["goods"][0].records()
         stats = dict(n_occ=r["n_occ"], n_distinct=r["n_distinct"], n_good=sum(len(g) for g in r["goods"]), n_unitigs=sum(len(q) for q in r["seqss"]),
                      n_cutter=len(r["cutter"]), n_cutter_occ=int(r["cutter"].occurrences()), n_components=len(r["comps"]), n_reads=n_reads * spg, n_bases=n_bases * spg,
                      n_records=nrec * spg, record_bytes=rbytes, n_singletons=int(sum(int(h[1]) for h in r["hists"])))
-        for x in r["goods"] + r["seqss"] + [r["cutter"], r["comps"]]:
-            x.close()
+        if not keep:
+            close(r)
         for kk, v in r["comm"].items():
             comm_acc[kk] = v if isinstance(v, str) else comm_acc.get(kk, 0) + v
-        return stats, r["matrix"]
+        return stats, (r if keep else None)
+
+    def close(r):
+        for x in r["goods"] + r["seqss"] + [r["cutter"], r["comps"]]:
+            x.close()
 
     comm_acc = {}
     for _ in range(args.warmup):
-        stats, _m = step()
+        stats, _r = step()
     comm_acc.clear()
     ctx.reset_timers()
     stage_t = {}
     barrier()
     gen_s[0] = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        stats, matrix = step(stage_t)
+    for i in range(args.steps):
+        stats, last = step(stage_t, keep=bool(args.dump_outputs) and i == args.steps - 1)
     barrier()
     elapsed = time.perf_counter() - t0 - gen_s[0]
     if gen_s[0] and "count" in stage_t:
@@ -623,7 +777,7 @@ def main():
             return r
 
         cpu = None
-        if not args.no_cpu_baseline and world == 1:       # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:       # reported at N=1 only
             cpu = cpu_baseline(bases, offsets, n_reads, rl, k, args)
 
         out = {
@@ -639,7 +793,7 @@ def main():
                        "reads_per_gpu": n_reads, "read_len": rl, "k": k, "genome_scale_bp": args.genome_scale,
                        "substitutions_per_base": round(sub16k / 16384, 5)},
             "roofline": roof(dom),
-            "roofline_hash_count": (lambda r: (r.update(other_shapes=_load_other_shapes()) or r) if isinstance(r, dict) and world == 1 else r)(
+            "roofline_hash_count": (lambda r: (r.update(other_shapes=_load_other_shapes()) or r) if isinstance(r, dict) and world == 1 and args.full else r)(
                 roof("k_skm_count" if "k_skm_count" in kern else "k_count")),
             "cpu_baseline": cpu,
             "end_to_end": e2e.get("end_to_end"),
@@ -647,7 +801,7 @@ def main():
             "end_to_end_config2": e2e.get("end_to_end_config2"),
             "cli": e2e.get("cli"),
             "stats": stats,
-            "extension_k63": _load_extension_k63() if world == 1 else None,
+            "extension_k63": _load_extension_k63() if world == 1 and args.full else None,
             # counting runs that threw their slices away and started over with more because a buffer found no place in the arena (8 x 200 M reads
             # at k = 21 on one GPU did in round 4 until the temporary lists were halved): 0 on every committed shape
             "slice_restarts": ctx.stat("slice_restarts"),
@@ -660,10 +814,14 @@ def main():
             "stage_ms_per_step": {kk: round(v / max(args.steps, 1) * 1e3, 3) for kk, v in stage_t.items()},
             "kernels": kern,
         }
+        if last is not None:
+            _dump_outputs(args.dump_outputs, last, stats, bases, n_reads, rl, k, False, device)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)
         os.dup2(2, 1)
+    if last is not None:
+        close(last)
     if use_dist:
         dist.destroy_process_group()
 
