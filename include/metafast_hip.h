@@ -444,6 +444,33 @@ int mf_features_reads_device_selected(mf_ctx *ctx, mf_comps *c, const void *d_ba
 int mf_features_reads_selected(mf_ctx *ctx, const char *components_bin, const char *const *files, int nfiles, int k, int threshold,
                                mf_table *selected, const char *vec_path, const char *breadth_path);
 
+/* ---- group comparison: the multi-sample join (pipelines 3 and 5 of the reference's Pipelines.md; mf_stats.hip) -------------------
+ * Each k-mer of the union of N samples gets its row of per-sample presence / counts and a decision is made over the row.  Keys are the
+ * 64-bit values of the tables / files (below 2^62, as for any k <= 31; a larger one is an error); result tables have k = 31 and come in
+ * ascending key order.  Option "stats_slices" (mf_ctx_set_option) forces the number of hash slices of the key space (0: as many as
+ * free HBM asks for); the result does not depend on it.
+ *
+ * StatsKmersFinder.runImpl (src/tools/StatsKmersFinder.java:89-297), samples numbered A first, then B; b = --maximal-bad-frequence:
+ * sample j holds x iff its count of x is > b; chi-squared test on (n1A, n1B) at p_chi2, then (p_mw > 0) Mann-Whitney on
+ * v_j = (c_j * M) / F_j (F_j = sum of sample j's counts, M = sum of all F_j / N), the kept k-mers to group A or B with
+ * (short)(int)mean.  chi = the chi-squared survivors with value 1.  counters[9] (MF_STATS_COUNTERS): k-mers, scarce, present in all,
+ * unique, rejected by chi-squared, rejected by Mann-Whitney, group A, group B, unique left (the reference's log lines :284-296).
+ * 1 <= |A|, 1 <= |B|, |A| + |B| <= 1024. */
+#define MF_STATS_COUNTERS 9
+int mf_stats_kmers_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *const *b, int nb, int max_bad, double p_chi2, double p_mw,
+                          mf_table **chi, mf_table **group_a, mf_table **group_b, uint64_t *counters);
+/* File form (the CLI's): .kmers.bin files of the two groups (duplicate records of a k-mer in one file: presence = some record > b, count =
+ * saturating sum, F_j = sum of all records > 0, IOUtils.loadKmersFreq) -> <out_dir>/filtered_chisquared.kmers.bin + .stat.txt,
+ * filtered_groupA.kmers.bin, filtered_groupB.kmers.bin; counters may be NULL. */
+int mf_stats_kmers(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, int max_bad, double p_chi2, double p_mw,
+                   const char *out_dir, uint64_t *counters);
+/* KmersSamplesCounter.runImpl (src/tools/KmersSamplesCounter.java:69-140): n(x) = number of samples whose count of x is > max_bad, for
+ * every x with n(x) > 0; at most 32767 samples. */
+int mf_kmers_samples_count_tables(mf_ctx *ctx, mf_table *const *t, int n, int max_bad, mf_table **out);
+/* File form: -> kmers_bin (records (x, n(x))) and stat_txt (histogram of n, may be NULL); *n_kmers (may be NULL) = records written */
+int mf_kmers_samples_count(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
+                           uint64_t *n_kmers);
+
 /* ---- A13  Bray-Curtis ---------------------------------------------------------------- */
 /* replaces DistanceMatrixCalculatorMain.brayCurtisDistance (src/tools/DistanceMatrixCalculatorMain.java:
  * 140-152): d = sum|a-b| / sum(|a|+|b|) on raw vectors; vecs is row-major [n_samples][n_comp]. */

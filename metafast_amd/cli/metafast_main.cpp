@@ -30,6 +30,12 @@
 #include <vector>
 #include "../../include/metafast_hip.h"
 
+// the group-comparison entry points are reached through weak references: a build of this driver against a library without them (the
+// sanitizer build links a stub of the older entry points) still links, and the tools stop with a message
+extern "C" int mf_stats_kmers(mf_ctx *, const char *const *, int, const char *const *, int, int, double, double, const char *, uint64_t *)
+    __attribute__((weak));
+extern "C" int mf_kmers_samples_count(mf_ctx *, const char *const *, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
+
 using std::string;
 using std::vector;
 
@@ -115,6 +121,11 @@ struct Args {
         char *e; long v = strtol(it->second[0].c_str(), &e, 10); if (*e) die("Can't parse integer value '%s' of option --%s", it->second[0].c_str(), k.c_str());
         return (int)v;
     }
+    double getd(const string &k, double def) const {
+        auto it = opt.find(k); if (it == opt.end() || it->second.empty()) return def;
+        char *e; double v = strtod(it->second[0].c_str(), &e); if (*e || it->second[0].empty()) die("Can't parse double value '%s' of option --%s", it->second[0].c_str(), k.c_str());
+        return v;
+    }
     vector<string> list(const string &k) const { auto it = opt.find(k); return it == opt.end() ? vector<string>() : it->second; }
 };
 struct OptDef { const char *lng; const char *sht; bool multi; bool flag; };
@@ -137,6 +148,7 @@ static const OptDef OPTS[] = {
     {"kmers-file", "kf", false, false}, {"output-file", "o", false, false}, {"split", "", false, true}, {"long", "", false, true},
     {"use-reads-for-calculating-features", "", false, true}, {"device", "", false, false}, {"devices", "", false, false},
     {"positiveReads", "pos", true, false}, {"negativeReads", "neg", true, false}, {"filter-kmers", "", true, false}, {"max-thresh", "", false, false},
+    {"a-kmers", "A", true, false}, {"b-kmers", "B", true, false}, {"p-value-chi2", "pchi2", false, false}, {"p-value-mw", "pmw", false, false},
 };
 // `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
@@ -147,11 +159,12 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
     auto long_of_short = [&](const string &s) -> string {
         if (s == "i") {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
-            if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter") return "k-mers";
+            if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers") return "k-mers";
             if (tool == "component-cutter") return "sequences";
             return "reads";
         }
-        if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter") ? "maximal-bad-frequence" : "maximal-bad-frequency";
+        if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers")
+                                 ? "maximal-bad-frequence" : "maximal-bad-frequency";
         if (s == "l") return (tool == "seq-builder" || tool == "seq-builder-many") ? "sequence-len" : "min-seq-len";
         if (s == "o") return (tool == "view" || tool == "bin2fasta") ? "output-file" : "output-dir";
         if (s == "cf") return "components-file";                           // ViewMain.java:45, BinaryToFasta.java:47
@@ -841,6 +854,8 @@ static const char *TOOLS_TEXT =
     "heatmap-maker\t\tCluster the samples of a distance matrix and renumber it (no image)\n"
     "kmer-counter-posneg\tCount k-mers for files from two groups independently\n"
     "kmers-filter\t\tFilter k-mers from test set according to known samples\n"
+    "kmers-samples-counter\tCount number of samples containing k-mers from multiple samples\n"
+    "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -890,6 +905,13 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
         v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
              PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV("max-thresh", a.get("max-thresh", "0")),
              PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
+    } else if (tool == "kmers-samples-counter") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
+             PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
+    } else if (tool == "stats-kmers") {
+        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV("p-value-chi2", a.get("p-value-chi2", "0.05")),
+             PV("p-value-mw", a.get("p-value-mw", "0.05")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")),
+             PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -913,7 +935,8 @@ int main(int argc, char **argv) {
         return 0;
     }
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
-                                  "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter"};
+                                  "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
+                                  "kmers-samples-counter", "stats-kmers"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -983,6 +1006,8 @@ int main(int argc, char **argv) {
     else if (tool == "matrix-builder") need("reads", "i");
     else if (tool == "kmer-counter-posneg") { need("k", "k"); need("positiveReads", "pos"); need("negativeReads", "neg"); }
     else if (tool == "kmers-filter") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
+    else if (tool == "kmers-samples-counter") { need("k", "k"); need("k-mers", "i"); }
+    else if (tool == "stats-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1057,6 +1082,50 @@ int main(int argc, char **argv) {
         }
         mf_table_destroy(filter);
         outs = {written.empty() ? PV::null("resulting-kmers-file") : PV::file("resulting-kmers-file", written.back())};
+    } else if (tool == "kmers-samples-counter") {
+        // KmersSamplesCounter.java:69-140: the number of input files that hold each k-mer with a count > b
+        check_k(k);
+        const int b = a.geti("maximal-bad-frequence", 1);
+        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
+        const vector<string> files = a.list("k-mers");
+        mkdirs(out_dir); mkdirs(st_dir);
+        if (!mf_kmers_samples_count) die("kmers-samples-counter: this build of the library has no mf_kmers_samples_count");
+        mf_ctx *ctx = ctx_of(e, a);
+        auto fp = cptrs(files);
+        const string out = out_dir + "/n_samples.kmers.bin", st = st_dir + "/n_samples.stat.txt";
+        uint64_t c = 0;
+        check(mf_kmers_samples_count(ctx, fp.data(), (int)fp.size(), b, k, out.c_str(), st.c_str(), &c));
+        logmsg("INFO", "%s k-mers found, %s (100.0%%) of them is good (not erroneous)", group_digits(c).c_str(), group_digits(c).c_str());
+        if (c == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
+        logmsg("INFO", "Good k-mers printed to %s", out.c_str());
+        outs = {PV::file("resulting-kmers-file", out)};
+    } else if (tool == "stats-kmers") {
+        // StatsKmersFinder.java:89-297 (no -k: the join works on the files' 64-bit keys)
+        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers");
+        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
+        const int b = a.geti("maximal-bad-frequence", 0);
+        const string out_dir = a.get("output-dir", wd + "/kmers");
+        mkdirs(out_dir);
+        if (!mf_stats_kmers) die("stats-kmers: this build of the library has no mf_stats_kmers");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("INFO", "Loading k-mers occurrences...");
+        auto pa = cptrs(af), pb = cptrs(bf);
+        uint64_t c[MF_STATS_COUNTERS] = {0};
+        check(mf_stats_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), b, pchi2, pmw, out_dir.c_str(), c));
+        logmsg("INFO", "Survived after chi-squared test k-mers printed to: %s", (out_dir + "/filtered_chisquared.kmers.bin").c_str());
+        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
+        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
+        logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
+        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
+        logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
+        logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7]));
+        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[8]);
+        logmsg("INFO", "Total group A k-mers = %llu", (unsigned long long)c[6]);
+        logmsg("INFO", "Total group B k-mers = %llu", (unsigned long long)c[7]);
+        logmsg("DEBUG", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
+        logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
+        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
+        outs = {PV::files("resulting-kmers-file", {out_dir + "/filtered_groupA.kmers.bin"})};
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

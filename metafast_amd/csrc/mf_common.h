@@ -118,6 +118,7 @@ struct mf_ctx {
     int64_t opt_wide_ablate = 0;         // ... TIMING ONLY, wrong tables: 1 = large buckets skipped, 2 = the representatives' walk skipped
     int64_t opt_wide_passes = 0;   // mf_count_wide_device: passes over the reads, each for one prefix class of the canonical k-mers (0 = as many as the memory asks for; tests force a number)
     int64_t opt_cc_sparse = 1;     // component cutter: threshold levels that few vertices reach run on a list of them (0: every level visits all vertices)
+    int64_t opt_stats_slices = 0;  // multi-sample join (mf_stats.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
     int64_t opt_dcc_sparse = 0;    // sharded cutter, levels after the first: 1 = always the sparse set-up of the arrays over all vertex ids (tests)
     int64_t opt_dcc_test_fail = 0; int64_t dcc_test_calls[3] = {0, 0, 0};   // tests only: which * 1000 + n makes the n-th call of mf_dcc_merge (which = 1) / mf_dcc_level_local (2) on this context fail
     int64_t opt_nbr_global = 0;    // 1: neighbour lookups of the graph kernels through the HBM index only (A/B of mf_nbr.h)

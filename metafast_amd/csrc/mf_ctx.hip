@@ -197,6 +197,7 @@ extern "C" int mf_ctx_set_option(mf_ctx *ctx, const char *name, int64_t v) {
     else if (s == "dcc_sparse") ctx->opt_dcc_sparse = v;
     else if (s == "dcc_test_fail") { ctx->opt_dcc_test_fail = v; ctx->dcc_test_calls[1] = ctx->dcc_test_calls[2] = 0; }
     else if (s == "cc_sparse") ctx->opt_cc_sparse = v;
+    else if (s == "stats_slices") { if (v < 0 || v > 4096) return mf_set_error("stats_slices must be in [0, 4096]"); ctx->opt_stats_slices = v; }
     else if (s == "gz_device_min_bytes") ctx->opt_gz_device_min = v;
     else if (s == "gz_piece_bytes") { if (v < 4096) return mf_set_error("gz_piece_bytes must be at least 4096"); ctx->opt_gz_piece = v; }
     else if (s == "ut_double_after") { if (v < 1 || v > 64) return mf_set_error("ut_double_after must be in [1, 64]"); ctx->opt_ut_double_after = v; }

@@ -659,13 +659,17 @@ extern "C" int mf_table_write_kmers(const mf_table *t, int threshold, const char
 // the files go to HBM as they are and are decoded there; records with freq <= freq_threshold are dropped; a k-mer that
 // occurs in several files gets the (saturating) sum
 int mf_table_from_device_pairs(mf_ctx *ctx, const uint64_t *d_keys, const uint16_t *d_vals, uint64_t n, int k, mf_table **out);
-extern "C" int mf_table_load_kmers(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_table **out) {
-    mf_range rng_("mf:load_kmers(file)");
+int mf_sum_counts(mf_ctx *ctx, const uint16_t *d_counts, uint64_t n, uint64_t *total);
+// freq_sum (may be NULL): the sum of the count fields of the records with count > freq_threshold, before duplicates are summed with
+// saturation -- IOUtils.loadKmersFreq(...).second() (src/io/IOUtils.java:403-435) for freq_threshold = 0; such a load reads the files
+// themselves (a table of the file cache has summed them already)
+int mf_table_load_kmers_sum(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_table **out, uint64_t *freq_sum) {
     if (!ctx || !out || (nfiles && !files)) return mf_set_error("mf_table_load_kmers: NULL argument");
     *out = nullptr;
+    if (freq_sum) *freq_sum = 0;
     MF_HIP(hipSetDevice(ctx->device));
     io_timer tm("load_kmers");
-    if (nfiles == 1) {
+    if (nfiles == 1 && !freq_sum) {
         mf_file_entry *e = file_cache_get(ctx, files[0]);
         if (e && e->t && e->t->k == k) {
             // (the file's records all have count > e->thr: a threshold at or below that keeps every one of them -- the same table)
@@ -718,16 +722,23 @@ extern "C" int mf_table_load_kmers(mf_ctx *ctx, const char *const *files, int nf
     // keep the records with freq > freq_threshold (encoded as freq + 1 > 0)
     mf_table *all = nullptr;
     {
-        mf_table tmp; tmp.ctx = ctx; tmp.k = k; tmp.n = total; tmp.d_keys = dk.p; tmp.d_counts = dc.p; tmp.owns_arrays = false;
+        // (cut_thr = 0: the cut keeps no histogram of what it drops -- the table it makes is only the input of the one below, and the
+        // encoded counts run up to 32768, one past the histogram's last bin)
+        mf_table tmp; tmp.ctx = ctx; tmp.k = k; tmp.n = total; tmp.d_keys = dk.p; tmp.d_counts = dc.p; tmp.owns_arrays = false; tmp.cut_thr = 0;
         MF_TRY(mf_table_filter(&tmp, 0, &all));
     }
     k_counts_minus_one<<<(unsigned)((all->n + 255) / 256 + 1), 256, 0, ctx->stream>>>(all->d_counts, all->n);
     int rc = mf_table_from_device_pairs(ctx, all->d_keys, all->d_counts, all->n, k, out);
+    if (rc == MF_OK && freq_sum) rc = mf_sum_counts(ctx, all->d_counts, all->n, freq_sum);
     const hipError_t se = hipStreamSynchronize(ctx->stream);
     tm.lap("filter+partition");
     mf_table_destroy(all);                                  // (on every path: the synchronise used to return past it)
     if (se != hipSuccess) return mf_set_error("hipStreamSynchronize failed: %s", hipGetErrorString(se));
     return rc;
+}
+extern "C" int mf_table_load_kmers(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_table **out) {
+    mf_range rng_("mf:load_kmers(file)");
+    return mf_table_load_kmers_sum(ctx, files, nfiles, freq_threshold, k, out, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

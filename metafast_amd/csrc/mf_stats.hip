@@ -1,0 +1,693 @@
+// mf_stats.hip -- the multi-sample join of k-mer tables behind stats-kmers (src/tools/StatsKmersFinder.java:89-297) and
+// kmers-samples-counter (src/tools/KmersSamplesCounter.java:69-140).
+//
+// Passes:
+//   union   every sample's keys with count > b go into an HBM open-addressed table of 16-byte slots {key, presence, row}; the
+//           presence word takes one atomic add per (sample, key): 1 for group A (or for every sample: kmers-samples-counter),
+//           1 << 16 for group B.  The key space is cut into S hash slices (top bits of fmix64), one union table per slice, so that
+//           the table fits in free HBM; the samples are streamed once per slice.
+//   select  the chi-squared decision depends on (n1A, n1B) only: the host evaluates StatsKmersFinder.chisq (float / double, in
+//           the reference's order, no contraction) into a (nA+1) x (nB+1) flag table and the kernel looks it up.  Survivors get a
+//           row number.
+//   gather  the samples again at threshold 0: every entry of a survivor fills its cell of a u16 [rows][N] count matrix.
+//   row     v_j = ((double)c_j * M) / F_j, 2 * U1 = sum over pairs of 2 [vA > vB] + [vA == vB] in integers, the Mann-Whitney test
+//           as 2 * Umin < T for one integer T the host finds from the p-value formula, the in-order means, the group and Java's
+//           (short)(int) cast.  One thread per row up to MF_STATS_THREAD_N samples, one wave per row above.
+// No floating point of the decisions but v_j and the means runs on the device, and those are IEEE double operations in the
+// reference's order (no contraction in this file).
+#pragma clang fp contract(off)
+#include "mf_common.h"
+#include <algorithm>
+#include <cmath>
+#include <functional>
+#include <memory>
+#include <sys/stat.h>
+
+#define MF_STATS_MAX_N 1024          // samples of one stats-kmers run (the row kernels keep a row's values in LDS)
+#define MF_STATS_THREAD_N 32         // up to this many samples: one thread per row (values in LDS, 64 KiB per 256 rows), else a wave per row
+#define MF_STATS_KEY_LIMIT (1ull << 62)   // keys of k <= 31; the union table's empty marker lies above
+static constexpr uint32_t MF_NO_ROW = 0xFFFFFFFFu;
+
+struct mf_uslot { uint64_t key; uint32_t cnt; uint32_t row; };
+
+int mf_sum_counts(mf_ctx *ctx, const uint16_t *d_counts, uint64_t n, uint64_t *total);
+int mf_table_load_kmers_sum(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_table **out, uint64_t *freq_sum);
+
+// slice of a key: the top 32 bits of fmix64 scaled to [0, S); the slot inside a slice's table comes from the LOW bits
+__device__ __forceinline__ uint32_t mf_stats_slice(uint64_t h, uint32_t S) { return (uint32_t)(((h >> 32) * (uint64_t)S) >> 32); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// kernels
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ void k_stats_init(mf_uslot *__restrict__ slots, uint64_t cap) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {
+        ulonglong2 v; v.x = MF_EMPTY; v.y = (uint64_t)MF_NO_ROW << 32;
+        *reinterpret_cast<ulonglong2 *>(&slots[i]) = v;
+    }
+}
+
+// flags: bit 0 = a key >= 2^62, bit 1 = the table is full (never with the sizes the host picks; an error, never a write out of bounds)
+__global__ __launch_bounds__(256) void k_stats_union(mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
+                                                     const uint16_t *__restrict__ cnts, uint64_t n, int thr, uint32_t add, uint32_t S, uint32_t s,
+                                                     unsigned long long *__restrict__ n_union, unsigned int *__restrict__ flags) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if ((int)cnts[i] <= thr) continue;
+        const uint64_t key = keys[i];
+        if (key >= MF_STATS_KEY_LIMIT) { atomicOr(flags, 1u); continue; }
+        const uint64_t h = mf_hash64(key);
+        if (mf_stats_slice(h, S) != s) continue;
+        uint64_t p = h & mask;
+        bool done = false;
+        for (uint64_t probe = 0; probe <= mask; probe++) {
+            const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long *>(&slots[p].key), (unsigned long long)MF_EMPTY,
+                                                     (unsigned long long)key);
+            if (old == MF_EMPTY || old == key) {
+                if (old == MF_EMPTY) atomicAdd(n_union, 1ull);
+                atomicAdd(&slots[p].cnt, add);
+                done = true;
+                break;
+            }
+            p = (p + 1) & mask;
+        }
+        if (!done) atomicOr(flags, 2u);
+    }
+}
+
+// wave sum of a per-lane counter into a 64-bit global counter
+__device__ __forceinline__ void mf_stats_add(unsigned long long *ctr, uint32_t x) {
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
+    if (mf_lane() == 0 && x) atomicAdd(ctr, (unsigned long long)x);
+}
+
+// stats-kmers pass 1 over the union (StatsKmersFinder.java:129-162): counters [0] n, [1] scarce, [2] in all, [3] unique, [4] chi-squared
+// rejected; survivors get row numbers and their keys go to rkeys.  (uniform trip count: every lane reaches mf_wave_reserve)
+__global__ __launch_bounds__(256) void k_stats_select(mf_uslot *__restrict__ slots, uint64_t cap, const uint8_t *__restrict__ chi_keep, int na, int nb,
+                                                      int scarce_max, uint64_t *__restrict__ rkeys, unsigned int *__restrict__ cursor,
+                                                      unsigned long long *__restrict__ ctr) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t c_n = 0, c_scarce = 0, c_all = 0, c_uniq = 0, c_rej = 0;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < cap; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        bool keep = false;
+        uint64_t key = MF_EMPTY;
+        if (i < cap) {
+            key = slots[i].key;
+            if (key != MF_EMPTY) {
+                const uint32_t c = slots[i].cnt;
+                const int n1a = (int)(c & 0xFFFFu), n1b = (int)(c >> 16);
+                c_n++;
+                if (n1a + n1b <= scarce_max) c_scarce++;
+                else if (n1a + n1b == na + nb) c_all++;
+                else {
+                    if (n1a == 0 || n1b == 0) c_uniq++;
+                    if (chi_keep[(size_t)n1a * (size_t)(nb + 1) + (size_t)n1b]) keep = true;
+                    else c_rej++;
+                }
+            }
+        }
+        const uint32_t r = mf_wave_reserve(cursor, keep ? 1u : 0u);
+        if (keep) { slots[i].row = r; rkeys[r] = key; }
+    }
+    mf_stats_add(&ctr[0], c_n); mf_stats_add(&ctr[1], c_scarce); mf_stats_add(&ctr[2], c_all); mf_stats_add(&ctr[3], c_uniq); mf_stats_add(&ctr[4], c_rej);
+}
+
+// kmers-samples-counter: every union entry -> (key, number of samples)
+__global__ __launch_bounds__(256) void k_stats_nsamples(const mf_uslot *__restrict__ slots, uint64_t cap, uint64_t *__restrict__ okeys,
+                                                        uint16_t *__restrict__ ovals, unsigned int *__restrict__ cursor) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < cap; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        const bool here = i < cap && slots[i].key != MF_EMPTY;
+        const uint32_t r = mf_wave_reserve(cursor, here ? 1u : 0u);
+        if (here) { okeys[r] = slots[i].key; ovals[r] = (uint16_t)slots[i].cnt; }
+    }
+}
+
+// one sample's entries (count > 0) into its column of the survivors' count matrix
+__global__ __launch_bounds__(256) void k_stats_gather(const mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
+                                                      const uint16_t *__restrict__ cnts, uint64_t n, uint32_t S, uint32_t s, uint32_t col, uint32_t N,
+                                                      uint16_t *__restrict__ mat) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint16_t c = cnts[i];
+        if (!c) continue;
+        const uint64_t key = keys[i];
+        if (key >= MF_STATS_KEY_LIMIT) continue;
+        const uint64_t h = mf_hash64(key);
+        if (mf_stats_slice(h, S) != s) continue;
+        uint64_t p = h & mask;
+        for (uint64_t probe = 0; probe <= mask; probe++) {
+            const ulonglong2 raw = *reinterpret_cast<const ulonglong2 *>(&slots[p]);
+            if (raw.x == key) {
+                const uint32_t row = (uint32_t)(raw.y >> 32);
+                if (row != MF_NO_ROW) mat[(uint64_t)row * N + col] = c;
+                break;
+            }
+            if (raw.x == MF_EMPTY) break;
+            p = (p + 1) & mask;
+        }
+    }
+}
+
+struct mf_stats_row_args {
+    const uint16_t *mat; const uint64_t *rkeys; uint64_t m;
+    int na, nb;
+    const double *F; double M;
+    int mw; uint32_t T;                                  // mw != 0: keep iff 2 * Umin < T
+    uint64_t *ka, *kb; uint16_t *va, *vb;                 // group A / B outputs
+    unsigned int *cur;                                    // [0] A, [1] B
+    unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] unique left
+};
+// Java's (short)(int)x: NaN -> 0, saturation to int, low 16 bits (JLS 5.1.3)
+__device__ __forceinline__ uint16_t mf_java_short(double x) {
+    int32_t i;
+    if (x != x) i = 0;
+    else if (x >= 2147483647.0) i = 2147483647;
+    else if (x <= -2147483648.0) i = (-2147483647 - 1);
+    else i = (int32_t)x;                                  // (in range: truncation toward zero)
+    return (uint16_t)(uint32_t)i;
+}
+// decision + output of one row: group 0 (A) / 1 (B) / -1 (rejected by the Mann-Whitney test) and the value
+__device__ __forceinline__ int mf_stats_group(bool pass, double meanA, double meanB, uint16_t *val) {
+    if (!pass) return -1;
+    if (meanA > meanB) { *val = mf_java_short(meanA); return 0; }
+    *val = mf_java_short(meanB);
+    return 1;
+}
+__device__ __forceinline__ void mf_stats_flush(unsigned long long *ctr, uint32_t c_mw, uint32_t c_a, uint32_t c_b, uint32_t c_ul) {
+    mf_stats_add(&ctr[5], c_mw); mf_stats_add(&ctr[6], c_a); mf_stats_add(&ctr[7], c_b); mf_stats_add(&ctr[8], c_ul);
+}
+
+// one thread per row: the row's N values in LDS, sample j of thread t at v[j * 256 + t] (no bank conflicts)
+__global__ __launch_bounds__(256) void k_stats_rows_thread(mf_stats_row_args a) {
+    extern __shared__ double vs[];
+    const int N = a.na + a.nb;
+    uint32_t c_mw = 0, c_a = 0, c_b = 0, c_ul = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * blockDim.x; r0 < a.m; r0 += stride) {   // uniform trip count (mf_wave_reserve)
+        const uint64_t r = r0 + threadIdx.x;
+        int grp = -1; uint16_t val = 0;
+        if (r < a.m) {
+            double *v = vs + threadIdx.x;
+            const uint16_t *row = a.mat + r * (uint64_t)N;
+            bool nan_a = false;
+            for (int j = 0; j < N; j++) {
+                const double x = ((double)row[j] * a.M) / a.F[j];
+                v[(size_t)j * 256] = x;
+                if (j < a.na && x != x) nan_a = true;
+            }
+            bool pass = true;
+            if (a.mw) {
+                if (nan_a) pass = false;
+                else {
+                    uint32_t u2 = 0;
+                    for (int i = 0; i < a.na; i++) {
+                        const double x = v[(size_t)i * 256];
+                        for (int j = a.na; j < N; j++) { const double y = v[(size_t)j * 256]; u2 += (x > y ? 2u : 0u) + (x == y ? 1u : 0u); }
+                    }
+                    const uint32_t tot = 2u * (uint32_t)a.na * (uint32_t)a.nb, u2o = tot - u2;
+                    pass = (u2 < u2o ? u2 : u2o) < a.T;
+                }
+            }
+            double sa = 0.0, sb = 0.0;
+            for (int j = 0; j < a.na; j++) sa += v[(size_t)j * 256];
+            for (int j = a.na; j < N; j++) sb += v[(size_t)j * 256];
+            const double meanA = sa / (double)a.na, meanB = sb / (double)a.nb;
+            grp = mf_stats_group(pass, meanA, meanB, &val);
+            c_mw += grp < 0; c_a += grp == 0; c_b += grp == 1;
+            c_ul += grp >= 0 && (meanA == 0.0 || meanB == 0.0);
+        }
+        const uint32_t ia = mf_wave_reserve(&a.cur[0], grp == 0 ? 1u : 0u);
+        const uint32_t ib = mf_wave_reserve(&a.cur[1], grp == 1 ? 1u : 0u);
+        if (grp == 0) { a.ka[ia] = a.rkeys[r]; a.va[ia] = val; }
+        else if (grp == 1) { a.kb[ib] = a.rkeys[r]; a.vb[ib] = val; }
+    }
+    mf_stats_flush(a.ctr, c_mw, c_a, c_b, c_ul);
+}
+
+// one wave per row (N > MF_STATS_THREAD_N): the lanes compute the row's values into LDS, then share out the A x B pairs
+__global__ __launch_bounds__(256) void k_stats_rows_wave(mf_stats_row_args a) {
+    __shared__ double vs[4][MF_STATS_MAX_N];
+    const int N = a.na + a.nb, w = threadIdx.x >> 6, lane = mf_lane();
+    double *v = vs[w];
+    uint32_t c_mw = 0, c_a = 0, c_b = 0, c_ul = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * 4; r0 < a.m; r0 += (uint64_t)gridDim.x * 4) {   // block-uniform trip count
+        const uint64_t r = r0 + (uint64_t)w;
+        const bool live = r < a.m;
+        bool nan_a = false;
+        if (live) {
+            const uint16_t *row = a.mat + r * (uint64_t)N;
+            for (int j = lane; j < N; j += 64) {
+                const double x = ((double)row[j] * a.M) / a.F[j];
+                v[j] = x;
+                if (j < a.na && x != x) nan_a = true;
+            }
+        }
+        __syncthreads();
+        const bool any_nan_a = __any(nan_a);
+        bool pass = true;
+        if (live && a.mw) {
+            if (any_nan_a) pass = false;
+            else {
+                uint32_t u2 = 0;
+                for (int i = 0; i < a.na; i++) {
+                    const double x = v[i];
+                    for (int j = a.na + lane; j < N; j += 64) { const double y = v[j]; u2 += (x > y ? 2u : 0u) + (x == y ? 1u : 0u); }
+                }
+                for (int d = 32; d >= 1; d >>= 1) u2 += __shfl_xor(u2, d, 64);
+                const uint32_t tot = 2u * (uint32_t)a.na * (uint32_t)a.nb, u2o = tot - u2;
+                pass = (u2 < u2o ? u2 : u2o) < a.T;
+            }
+        }
+        if (live && lane == 0) {
+            double sa = 0.0, sb = 0.0;
+            for (int j = 0; j < a.na; j++) sa += v[j];
+            for (int j = a.na; j < N; j++) sb += v[j];
+            int grp = -1; uint16_t val = 0;
+            const uint64_t key = a.rkeys[r];
+            const double meanA = sa / (double)a.na, meanB = sb / (double)a.nb;
+            grp = mf_stats_group(pass, meanA, meanB, &val);
+            c_mw += grp < 0; c_a += grp == 0; c_b += grp == 1;
+            c_ul += grp >= 0 && (meanA == 0.0 || meanB == 0.0);
+            if (grp == 0) { const uint32_t i = atomicAdd(&a.cur[0], 1u); a.ka[i] = key; a.va[i] = val; }
+            else if (grp == 1) { const uint32_t i = atomicAdd(&a.cur[1], 1u); a.kb[i] = key; a.vb[i] = val; }
+        }
+        __syncthreads();
+    }
+    mf_stats_flush(a.ctr, c_mw, c_a, c_b, c_ul);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host: the decisions' tables (StatsKmersFinder.chisq :300-316; commons-math3 3.6.1 MannWhitneyUTest.calculateAsymptoticPValue)
+// ---------------------------------------------------------------------------------------------------------------------------
+static bool chisq_keep(float c0, float c1, float p0, float p1, double value) {
+    float tmp = c0;
+    c0 = 100 * c0 / (c0 + c1);
+    c1 = 100 * c1 / (tmp + c1);
+    tmp = p0;
+    p0 = 100 * p0 / (p0 + p1);
+    p1 = 100 * p1 / (tmp + p1);
+    const float gr_1 = c0 + c1, gr_2 = p0 + p1, all = gr_1 + gr_2;
+    const float x1 = gr_1 / all * (p1 + c1), x2 = gr_1 / all * (p0 + c0), x3 = gr_2 / all * (p1 + c1), x4 = gr_2 / all * (p0 + c0);
+    const double d1 = (double)std::fabs(p1 - x1) - 0.5, d2 = (double)std::fabs(p0 - x2) - 0.5, d3 = (double)std::fabs(c1 - x3) - 0.5,
+                 d4 = (double)std::fabs(c0 - x4) - 0.5;
+    double kk = d1 * d1 / (double)x1;
+    kk = kk + d2 * d2 / (double)x2;
+    kk = kk + d3 * d3 / (double)x3;
+    kk = kk + d4 * d4 / (double)x4;
+    return value < kk;                                    // (NaN: rejected)
+}
+// ChiSquaredDistribution(1).inverseCumulativeProbability(1 - p): P(X > q) = erfc(sqrt(q / 2)) = 1 - (1 - p), by bisection
+static double chi2_1_quantile(double p_chi2) {
+    const double P = 1.0 - p_chi2, tail = 1.0 - P;
+    if (P >= 1.0) return INFINITY;
+    if (P <= 0.0) return 0.0;
+    double lo = 0.0, hi = 1.0;
+    while (std::erfc(std::sqrt(hi / 2.0)) > tail && hi < 1e300) hi *= 2.0;
+    for (int it = 0; it < 400 && lo < hi; it++) {
+        const double mid = lo + (hi - lo) / 2.0;
+        if (mid <= lo || mid >= hi) break;
+        if (std::erfc(std::sqrt(mid / 2.0)) > tail) lo = mid; else hi = mid;
+    }
+    return hi;
+}
+static double mw_pvalue(double umin, int n1, int n2) {
+    const long long prod = (long long)n1 * n2;
+    const double EU = (double)prod / 2.0, VarU = (double)(prod * (long long)(n1 + n2 + 1)) / 12.0;
+    const double z = (umin - EU) / std::sqrt(VarU);
+    double cdf;
+    if (std::fabs(z) > 40.0) cdf = z < 0 ? 0.0 : 1.0;
+    else cdf = 0.5 * std::erfc(-z / std::sqrt(2.0));
+    return 2 * cdf;
+}
+// p grows with Umin: the smallest 2 * Umin in [0, nA nB] whose p is not < pmw (nA nB + 1: every row passes)
+static uint32_t mw_threshold(int na, int nb, double pmw) {
+    const uint32_t top = (uint32_t)na * (uint32_t)nb;
+    for (uint32_t u2 = 0; u2 <= top; u2++)
+        if (!(mw_pvalue(u2 / 2.0, na, nb) < pmw)) return u2;
+    return top + 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host: the join
+// ---------------------------------------------------------------------------------------------------------------------------
+// a sample for a pass: pass 0 = presence (entries with count > b count), pass 1 = counts (threshold 0) + F_j.  *own: destroy after use.
+using stats_get = std::function<int(int j, int pass, mf_table **t, bool *own, uint64_t *F)>;
+
+static uint64_t pow2_ge(uint64_t x) { uint64_t p = 1; while (p < x) p <<= 1; return p; }
+
+// slices and union-table capacity for an upper bound `total` of the entries that go in
+static int plan_slices(mf_ctx *ctx, uint64_t total, uint32_t *S_out, uint64_t *cap_out) {
+    uint32_t S = (uint32_t)std::max<int64_t>(ctx->opt_stats_slices, 0);
+    auto cap_of = [&](uint32_t s) {
+        const double per = (double)total / s;
+        return pow2_ge((uint64_t)(2.0 * (per + 6.0 * std::sqrt(per) + 1024.0)));
+    };
+    if (!S) {
+        size_t fr = 0, tot = 0;
+        MF_HIP(hipMemGetInfo(&fr, &tot));
+        const double budget = 0.4 * (double)(fr + mf_arena_idle(ctx));
+        S = 1;
+        while (S < 4096 && (double)cap_of(S) * sizeof(mf_uslot) > budget) S++;
+    }
+    *S_out = S;
+    *cap_out = cap_of(S);
+    if (*cap_out >= (1ull << 40)) return mf_set_error("stats join: %llu entries do not fit", (unsigned long long)total);
+    return MF_OK;
+}
+
+static unsigned grid_for(mf_ctx *ctx, uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->n_cu * 16)); }
+
+// union of one slice: every sample's entries with count > b; adds: add_of(j)
+static int union_slice(mf_ctx *ctx, const stats_get &get, int N, int b, uint32_t S, uint32_t s, uint64_t cap, mf_buf<mf_uslot> &slots,
+                       const std::function<uint32_t(int)> &add_of, uint64_t *n_union) {
+    MF_TRY(slots.alloc(ctx, cap));
+    mf_buf<unsigned long long> nu; MF_TRY(nu.alloc(ctx, 1));
+    mf_buf<unsigned int> flags; MF_TRY(flags.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(nu.p, 0, 8, ctx->stream));
+    MF_HIP(hipMemsetAsync(flags.p, 0, 4, ctx->stream));
+    {
+        mf_ktimer tm(ctx, "k_stats_init");
+        k_stats_init<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap);
+    }
+    for (int j = 0; j < N; j++) {
+        mf_table *t = nullptr; bool own = false; uint64_t F = 0;
+        MF_TRY(get(j, 0, &t, &own, &F));
+        if (t->n) {
+            mf_ktimer tm(ctx, "k_stats_union");
+            k_stats_union<<<grid_for(ctx, t->n), 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add_of(j), S, s, nu.p, flags.p);
+        }
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (own) mf_table_destroy(t);
+        if (e != hipSuccess) return mf_set_error("stats join: union pass failed: %s", hipGetErrorString(e));
+    }
+    unsigned int fl = 0; unsigned long long n = 0;
+    MF_HIP(hipMemcpyAsync(&fl, flags.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipMemcpyAsync(&n, nu.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    if (fl & 1u) return mf_set_error("stats join: a k-mer key >= 2^62 (k-mers files hold k <= 31)");
+    if (fl & 2u) return mf_set_error("stats join: the union table of a slice is full (raise option stats_slices)");
+    *n_union = n;
+    return MF_OK;
+}
+
+// (key, value) pairs -> ascending table; the arrays move into the table.  Result tables have k = 31: their keys are any values below
+// 2^62 (the union pass rejects larger ones), and the exports / writers order 2k = 62 key bits.
+static int pairs_to_table(mf_ctx *ctx, mf_buf<uint64_t> &keys, mf_buf<uint16_t> &vals, uint64_t n, mf_table **out) {
+    const int k = 31;
+    mf_buf<uint64_t> sk; mf_buf<uint16_t> sv;
+    MF_TRY(sk.alloc(ctx, n)); MF_TRY(sv.alloc(ctx, n));
+    if (n) MF_TRY(mf_sort_pairs(ctx, keys.p, vals.p, n, 2 * k, sk.p, sv.p));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t kb = sk.bytes(), vb = sv.bytes();
+    return mf_table_adopt(ctx, k, n, 0, sk.take(), kb, sv.take(), vb, out);
+}
+
+// appends device pieces (one per slice) into one buffer
+template <typename T>
+static int concat(mf_ctx *ctx, std::vector<mf_buf<T> *> &parts, const std::vector<uint64_t> &ns, mf_buf<T> &out, uint64_t *n) {
+    uint64_t tot = 0;
+    for (uint64_t x : ns) tot += x;
+    MF_TRY(out.alloc(ctx, tot));
+    uint64_t at = 0;
+    for (size_t i = 0; i < parts.size(); i++) {
+        if (ns[i]) MF_HIP(hipMemcpyAsync(out.p + at, parts[i]->p, ns[i] * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        at += ns[i];
+    }
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    *n = tot;
+    return MF_OK;
+}
+
+static int stats_join(mf_ctx *ctx, const stats_get &get, int na, int nb, uint64_t total, int b, double pchi2, double pmw, mf_table **chi_out,
+                      mf_table **a_out, mf_table **b_out, uint64_t *counters) {
+    const int N = na + nb;
+    // the decisions' tables
+    const double q = chi2_1_quantile(pchi2);
+    std::vector<uint8_t> chi((size_t)(na + 1) * (nb + 1), 0);
+    for (int n1a = 0; n1a <= na; n1a++)
+        for (int n1b = 0; n1b <= nb; n1b++) chi[(size_t)n1a * (nb + 1) + n1b] = chisq_keep((float)(na - n1a), (float)n1a, (float)(nb - n1b), (float)n1b, q) ? 1 : 0;
+    const int scarce_max = (int)std::ceil(N * 0.05);
+    const int mw = pmw > 0 ? 1 : 0;
+    const uint32_t T = mw ? mw_threshold(na, nb, pmw) : 0u;
+    if (ctx->opt_verbose) fprintf(stderr, "[mf] stats: q = %.17g, scarce <= %d, 2*Umin < %u\n", q, scarce_max, T);
+    mf_buf<uint8_t> dchi; MF_TRY(dchi.alloc(ctx, chi.size()));
+    MF_HIP(hipMemcpyAsync(dchi.p, chi.data(), chi.size(), hipMemcpyHostToDevice, ctx->stream));
+    mf_buf<unsigned long long> ctr; MF_TRY(ctr.alloc(ctx, 9));
+    MF_HIP(hipMemsetAsync(ctr.p, 0, 9 * 8, ctx->stream));
+
+    uint32_t S = 1; uint64_t cap = 0;
+    MF_TRY(plan_slices(ctx, total, &S, &cap));
+    std::vector<std::unique_ptr<mf_buf<uint64_t>>> pk_chi, pk_a, pk_b;
+    std::vector<std::unique_ptr<mf_buf<uint16_t>>> pv_a, pv_b;
+    std::vector<uint64_t> n_chi, n_a, n_b;
+    std::vector<uint64_t> F((size_t)N, 0);
+    bool have_F = false;
+    for (uint32_t s = 0; s < S; s++) {
+        mf_buf<mf_uslot> slots; uint64_t nu = 0;
+        MF_TRY(union_slice(ctx, get, N, b, S, s, cap, slots, [&](int j) { return j < na ? 1u : (1u << 16); }, &nu));
+        // select
+        pk_chi.emplace_back(new mf_buf<uint64_t>()); mf_buf<uint64_t> &rkeys = *pk_chi.back();
+        MF_TRY(rkeys.alloc(ctx, nu));
+        mf_buf<unsigned int> cur; MF_TRY(cur.alloc(ctx, 2));
+        MF_HIP(hipMemsetAsync(cur.p, 0, 8, ctx->stream));
+        {
+            mf_ktimer tm(ctx, "k_stats_select");
+            k_stats_select<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap, dchi.p, na, nb, scarce_max, rkeys.p, cur.p, ctr.p);
+        }
+        unsigned int m32 = 0;
+        MF_HIP(hipMemcpyAsync(&m32, cur.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+        const uint64_t m = m32;
+        n_chi.push_back(m);
+        // gather
+        mf_buf<uint16_t> mat; MF_TRY(mat.alloc(ctx, m * (uint64_t)N));
+        if (m) MF_HIP(hipMemsetAsync(mat.p, 0, mat.bytes(), ctx->stream));
+        const bool need_counts = m > 0 || !have_F;
+        for (int j = 0; j < N && need_counts; j++) {
+            mf_table *t = nullptr; bool own = false; uint64_t Fj = 0;
+            MF_TRY(get(j, 1, &t, &own, &Fj));
+            F[(size_t)j] = Fj;
+            if (m && t->n) {
+                mf_ktimer tm(ctx, "k_stats_gather");
+                k_stats_gather<<<grid_for(ctx, t->n), 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, S, s, (uint32_t)j, (uint32_t)N, mat.p);
+            }
+            const hipError_t e = hipStreamSynchronize(ctx->stream);
+            if (own) mf_table_destroy(t);
+            if (e != hipSuccess) return mf_set_error("stats join: gather pass failed: %s", hipGetErrorString(e));
+        }
+        have_F = true;
+        slots.reset();
+        // rows
+        uint64_t Fsum = 0;
+        for (uint64_t x : F) Fsum += x;
+        const double M = (double)Fsum / N;
+        std::vector<double> Fd((size_t)N);
+        for (int j = 0; j < N; j++) Fd[(size_t)j] = (double)F[(size_t)j];
+        mf_buf<double> dF; MF_TRY(dF.alloc(ctx, N));
+        MF_HIP(hipMemcpyAsync(dF.p, Fd.data(), (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream));
+        pk_a.emplace_back(new mf_buf<uint64_t>()); pk_b.emplace_back(new mf_buf<uint64_t>());
+        pv_a.emplace_back(new mf_buf<uint16_t>()); pv_b.emplace_back(new mf_buf<uint16_t>());
+        MF_TRY(pk_a.back()->alloc(ctx, m)); MF_TRY(pk_b.back()->alloc(ctx, m)); MF_TRY(pv_a.back()->alloc(ctx, m)); MF_TRY(pv_b.back()->alloc(ctx, m));
+        MF_HIP(hipMemsetAsync(cur.p, 0, 8, ctx->stream));
+        if (m) {
+            mf_stats_row_args ra{mat.p, rkeys.p, m, na, nb, dF.p, M, mw, T, pk_a.back()->p, pk_b.back()->p, pv_a.back()->p, pv_b.back()->p, cur.p, ctr.p};
+            if (N <= MF_STATS_THREAD_N) {
+                mf_ktimer tm(ctx, "k_stats_rows_thread");
+                k_stats_rows_thread<<<(unsigned)std::min<uint64_t>((m + 255) / 256, (uint64_t)ctx->n_cu * 8), 256, (size_t)N * 256 * sizeof(double), ctx->stream>>>(ra);
+            } else {
+                mf_ktimer tm(ctx, "k_stats_rows_wave");
+                k_stats_rows_wave<<<(unsigned)std::min<uint64_t>((m + 3) / 4, (uint64_t)ctx->n_cu * 16), 256, 0, ctx->stream>>>(ra);
+            }
+        }
+        unsigned int cc[2] = {0, 0};
+        MF_HIP(hipMemcpyAsync(cc, cur.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+        n_a.push_back(cc[0]); n_b.push_back(cc[1]);
+    }
+    unsigned long long hc[9];
+    MF_HIP(hipMemcpyAsync(hc, ctr.p, 9 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 9; i++) counters[i] = hc[i];
+    // the three lists: concatenated over the slices, sorted, as tables
+    auto finish = [&](std::vector<std::unique_ptr<mf_buf<uint64_t>>> &pk, std::vector<std::unique_ptr<mf_buf<uint16_t>>> *pv, std::vector<uint64_t> &ns,
+                      mf_table **out) -> int {
+        std::vector<mf_buf<uint64_t> *> kp;
+        for (auto &x : pk) kp.push_back(x.get());
+        mf_buf<uint64_t> keys; mf_buf<uint16_t> vals; uint64_t n = 0;
+        MF_TRY(concat(ctx, kp, ns, keys, &n));
+        if (pv) {
+            std::vector<mf_buf<uint16_t> *> vp;
+            for (auto &x : *pv) vp.push_back(x.get());
+            uint64_t n2 = 0;
+            MF_TRY(concat(ctx, vp, ns, vals, &n2));
+        } else {
+            MF_TRY(vals.alloc(ctx, n));
+            std::vector<uint16_t> ones(std::max<uint64_t>(n, 1), 1);
+            if (n) MF_HIP(hipMemcpyAsync(vals.p, ones.data(), n * 2, hipMemcpyHostToDevice, ctx->stream));
+            MF_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        for (auto &x : pk) x->reset();
+        if (pv) for (auto &x : *pv) x->reset();
+        return pairs_to_table(ctx, keys, vals, n, out);
+    };
+    MF_TRY(finish(pk_chi, nullptr, n_chi, chi_out));
+    MF_TRY(finish(pk_a, &pv_a, n_a, a_out));
+    return finish(pk_b, &pv_b, n_b, b_out);
+}
+
+static int nsamples_join(mf_ctx *ctx, const stats_get &get, int N, uint64_t total, int b, mf_table **out) {
+    uint32_t S = 1; uint64_t cap = 0;
+    MF_TRY(plan_slices(ctx, total, &S, &cap));
+    std::vector<std::unique_ptr<mf_buf<uint64_t>>> pk;
+    std::vector<std::unique_ptr<mf_buf<uint16_t>>> pv;
+    std::vector<uint64_t> ns;
+    for (uint32_t s = 0; s < S; s++) {
+        mf_buf<mf_uslot> slots; uint64_t nu = 0;
+        MF_TRY(union_slice(ctx, get, N, b, S, s, cap, slots, [](int) { return 1u; }, &nu));
+        pk.emplace_back(new mf_buf<uint64_t>()); pv.emplace_back(new mf_buf<uint16_t>());
+        MF_TRY(pk.back()->alloc(ctx, nu)); MF_TRY(pv.back()->alloc(ctx, nu));
+        mf_buf<unsigned int> cur; MF_TRY(cur.alloc(ctx, 1));
+        MF_HIP(hipMemsetAsync(cur.p, 0, 4, ctx->stream));
+        {
+            mf_ktimer tm(ctx, "k_stats_nsamples");
+            k_stats_nsamples<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap, pk.back()->p, pv.back()->p, cur.p);
+        }
+        unsigned int m = 0;
+        MF_HIP(hipMemcpyAsync(&m, cur.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+        if (m != nu) return mf_set_error("kmers-samples-counter: %u union entries written, %llu claimed", m, (unsigned long long)nu);
+        ns.push_back(m);
+    }
+    std::vector<mf_buf<uint64_t> *> kp; std::vector<mf_buf<uint16_t> *> vp;
+    for (auto &x : pk) kp.push_back(x.get());
+    for (auto &x : pv) vp.push_back(x.get());
+    mf_buf<uint64_t> keys; mf_buf<uint16_t> vals; uint64_t n = 0, n2 = 0;
+    MF_TRY(concat(ctx, kp, ns, keys, &n));
+    MF_TRY(concat(ctx, vp, ns, vals, &n2));
+    pk.clear(); pv.clear();
+    return pairs_to_table(ctx, keys, vals, n, out);
+}
+
+static int check_groups(int na, int nb) {
+    if (na < 1 || nb < 1) return mf_set_error("stats-kmers: both groups need at least one sample (|A| = %d, |B| = %d)", na, nb);
+    if (na + nb > MF_STATS_MAX_N)
+        return mf_set_error("stats-kmers: %d samples, this build supports at most %d (|A| + |B|)", na + nb, MF_STATS_MAX_N);
+    return MF_OK;
+}
+static int check_p(double pchi2) {
+    if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) return mf_set_error("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
+    return MF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// C-ABI
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int mf_stats_kmers_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *const *b, int nb, int max_bad, double p_chi2, double p_mw,
+                                     mf_table **chi, mf_table **group_a, mf_table **group_b, uint64_t *counters) {
+    mf_range rng_("mf:stats_kmers");
+    if (!ctx || !chi || !group_a || !group_b || !counters || (na && !a) || (nb && !b)) return mf_set_error("mf_stats_kmers_tables: NULL argument");
+    *chi = *group_a = *group_b = nullptr;
+    MF_TRY(check_groups(na, nb));
+    MF_TRY(check_p(p_chi2));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    for (int j = 0; j < na + nb; j++) {
+        const mf_table *t = j < na ? a[j] : b[j - na];
+        if (!t) return mf_set_error("mf_stats_kmers_tables: table %d is NULL", j);
+        if (t->ctx != ctx) return mf_set_error("mf_stats_kmers_tables: table %d belongs to another context", j);
+        total += t->n;
+    }
+    std::vector<uint64_t> F((size_t)(na + nb), 0);
+    std::vector<bool> have((size_t)(na + nb), false);
+    stats_get get = [&](int j, int pass, mf_table **t, bool *own, uint64_t *Fj) -> int {
+        *t = j < na ? a[j] : b[j - na];
+        *own = false;
+        if (pass == 1) {
+            if (!have[(size_t)j]) { MF_TRY(mf_sum_counts(ctx, (*t)->d_counts, (*t)->n, &F[(size_t)j])); have[(size_t)j] = true; }
+            *Fj = F[(size_t)j];
+        }
+        return MF_OK;
+    };
+    return stats_join(ctx, get, na, nb, total, max_bad, p_chi2, p_mw, chi, group_a, group_b, counters);
+}
+
+static int file_records(const char *const *files, int n, uint64_t *total) {
+    *total = 0;
+    for (int j = 0; j < n; j++) {
+        if (!files[j]) return mf_set_error("file %d is NULL", j);
+        struct stat st;
+        if (stat(files[j], &st) != 0) return mf_set_error("can't open '%s'", files[j]);
+        *total += (uint64_t)st.st_size / 10;
+    }
+    return MF_OK;
+}
+
+extern "C" int mf_stats_kmers(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, int max_bad, double p_chi2,
+                              double p_mw, const char *out_dir, uint64_t *counters) {
+    mf_range rng_("mf:stats_kmers(files)");
+    if (!ctx || !out_dir || (na && !a_files) || (nb && !b_files)) return mf_set_error("mf_stats_kmers: NULL argument");
+    MF_TRY(check_groups(na, nb));
+    MF_TRY(check_p(p_chi2));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t ta = 0, tb = 0;
+    MF_TRY(file_records(a_files, na, &ta));
+    MF_TRY(file_records(b_files, nb, &tb));
+    // (the join keys on the 64-bit values the files hold: k = 31 only picks the loader's internal partitioning, which changes no result;
+    // every key of a k <= 31 file is below 2^62, a larger one is an error)
+    stats_get get = [&](int j, int pass, mf_table **t, bool *own, uint64_t *Fj) -> int {
+        const char *one[1] = {j < na ? a_files[j] : b_files[j - na]};
+        *own = true;
+        return mf_table_load_kmers_sum(ctx, one, 1, pass == 0 ? max_bad : 0, 31, t, pass == 1 ? Fj : nullptr);
+    };
+    mf_table *chi = nullptr, *ga = nullptr, *gb = nullptr;
+    uint64_t c[9] = {0};
+    int rc = stats_join(ctx, get, na, nb, ta + tb, max_bad, p_chi2, p_mw, &chi, &ga, &gb, c);
+    const std::string d(out_dir);
+    uint64_t w = 0;
+    if (rc == MF_OK) rc = mf_table_write_kmers(chi, 0, (d + "/filtered_chisquared.kmers.bin").c_str(), (d + "/filtered_chisquared.stat.txt").c_str(), &w);
+    // (values are Java shorts: every record is written, none is a count the histogram knows)
+    if (rc == MF_OK) rc = mf_table_write_kmers(ga, -1, (d + "/filtered_groupA.kmers.bin").c_str(), nullptr, &w);
+    if (rc == MF_OK) rc = mf_table_write_kmers(gb, -1, (d + "/filtered_groupB.kmers.bin").c_str(), nullptr, &w);
+    mf_table_destroy(chi); mf_table_destroy(ga); mf_table_destroy(gb);
+    if (rc == MF_OK && counters) memcpy(counters, c, sizeof c);
+    return rc;
+}
+
+extern "C" int mf_kmers_samples_count_tables(mf_ctx *ctx, mf_table *const *t, int n, int max_bad, mf_table **out) {
+    mf_range rng_("mf:kmers_samples_counter");
+    if (!ctx || !out || (n && !t)) return mf_set_error("mf_kmers_samples_count_tables: NULL argument");
+    *out = nullptr;
+    if (n > 32767) return mf_set_error("kmers-samples-counter: %d input files, at most 32767 (the count is a Java short)", n);
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    for (int j = 0; j < n; j++) {
+        if (!t[j]) return mf_set_error("mf_kmers_samples_count_tables: table %d is NULL", j);
+        if (t[j]->ctx != ctx) return mf_set_error("mf_kmers_samples_count_tables: table %d belongs to another context", j);
+        total += t[j]->n;
+    }
+    stats_get get = [&](int j, int, mf_table **tt, bool *own, uint64_t *) -> int { *tt = t[j]; *own = false; return MF_OK; };
+    return nsamples_join(ctx, get, n, total, max_bad, out);
+}
+
+extern "C" int mf_kmers_samples_count(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
+                                      uint64_t *n_kmers) {
+    mf_range rng_("mf:kmers_samples_counter(files)");
+    if (!ctx || !kmers_bin || (n && !files)) return mf_set_error("mf_kmers_samples_count: NULL argument");
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    if (n > 32767) return mf_set_error("kmers-samples-counter: %d input files, at most 32767 (the count is a Java short)", n);
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    MF_TRY(file_records(files, n, &total));
+    stats_get get = [&](int j, int, mf_table **tt, bool *own, uint64_t *) -> int {
+        const char *one[1] = {files[j]};
+        *own = true;
+        return mf_table_load_kmers_sum(ctx, one, 1, max_bad, k, tt, nullptr);
+    };
+    mf_table *t = nullptr;
+    MF_TRY(nsamples_join(ctx, get, n, total, max_bad, &t));
+    uint64_t w = 0;
+    const int rc = mf_table_write_kmers(t, 0, kmers_bin, stat_txt, &w);
+    mf_table_destroy(t);
+    if (rc == MF_OK && n_kmers) *n_kmers = w;
+    return rc;
+}

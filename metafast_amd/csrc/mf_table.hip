@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_count_hist(const uint16_t *__restrict__
     for (; i < n; i += stride) {
         uint32_t v = c[i];
         if (v < 1024) atomicAdd(&lo[v], 1u);
-        else atomicAdd(&hist[v], 1ull);
+        else if (v <= (uint32_t)MF_MAX_COUNT) atomicAdd(&hist[v], 1ull);     // (values above are no counts: the Java shorts of stats-kmers)
     }
     __syncthreads();
     for (int j = threadIdx.x; j < 1024; j += blockDim.x)

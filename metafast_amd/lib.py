@@ -143,7 +143,13 @@ _SIGS = {
     "mf_synth_reads_host": (i32, [u64, i32, u64, u64, i32, u64, vp, vp]),
     "mf_synth_reads_device_ex": (i32, [vp, u64, i32, u64, u64, i32, u64, i32, vp, vp]),
     "mf_synth_reads_host_ex": (i32, [u64, i32, u64, u64, i32, u64, i32, vp, vp]),
+    "mf_stats_kmers_tables": (i32, [vp, vp, i32, vp, i32, i32, C.c_double, C.c_double, pvp, pvp, pvp, vp]),
+    "mf_stats_kmers": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, C.c_double, C.c_double, cp, vp]),
+    "mf_kmers_samples_count_tables": (i32, [vp, vp, i32, i32, pvp]),
+    "mf_kmers_samples_count": (i32, [vp, C.POINTER(cp), i32, i32, i32, cp, cp, pu64]),
 }
+
+STATS_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "unique_left")
 
 
 class MetafastError(RuntimeError):
@@ -440,6 +446,37 @@ class Context:
     def features_files(self, components_bin, kmers_bin, k, threshold, vec_path, breadth_path, selected=None):
         _check(lib().mf_features_selected(self.h, os.fsencode(components_bin), os.fsencode(kmers_bin), k, threshold,
                                           selected.h if selected is not None else None, _opt(vec_path), _opt(breadth_path)))
+
+    # ---- group comparison (multi-sample join) ----
+    def stats_kmers(self, a_tables, b_tables, p_chi2=0.05, p_mw=0.05, max_bad=0):
+        """StatsKmersFinder (src/tools/StatsKmersFinder.java:89-297) on resident tables -> (chi-squared survivors, group A, group B,
+        dict of the nine counters)"""
+        ha = (C.c_void_p * max(len(a_tables), 1))(*[t.h for t in a_tables])
+        hb = (C.c_void_p * max(len(b_tables), 1))(*[t.h for t in b_tables])
+        chi, ga, gb = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(len(STATS_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_stats_kmers_tables(self.h, ha, len(a_tables), hb, len(b_tables), max_bad, p_chi2, p_mw, C.byref(chi), C.byref(ga),
+                                           C.byref(gb), ctr.ctypes.data))
+        return Table(self, chi), Table(self, ga), Table(self, gb), dict(zip(STATS_COUNTERS, map(int, ctr)))
+
+    def stats_kmers_files(self, a_files, b_files, out_dir, p_chi2=0.05, p_mw=0.05, max_bad=0):
+        """the same from .kmers.bin files -> out_dir/filtered_{chisquared,groupA,groupB}.kmers.bin; returns the counters"""
+        ctr = np.zeros(len(STATS_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_stats_kmers(self.h, _cfiles(a_files), len(a_files), _cfiles(b_files), len(b_files), max_bad, p_chi2, p_mw,
+                                    os.fsencode(out_dir), ctr.ctypes.data))
+        return dict(zip(STATS_COUNTERS, map(int, ctr)))
+
+    def kmers_samples_count(self, tables, max_bad=1):
+        """KmersSamplesCounter (src/tools/KmersSamplesCounter.java:69-140): Table of (k-mer, number of samples with count > max_bad)"""
+        h = (C.c_void_p * max(len(tables), 1))(*[t.h for t in tables])
+        t = C.c_void_p()
+        _check(lib().mf_kmers_samples_count_tables(self.h, h, len(tables), max_bad, C.byref(t)))
+        return Table(self, t)
+
+    def kmers_samples_count_files(self, files, k, kmers_bin, stat_txt=None, max_bad=1):
+        n = C.c_uint64()
+        _check(lib().mf_kmers_samples_count(self.h, _cfiles(files), len(files), max_bad, k, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
+        return n.value
 
     # ---- synthetic reads ----
     def synth_reads_device(self, seed, sample, first_read, n_reads, read_len, genome_scale_bp, d_bases, d_offsets, sub_per_16384=82):
