@@ -51,59 +51,55 @@ struct mf_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int n_cu = 256;
-    // options
+    // options (mf_ctx_set_option, mf_ctx.hip).  First the ones whose setter does more than check a range ...
     int64_t opt_l1_bits = -1;      // -1 = auto
     int64_t opt_l2_bits = -1;
-    int64_t opt_part_target = 6144;  // mean k-mer occurrences per final partition (k_skm_count2: ~800 distinct k-mers in 4096 slots)
-    int64_t opt_part_target_long = 256;   // ... for assembled sequences (mean length >= 8k: nearly duplicate-free)
-    int64_t opt_scatter_staged = 1;
-    int64_t opt_profile = 0;
-    int64_t opt_l1_blocks = 0;     // 0 = auto
-    int64_t opt_verbose = 0;
-    int64_t opt_skm = 1;           // super-k-mer counting path (mf_skm.hip) for k >= MF_SKM_MIN_K; 0 = always one record per k-mer
-    int64_t opt_skm_dyn = 1;       // one-pass level-1 scatter with sampled region sizes: 0 never, 1 auto (large inputs), 2 always
-    int64_t opt_stream_reader = 1; // plain FASTA/FASTQ files go through the pinned, double-buffered streaming reader (mf_io.hip)
-    int64_t opt_sr_piece = 8 << 20, opt_sr_slack = 1 << 20;
-    double t_hipmalloc = 0; uint64_t n_hipmalloc = 0, b_hipmalloc = 0;   // seconds / calls / bytes inside hipMalloc (diagnostics: MF_IO_TIMING)
-    bool pin_pool_pinned = false;                                  // (hipHostMalloc'ed; else plain page-aligned host memory, option host_pinned = 0)
-    void *pin_pool = nullptr; size_t pin_pool_bytes = 0;           // pinned staging chunks of the streaming reader (lazy, kept)
-    void *up_pool = nullptr; size_t up_pool_bytes = 0; bool up_pool_pinned = false;   // staging chunks of mf_upload_file (mf_dparse.hip): small and PINNED (lazy, kept)
     int64_t opt_skm_slices = 0;    // digit-range slices of a counting run (0 = as many as the HBM budget asks for)
     int64_t opt_skm_dedupe = 1;    // k_skm_count: identical records of a unit are counted once, with their multiplicity (0 = every record for itself)
-    int64_t opt_skm_shared = 1;    // slices behind one level 1 over all digits: 0 never, 1 when it fits, 2 whenever a run is sliced
-    int64_t opt_arena_cap_gb = 0;  // pretend the device has this much memory when the slices are chosen (0 = what it has)
-    int64_t opt_skm_batches = 0;   // partitions are counted + gathered in this many batches (0 = auto); tests force small values
-    int64_t opt_union_samples = 0;     // hint: the sequences of the next count are the unitigs of this many samples (they share k-mers: partitions are planned twice as large from 4 on)
-    int own_rank = 0, own_world = 1;   // mf_count_device_shard: only the k-mers this rank owns (level-1 digits [nd1 * rank / world, nd1 * (rank + 1) / world)) are counted
-    int64_t opt_skm_pilot = 1;     // reads: a few level-1 digit regions are counted first to measure distinct k-mers per occurrence; the later levels are planned from it (0 = plan from the occurrences alone)
-    #ifdef SKM_BIG_UNITS
-    int64_t opt_skm_unit_distinct = 4400;
-#elif defined(SKM_SMALL_UNITS)
-    int64_t opt_skm_unit_distinct = 1100;
-#else
-    int64_t opt_skm_unit_distinct = 2200;
-#endif   // ... so that a counting unit is expected to hold at most this many distinct k-mers (the LDS table takes C2_FILL = 3400 claims)
-    int64_t opt_skm_dynq = 1;      // k_skm_count: units handed out from a counter as the workgroups get to them (0: fixed stride)
+    int64_t opt_skm_unit_records = 0;      // a counting unit holds at most this many super-k-mer records (the identical-record search of k_skm_count covers 2048); 0: 2000 for k >= 25, 4000 below (short k-mers make short records: mf_skm.hip)
+    int64_t opt_wide_finish = 1;   // mf_count_wide_device: radix passes over the leading 32 bits + the order inside the buckets in LDS (0: radix passes over all 2k bits)
+    int64_t opt_file_cache_gb = 0; // > 0: tables / components written to files stay in HBM (up to this many GB) and are handed out when the same file is loaded again
+    int64_t opt_dcc_test_fail = 0; // tests only: which * 1000 + n makes the n-th call of mf_dcc_merge (which = 1) / mf_dcc_level_local (2) on this context fail
+    // ... then the rows of its table, in the table's order: the count for k <= 31
+    int64_t opt_part_target = 6144;  // mean k-mer occurrences per final partition (k_skm_count2: ~800 distinct k-mers in 4096 slots)
+    int64_t opt_part_target_long = 256;   // ... for assembled sequences (mean length >= 8k: nearly duplicate-free)
     int64_t opt_part_good = 220;   // ... and a TABLE partition at most this many k-mers that survive the cut (the graph kernels' LDS lookup table takes 352, mf_nbr.h)
     int64_t opt_unit_parts_long = 3;   // assembled sequences: log2 of the table partitions counted as one unit (k_gather_split_n cuts them apart)
-    int64_t opt_skm_unit_records = 0;      // ... and at most this many super-k-mer records (the identical-record search of k_skm_count covers 2048); 0: 2000 for k >= 25, 4000 below (short k-mers make short records: mf_skm.hip)
-    double last_pilot_rho = -1.0;
-    double last_l1_per_occ = 0; int last_l1_k = 0;   // records (with padding) of the last run's level 1 per k-mer occurrence, for k = last_l1_k: the next sample's buffers are planned with it  // what the last pilot measured (diagnostics; < 0: none ran)
+    int64_t opt_scatter_staged = 1;
+    int64_t opt_scatter_fast = 1;  // k_skm_scatter: runs dealt evenly over the lanes through LDS where the level leaves room (0 = never)
+    int64_t opt_l1_blocks = 0;     // 0 = auto
+    int64_t opt_skm = 1;           // super-k-mer counting path (mf_skm.hip) for k >= MF_SKM_MIN_K; 0 = always one record per k-mer
+    int64_t opt_skm_dyn = 1;       // one-pass level-1 scatter with sampled region sizes: 0 never, 1 auto (large inputs), 2 always
+    int64_t opt_skm_dynq = 1;      // k_skm_count: units handed out from a counter as the workgroups get to them (0: fixed stride)
+    int64_t opt_skm_shared = 1;    // slices behind one level 1 over all digits: 0 never, 1 when it fits, 2 whenever a run is sliced
+    int64_t opt_skm_batches = 0;   // partitions are counted + gathered in this many batches (0 = auto); tests force small values
+    int64_t opt_skm_pilot = 1;     // reads: a few level-1 digit regions are counted first to measure distinct k-mers per occurrence; the later levels are planned from it (0 = plan from the occurrences alone)
+    int64_t opt_skm_unit_distinct = 2200;   // ... so that a counting unit is expected to hold at most this many distinct k-mers (the LDS table takes C2_FILL = 3400 claims)
+    int64_t opt_union_samples = 0;     // hint: the sequences of the next count are the unitigs of this many samples (they share k-mers: partitions are planned twice as large from 4 on)
+    int64_t opt_arena_cap_gb = 0;  // pretend the device has this much memory when the slices are chosen (0 = what it has)
+    int64_t opt_profile = 0;
+    int64_t opt_verbose = 0;
+    // ... the file readers
+    int64_t opt_stream_reader = 1; // plain FASTA/FASTQ files go through the pinned, double-buffered streaming reader (mf_io.hip)
+    int64_t opt_sr_piece = 8 << 20, opt_sr_slack = 1 << 20;
     int64_t opt_device_parse = 1;  // plain FASTA / FASTQ files are parsed on the device (mf_dparse.hip); files it is not sure about go to the host readers
-    int64_t opt_device_parse_piece = 8 << 20, opt_device_parse_threads = 8;   // upload: piece size and host threads (each owns two staging chunks of a piece)
     int64_t opt_device_parse_min = 1 << 20;   // ... from this size on (bytes): a small file is not worth the kernels' launches
+    int64_t opt_device_parse_piece = 8 << 20, opt_device_parse_threads = 8;   // upload: piece size and host threads (each owns two staging chunks of a piece)
     int64_t opt_host_pinned = 0;   // staging buffers of the file readers / writers: 1 = hipHostMalloc (0.16 - 0.29 s per GB to get, 0.1 s to give back), 0 = plain host memory (copies to and from it run at the same 56 GB/s on this platform: tools/pin_alloc.hip)
-    int64_t opt_file_cache_gb = 0; // > 0: tables / components written to files stay in HBM (up to this many GB) and are handed out when the same file is loaded again
     int64_t opt_gz_device_min = 32 << 20;   // .fa.gz / .fq.gz files of at least this size are inflated on many threads straight into HBM (mf_dparse_gz); tests: 0
     int64_t opt_gz_piece = 2 << 20;         // ... in pieces of at least this many compressed bytes (tests: 65536)
-    int64_t opt_ut_double_after = 4;   // unitigs: walks still under way after this many chunked rounds (32, 128, 512, 4096 jumps) double the jump words instead (tests: 1)
-    int64_t opt_ut_plain_rounds = 3;   // unitigs of a table without partitions (2k-bit tables, k < 20): rounds of doubling the one-hop jump words over all nodes before the walks (0: none)
-    int64_t opt_cc_compress = 1;   // a pass that points every vertex at its root before the components' sizes are added up (mf_cc.hip, k_cc_compress)
     int64_t opt_stream_count = 1;  // mf_count_reads*: plain FASTA / FASTQ files are counted WHILE they cross PCIe (mf_stream.hip: upload || parse || level-1 scatter, piece by piece)
     int64_t opt_stream_count_min = 512 << 20, opt_stream_count_piece = 256 << 20;   // ... from this many bytes of files on; bytes per piece
     int64_t opt_stream_count_test_pct = 100;   // (tests: the digit regions get this share of what the sample says -- below 100 they overflow and the count steps back)
-    uint64_t n_streamed = 0, n_stream_stepped_back = 0;     // counts that went that way / that started that way and were done again from whole files
-    void *up_stream = nullptr;     // hipStream_t of the streamed count's uploads (lazy)
+    // ... the graph stages and the multi-sample join
+    int64_t opt_nbr_global = 0;    // 1: neighbour lookups of the graph kernels through the HBM index only (A/B of mf_nbr.h)
+    int64_t opt_ut_double_after = 4;   // unitigs: walks still under way after this many chunked rounds (32, 128, 512, 4096 jumps) double the jump words instead (tests: 1)
+    int64_t opt_ut_plain_rounds = 3;   // unitigs of a table without partitions (2k-bit tables, k < 20): rounds of doubling the one-hop jump words over all nodes before the walks (0: none)
+    int64_t opt_cc_compress = 1;   // a pass that points every vertex at its root before the components' sizes are added up (mf_cc.hip, k_cc_compress)
+    int64_t opt_cc_sparse = 1;     // component cutter: threshold levels that few vertices reach run on a list of them (0: every level visits all vertices)
+    int64_t opt_dcc_sparse = 0;    // sharded cutter, levels after the first: 1 = always the sparse set-up of the arrays over all vertex ids (tests)
+    int64_t opt_stats_slices = 0;  // multi-sample join (mf_stats.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
+    // ... the count for k = 32..63
     int64_t opt_wide_skm = 1;      // mf_count_wide_device: super-k-mer records + LDS tables (mf_wskm.hip) instead of sorting every occurrence (0: the sort path, mf_wide.hip)
     int64_t opt_wide_skm_min = 1 << 20;     // ... from this many k-mer occurrences on (tests: 1)
     int64_t opt_wide_skm_lazy_order = 1;    // ... the table stays in the order of the counting units until an export / the cutter asks for ascending k-mers (0: ordered at once)
@@ -112,18 +108,20 @@ struct mf_ctx {
     int64_t opt_wide_skm_merge = 1;         // ... small neighbouring partitions share a counting unit (0: a unit per partition)
     int64_t opt_wide_skm_lead = 1;          // ... the kept entries are ordered by their leading 32 bits + a look at the runs of equal ones (0: all bits are sorted; tests)
     int64_t opt_wide_skm_unit = 2400;       // ... k-mer occurrences per counting unit (tests lower it: units that overflow the LDS table are counted in passes)
-    int64_t opt_wide_finish = 1;   // mf_count_wide_device: radix passes over the leading 32 bits + the order inside the buckets in LDS (0: radix passes over all 2k bits)
-    int64_t opt_wide_big_bucket = 256;   // ... buckets of more entries than this (<= 256) go through the LDS hash table instead of the walk (tests lower it)
+    int64_t opt_wide_big_bucket = 256;   // wide_finish: buckets of more entries than this (<= 256) go through the LDS hash table instead of the walk (tests lower it)
     int64_t opt_wide_distinct = 1280;    // ... buckets of more distinct k-mers than this (<= 1280) are sorted aside (tests lower it)
-    int64_t opt_wide_ablate = 0;         // ... TIMING ONLY, wrong tables: 1 = large buckets skipped, 2 = the representatives' walk skipped
     int64_t opt_wide_passes = 0;   // mf_count_wide_device: passes over the reads, each for one prefix class of the canonical k-mers (0 = as many as the memory asks for; tests force a number)
-    int64_t opt_cc_sparse = 1;     // component cutter: threshold levels that few vertices reach run on a list of them (0: every level visits all vertices)
-    int64_t opt_stats_slices = 0;  // multi-sample join (mf_stats.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
-    int64_t opt_dcc_sparse = 0;    // sharded cutter, levels after the first: 1 = always the sparse set-up of the arrays over all vertex ids (tests)
-    int64_t opt_dcc_test_fail = 0; int64_t dcc_test_calls[3] = {0, 0, 0};   // tests only: which * 1000 + n makes the n-th call of mf_dcc_merge (which = 1) / mf_dcc_level_local (2) on this context fail
-    int64_t opt_nbr_global = 0;    // 1: neighbour lookups of the graph kernels through the HBM index only (A/B of mf_nbr.h)
-    int64_t opt_scatter_fast = 1;  // k_skm_scatter: runs dealt evenly over the lanes through LDS where the level leaves room (0 = never)
-    int64_t opt_ablate = 0;        // diagnostics only (tools/prof_count.py): results are WRONG when non-zero
+    // what the runs leave behind: counters, pools and stream handles
+    double t_hipmalloc = 0; uint64_t n_hipmalloc = 0, b_hipmalloc = 0;   // seconds / calls / bytes inside hipMalloc (diagnostics: MF_IO_TIMING)
+    bool pin_pool_pinned = false;                                  // (hipHostMalloc'ed; else plain page-aligned host memory, option host_pinned = 0)
+    void *pin_pool = nullptr; size_t pin_pool_bytes = 0;           // pinned staging chunks of the streaming reader (lazy, kept)
+    void *up_pool = nullptr; size_t up_pool_bytes = 0; bool up_pool_pinned = false;   // staging chunks of mf_upload_file (mf_dparse.hip): small and PINNED (lazy, kept)
+    int own_rank = 0, own_world = 1;   // mf_count_device_shard: only the k-mers this rank owns (level-1 digits [nd1 * rank / world, nd1 * (rank + 1) / world)) are counted
+    double last_pilot_rho = -1.0;      // what the last pilot measured (diagnostics; < 0: none ran)
+    double last_l1_per_occ = 0; int last_l1_k = 0;   // records (with padding) of the last run's level 1 per k-mer occurrence, for k = last_l1_k: the next sample's buffers are planned with it
+    uint64_t n_streamed = 0, n_stream_stepped_back = 0;     // streamed counts that went that way / that started that way and were done again from whole files
+    void *up_stream = nullptr;     // hipStream_t of the streamed count's uploads (lazy)
+    int64_t dcc_test_calls[3] = {0, 0, 0};   // (option dcc_test_fail: the calls made so far, by which)
     // workspace arena: a few large hipMalloc'd regions, sub-allocated with first-fit + coalescing free lists.
     // Everything runs on one stream, so a block can be handed out again as soon as it is released.
     struct span { size_t off, sz; };
@@ -404,12 +402,8 @@ __device__ __forceinline__ uint32_t mf_block_reserve(unsigned int *counter, uint
 // k - M + 2: 25 % at k = 21 with M = 15, 20 % with M = 13 -- tools/nbr_locality.py, profiles/r05h_nbr_locality.txt).  Measured on 50 M reads,
 // whole step (profiles/r05m_minimizer_length.txt): k = 21: 148.9 -> 127.6 ms, k = 23: 126.2 -> 117.7, k = 25: 116.6 -> 105.5 with M = 13; k = 27:
 // 99.6 -> 101.2, k = 29: 95.1 -> 102.5 (too few distinct M-mers per partition: units overflow the LDS table and are counted in several
-// passes); M = 11 loses everywhere (k_skm_count 68 - 125 ms instead of 20); M = 14 is within 1.6 % of 15 for k = 27 ... 30.  -DMF_SKM_M=<n> fixes one length for every k (experiments).
-#ifdef MF_SKM_M
-__host__ __device__ constexpr int mf_skm_m(int) { return MF_SKM_M; }
-#else
+// passes); M = 11 loses everywhere (k_skm_count 68 - 125 ms instead of 20); M = 14 is within 1.6 % of 15 for k = 27 ... 30.
 __host__ __device__ constexpr int mf_skm_m(int k) { return k <= 25 ? 13 : 15; }
-#endif
 #define MF_SKM_MIN_K 20           // shorter k: too few M-mers per k-mer for runs worth packing -> one-record-per-k-mer path
 #define MF_SKM_BASES 50           // bases a record can hold: x = bases 0..31, y = bases 32..49 | 22 digit bits | 6-bit k-mer count
 __device__ __forceinline__ uint32_t mf_mmer_rc(uint32_t f, int M) {      // reverse complement of a 2 M-bit M-mer
@@ -543,9 +537,6 @@ __device__ __forceinline__ bool mf_index_find_ph(const mf_index_view &ix, uint64
 __device__ __forceinline__ ulonglong2 mf_index_side_dir(const mf_index_view &ix, uint32_t ph) {
     return *reinterpret_cast<const ulonglong2 *>(&ix.dir[2 * (uint64_t)(ph >> (32 - ix.part_bits))]);
 }
-#ifndef MF_WALK_CAND
-#define MF_WALK_CAND 2
-#endif
 // hs: the interior's slot hash (home slot = hs & region mask, tag = its top bits)
 __device__ __forceinline__ uint32_t mf_index_side_hs(uint64_t pa, uint64_t pb, int k) {
     const uint64_t WM = (1ull << (2 * k - 4)) - 1ull;
@@ -565,7 +556,7 @@ __device__ __forceinline__ void mf_index_walk_side_v(const mf_index_view &ix, co
     const uint32_t rmask = (1u << (uint32_t)(d.x & 63ull)) - 1u, tag = hs >> MF_CIDX_REL_BITS;
     // the probe sequence first (its slots sit next to each other: one line, seldom two), the keys behind the matching tags
     // afterwards and TOGETHER: two memory latencies per lookup, not one per slot and one per key in turn
-    constexpr uint32_t NC = MF_WALK_CAND;                 // keys read together
+    constexpr uint32_t NC = 2;                            // keys read together
     uint32_t s = hs & rmask, nc = 0, cand[NC];
 #pragma unroll
     for (uint32_t q = 0; q < NC; q++) cand[q] = 0u;

@@ -215,14 +215,7 @@ __device__ __forceinline__ void mf_lds_write4_add_rtn4(const uint32_t (&wa)[4], 
                  : "memory");
 }
 __device__ __forceinline__ void mf_stage_insert_batch(const mf_stage &L, uint64_t *__restrict__ out, const uint32_t (&d)[MF_B],
-                                                      const uint64_t (&key)[MF_B], bool (&pending)[MF_B], int ablate = 0) {
-    if (ablate == 1) {            // diagnostic: k-mer generation + hashing only (keeps the values alive)
-        uint64_t acc = 0;
-#pragma unroll
-        for (int b = 0; b < MF_B; b++) acc += pending[b] ? key[b] + d[b] : 0;
-        if (acc == 0x123456789ull) out[0] = acc;
-        return;
-    }
+                                                      const uint64_t (&key)[MF_B], bool (&pending)[MF_B]) {
     const uint32_t ctr0 = mf_lds_addr(L.ctr), line0 = mf_lds_addr(L.line);
     const uint32_t dummy_ctr = ctr0 + 4u * ((uint32_t)L.nd + (uint32_t)mf_lane());               // ctr[nd .. nd+64): one per lane
     const uint32_t dummy_slot = line0 + 8u * ((uint32_t)L.nd * MF_LINE + (uint32_t)mf_lane());   // line[nd*8 .. nd*8+64)
@@ -271,7 +264,7 @@ __device__ __forceinline__ void mf_stage_insert_batch(const mf_stage &L, uint64_
                     const uint32_t dd = qd[e - e0];
                     const uint64_t pp = qpos[e - e0];
                     const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(&L.line[dd * MF_LINE + 2 * c]);
-                    if (ablate != 2) *reinterpret_cast<ulonglong2 *>(out + pp + 2 * c) = v;
+                    *reinterpret_cast<ulonglong2 *>(out + pp + 2 * c) = v;
                     asm volatile("" ::: "memory");
                     if (c == 0) __hip_atomic_store(&L.ctr[dd], 0u, __ATOMIC_RELEASE, MF_WG);   // reopen (after the reads above)
                 }
@@ -314,7 +307,7 @@ __global__ __launch_bounds__(1024) void k_l1_scatter(const uint8_t *__restrict__
                                                      const uint32_t *__restrict__ vmask, uint64_t n_words,
                                                      uint64_t words_per_block, int k, int bits,
                                                      const uint64_t *__restrict__ blockstart, int G,
-                                                     uint64_t *__restrict__ out, int ablate) {
+                                                     uint64_t *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nd = 1 << bits;
     mf_stage L = mf_stage_carve(smem, nd);
@@ -333,7 +326,7 @@ __global__ __launch_bounds__(1024) void k_l1_scatter(const uint8_t *__restrict__
             uint32_t d[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) d[u] = mf_digit(mf_phash(keys[u]), 0, bits);
-            if (STAGED) mf_stage_insert_batch(L, out, d, keys, valid, ablate);
+            if (STAGED) mf_stage_insert_batch(L, out, d, keys, valid);
             else {
 #pragma unroll
                 for (int u = 0; u < 4; u++)
@@ -468,7 +461,7 @@ __global__ __launch_bounds__(1024) void k_split(const uint64_t *__restrict__ in,
 __global__ __launch_bounds__(256) void k_count(uint64_t *__restrict__ keys, uint16_t *__restrict__ cnt,
                                                const uint64_t *__restrict__ pstart, const uint32_t *__restrict__ plen,
                                                uint32_t np, uint32_t *__restrict__ dcount,
-                                               unsigned int *__restrict__ overflow, int ablate) {
+                                               unsigned int *__restrict__ overflow) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t out_cursor;
     uint64_t *tk = reinterpret_cast<uint64_t *>(smem);                    // [MF_COUNT_SLOTS] + 64 dummy slots
@@ -511,16 +504,11 @@ __global__ __launch_bounds__(256) void k_count(uint64_t *__restrict__ keys, uint
 #pragma unroll
             for (int u = 0; u < MF_PF; u++) { uint32_t j = u * blockDim.x + threadIdx.x; R[u] = j < npairs_n ? nx2[j] : EE; }
         }
-        if (ablate != 3) {
 #pragma unroll
         for (int u = 0; u < MF_PF; u += 2) {
             uint64_t k4[4] = {K[u].x, K[u].y, K[u + 1].x, K[u + 1].y};
             mf_count_insert4(tk0, tc0, dummy_k, dummy_c, mask, slots, k4, overflow);
         }
-        } else { uint64_t acc = 0;
-#pragma unroll
-            for (int u = 0; u < MF_PF; u++) acc += K[u].x ^ K[u].y;
-            if (acc == 0x1234567ull) tk[0] = acc; }
         {   // partitions longer than the prefetch window (heavy hitters): the rest straight from HBM
             const ulonglong2 *in2 = reinterpret_cast<const ulonglong2 *>(keys + start);
             const uint32_t npairs = len >> 1;
@@ -558,7 +546,7 @@ __global__ __launch_bounds__(256) void k_count(uint64_t *__restrict__ keys, uint
             wb = __shfl(wb, 0, 64);
 #pragma unroll
             for (int i = 0; i < NCH; i++) {
-                if (i < nch && ck[i] != MF_EMPTY && ablate != 5) {
+                if (i < nch && ck[i] != MF_EMPTY) {
                     const uint32_t pos = wb + pre[i];
                     keys[start + pos] = ck[i];
                     cnt[start + pos] = (uint16_t)(cv[i] > (uint32_t)MF_MAX_COUNT ? (uint32_t)MF_MAX_COUNT : cv[i]);
@@ -741,10 +729,10 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
         mf_ktimer t(ctx, "k_l1_scatter");
         if (staged) {
             MF_TRY(set_lds(k_l1_scatter<true>, lds));
-            k_l1_scatter<true><<<G, 1024, lds, st>>>(d_bases, n_bases, vmask.p, n_words, wpb, k, bits1, blockstart.p, G, bufA.p, (int)ctx->opt_ablate);
+            k_l1_scatter<true><<<G, 1024, lds, st>>>(d_bases, n_bases, vmask.p, n_words, wpb, k, bits1, blockstart.p, G, bufA.p);
         } else {
             MF_TRY(set_lds(k_l1_scatter<false>, lds));
-            k_l1_scatter<false><<<G, 1024, lds, st>>>(d_bases, n_bases, vmask.p, n_words, wpb, k, bits1, blockstart.p, G, bufA.p, 0);
+            k_l1_scatter<false><<<G, 1024, lds, st>>>(d_bases, n_bases, vmask.p, n_words, wpb, k, bits1, blockstart.p, G, bufA.p);
         }
     }
     MF_DBG(ctx, "k_l1_scatter");
@@ -792,7 +780,7 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
         MF_TRY(set_lds(k_count, lds));
         unsigned grid = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * 3);
         mf_ktimer t(ctx, "k_count");
-        k_count<<<grid, 256, lds, st>>>(bufA.p, cnt.p, pstart.p, plen.p, np, dcount.p, (unsigned int *)&scal.p[2], (int)ctx->opt_ablate);
+        k_count<<<grid, 256, lds, st>>>(bufA.p, cnt.p, pstart.p, plen.p, np, dcount.p, (unsigned int *)&scal.p[2]);
     }
     MF_DBG(ctx, "k_count");
     mf_buf<uint64_t> doff; MF_TRY(doff.alloc(ctx, (size_t)np + 1));

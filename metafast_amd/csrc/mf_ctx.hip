@@ -156,73 +156,54 @@ extern "C" int mf_ctx_set_stream(mf_ctx *ctx, void *hip_stream) {
     return MF_OK;
 }
 
+// The options that are a range check and a store: name, member, lowest and highest accepted value (in the order of mf_ctx's fields).
+static const int64_t OPT_ANY_LO = INT64_MIN, OPT_ANY_HI = INT64_MAX;
+static const struct { const char *name; int64_t mf_ctx::*field; int64_t lo = OPT_ANY_LO, hi = OPT_ANY_HI; } mf_options[] = {
+    {"part_target", &mf_ctx::opt_part_target, 1, 16384}, {"part_target_long", &mf_ctx::opt_part_target_long, 1, 16384},
+    {"part_good", &mf_ctx::opt_part_good, 16, 4096}, {"unit_parts_long", &mf_ctx::opt_unit_parts_long, 0, 4},
+    {"scatter_staged", &mf_ctx::opt_scatter_staged}, {"scatter_fast", &mf_ctx::opt_scatter_fast}, {"l1_blocks", &mf_ctx::opt_l1_blocks},
+    {"skm", &mf_ctx::opt_skm}, {"skm_dyn", &mf_ctx::opt_skm_dyn}, {"skm_dynq", &mf_ctx::opt_skm_dynq}, {"skm_shared", &mf_ctx::opt_skm_shared},
+    {"skm_batches", &mf_ctx::opt_skm_batches}, {"skm_pilot", &mf_ctx::opt_skm_pilot}, {"skm_unit_distinct", &mf_ctx::opt_skm_unit_distinct, 64, 3400},
+    {"union_samples", &mf_ctx::opt_union_samples}, {"arena_cap_gb", &mf_ctx::opt_arena_cap_gb},
+    {"profile", &mf_ctx::opt_profile}, {"verbose", &mf_ctx::opt_verbose},
+    {"stream_reader", &mf_ctx::opt_stream_reader}, {"stream_piece_bytes", &mf_ctx::opt_sr_piece}, {"stream_slack_bytes", &mf_ctx::opt_sr_slack},
+    {"device_parse", &mf_ctx::opt_device_parse}, {"device_parse_min_bytes", &mf_ctx::opt_device_parse_min},
+    {"device_parse_piece_bytes", &mf_ctx::opt_device_parse_piece}, {"device_parse_threads", &mf_ctx::opt_device_parse_threads},
+    {"host_pinned", &mf_ctx::opt_host_pinned}, {"gz_device_min_bytes", &mf_ctx::opt_gz_device_min}, {"gz_piece_bytes", &mf_ctx::opt_gz_piece, 4096},
+    {"stream_count", &mf_ctx::opt_stream_count}, {"stream_count_min_bytes", &mf_ctx::opt_stream_count_min},
+    {"stream_count_piece_bytes", &mf_ctx::opt_stream_count_piece}, {"stream_count_test_pct", &mf_ctx::opt_stream_count_test_pct},
+    {"nbr_global", &mf_ctx::opt_nbr_global}, {"ut_double_after", &mf_ctx::opt_ut_double_after, 1, 64}, {"ut_plain_rounds", &mf_ctx::opt_ut_plain_rounds},
+    {"cc_compress", &mf_ctx::opt_cc_compress}, {"cc_sparse", &mf_ctx::opt_cc_sparse}, {"dcc_sparse", &mf_ctx::opt_dcc_sparse},
+    {"stats_slices", &mf_ctx::opt_stats_slices, 0, 4096},
+    {"wide_skm", &mf_ctx::opt_wide_skm}, {"wide_skm_min", &mf_ctx::opt_wide_skm_min}, {"wide_skm_lazy_order", &mf_ctx::opt_wide_skm_lazy_order},
+    {"wide_skm_fine", &mf_ctx::opt_wide_skm_fine}, {"wide_skm_pack", &mf_ctx::opt_wide_skm_pack}, {"wide_skm_merge", &mf_ctx::opt_wide_skm_merge},
+    {"wide_skm_lead", &mf_ctx::opt_wide_skm_lead}, {"wide_skm_unit", &mf_ctx::opt_wide_skm_unit},
+    {"wide_big_bucket", &mf_ctx::opt_wide_big_bucket, 1, 256}, {"wide_distinct", &mf_ctx::opt_wide_distinct, 1, 1280}, {"wide_passes", &mf_ctx::opt_wide_passes, 0, 65536},
+};
+
 extern "C" int mf_ctx_set_option(mf_ctx *ctx, const char *name, int64_t v) {
     if (!ctx || !name) return mf_set_error("mf_ctx_set_option: NULL argument");
     std::string s(name);
+    for (const auto &o : mf_options)
+        if (s == o.name) {
+            if (v < o.lo || v > o.hi)
+                return o.hi == OPT_ANY_HI ? mf_set_error("%s must be at least %lld", name, (long long)o.lo)
+                                          : mf_set_error("%s must be in [%lld, %lld]", name, (long long)o.lo, (long long)o.hi);
+            ctx->*o.field = v;
+            return MF_OK;
+        }
     if (s == "l1_bits") { if (v > MF_MAX_DIGIT_BITS) return mf_set_error("l1_bits > %d", MF_MAX_DIGIT_BITS); ctx->opt_l1_bits = v; }
     else if (s == "l2_bits") { if (v > MF_MAX_DIGIT_BITS) return mf_set_error("l2_bits > %d", MF_MAX_DIGIT_BITS); ctx->opt_l2_bits = v; }
-    else if (s == "part_target") { if (v < 1 || v > 16384) return mf_set_error("part_target out of [1,16384]"); ctx->opt_part_target = v; }
-    else if (s == "part_target_long") { if (v < 1 || v > 16384) return mf_set_error("part_target_long out of [1,16384]"); ctx->opt_part_target_long = v; }
-    else if (s == "scatter_staged") ctx->opt_scatter_staged = v;
-    else if (s == "profile") ctx->opt_profile = v;
-    else if (s == "l1_blocks") ctx->opt_l1_blocks = v;
-    else if (s == "verbose") ctx->opt_verbose = v;
-    else if (s == "ablate") ctx->opt_ablate = v;
-    else if (s == "scatter_fast") ctx->opt_scatter_fast = v;
-    else if (s == "skm") ctx->opt_skm = v;
-    else if (s == "skm_batches") ctx->opt_skm_batches = v;
     else if (s == "skm_slices") { if (v < 0 || v > 64 || (v & (v - 1))) return mf_set_error("skm_slices must be 0 or a power of two <= 64"); ctx->opt_skm_slices = v; }
-    else if (s == "arena_cap_gb") ctx->opt_arena_cap_gb = v;
-    else if (s == "skm_shared") ctx->opt_skm_shared = v;
     else if (s == "skm_dedupe") { if (v != 0 && v != 1 && v != 5) return mf_set_error("skm_dedupe must be 0, 1 or 5"); ctx->opt_skm_dedupe = v; }
-    else if (s == "stream_reader") ctx->opt_stream_reader = v;
-    else if (s == "stream_piece_bytes") ctx->opt_sr_piece = v;
-    else if (s == "stream_slack_bytes") ctx->opt_sr_slack = v;
-    else if (s == "skm_dyn") ctx->opt_skm_dyn = v;
-    else if (s == "nbr_global") ctx->opt_nbr_global = v;
-    else if (s == "ut_plain_rounds") ctx->opt_ut_plain_rounds = v;
-    else if (s == "cc_compress") ctx->opt_cc_compress = v;
-    else if (s == "stream_count") ctx->opt_stream_count = v;
-    else if (s == "stream_count_min_bytes") ctx->opt_stream_count_min = v;
-    else if (s == "stream_count_piece_bytes") ctx->opt_stream_count_piece = v;
-    else if (s == "stream_count_test_pct") ctx->opt_stream_count_test_pct = v;
-    else if (s == "wide_skm") ctx->opt_wide_skm = v;
-    else if (s == "wide_skm_min") ctx->opt_wide_skm_min = v;
-    else if (s == "wide_skm_unit") ctx->opt_wide_skm_unit = v;
-    else if (s == "wide_skm_lead") ctx->opt_wide_skm_lead = v;
-    else if (s == "wide_skm_merge") ctx->opt_wide_skm_merge = v;
-    else if (s == "wide_skm_pack") ctx->opt_wide_skm_pack = v;
-    else if (s == "wide_skm_fine") ctx->opt_wide_skm_fine = v;
-    else if (s == "wide_skm_lazy_order") ctx->opt_wide_skm_lazy_order = v;
-    else if (s == "dcc_sparse") ctx->opt_dcc_sparse = v;
-    else if (s == "dcc_test_fail") { ctx->opt_dcc_test_fail = v; ctx->dcc_test_calls[1] = ctx->dcc_test_calls[2] = 0; }
-    else if (s == "cc_sparse") ctx->opt_cc_sparse = v;
-    else if (s == "stats_slices") { if (v < 0 || v > 4096) return mf_set_error("stats_slices must be in [0, 4096]"); ctx->opt_stats_slices = v; }
-    else if (s == "gz_device_min_bytes") ctx->opt_gz_device_min = v;
-    else if (s == "gz_piece_bytes") { if (v < 4096) return mf_set_error("gz_piece_bytes must be at least 4096"); ctx->opt_gz_piece = v; }
-    else if (s == "ut_double_after") { if (v < 1 || v > 64) return mf_set_error("ut_double_after must be in [1, 64]"); ctx->opt_ut_double_after = v; }
+    else if (s == "skm_unit_records") { if (v != 0 && (v < 64 || v > (1 << 20))) return mf_set_error("skm_unit_records out of [64,2^20] (0: by k)"); ctx->opt_skm_unit_records = v; }
     else if (s == "wide_finish") ctx->opt_wide_finish = v ? 1 : 0;
-    else if (s == "wide_big_bucket") { if (v < 1 || v > 256) return mf_set_error("wide_big_bucket must be in [1, 256]"); ctx->opt_wide_big_bucket = v; }
-    else if (s == "wide_ablate") ctx->opt_wide_ablate = v;
-    else if (s == "wide_distinct") { if (v < 1 || v > 1280) return mf_set_error("wide_distinct must be in [1, 1280]"); ctx->opt_wide_distinct = v; }
-    else if (s == "wide_passes") { if (v < 0 || v > 65536) return mf_set_error("wide_passes must be in [0, 65536]"); ctx->opt_wide_passes = v; }
     else if (s == "file_cache") {                       // GB; -1: a quarter of the device's memory, -n: an n-th of that (n contexts share the device)
         if (v < 0) { size_t fr = 0, tot = 0; MF_HIP(hipSetDevice(ctx->device)); MF_HIP(hipMemGetInfo(&fr, &tot)); v = std::max<int64_t>(1, (int64_t)(tot >> 32) / -v); }
         ctx->opt_file_cache_gb = v;
         if (!v) mf_file_cache_clear(ctx);
     }
-    else if (s == "skm_pilot") ctx->opt_skm_pilot = v;
-    else if (s == "device_parse") ctx->opt_device_parse = v;
-    else if (s == "device_parse_min_bytes") ctx->opt_device_parse_min = v;
-    else if (s == "device_parse_piece_bytes") ctx->opt_device_parse_piece = v;
-    else if (s == "device_parse_threads") ctx->opt_device_parse_threads = v;
-    else if (s == "host_pinned") ctx->opt_host_pinned = v;
-    else if (s == "skm_dynq") ctx->opt_skm_dynq = v;
-    else if (s == "part_good") { if (v < 16 || v > 4096) return mf_set_error("part_good out of [16,4096]"); ctx->opt_part_good = v; }
-    else if (s == "unit_parts_long") { if (v < 0 || v > 4) return mf_set_error("unit_parts_long out of [0,4]"); ctx->opt_unit_parts_long = v; }
-    else if (s == "skm_unit_records") { if (v != 0 && (v < 64 || v > (1 << 20))) return mf_set_error("skm_unit_records out of [64,2^20] (0: by k)"); ctx->opt_skm_unit_records = v; }
-    else if (s == "skm_unit_distinct") { if (v < 64 || v > 3400) return mf_set_error("skm_unit_distinct out of [64,3400]"); ctx->opt_skm_unit_distinct = v; }
-    else if (s == "union_samples") ctx->opt_union_samples = v;
+    else if (s == "dcc_test_fail") { ctx->opt_dcc_test_fail = v; ctx->dcc_test_calls[1] = ctx->dcc_test_calls[2] = 0; }
     else return mf_set_error("unknown option '%s'", name);
     return MF_OK;
 }

@@ -19,9 +19,6 @@
 #pragma once
 #include "mf_common.h"
 #ifdef __HIPCC__
-#ifndef NB_ABLATE
-#define NB_ABLATE 0
-#endif
 #define NB_SLOTS 1024               // 16-bit slots of a wave's index (tag | position): load <= 0.34, on average half of that
 #define NB_CAP 352                 // keys of a partition that go into LDS
 #define NB_WAVES 4                 // waves (= partitions in flight) per workgroup
@@ -216,7 +213,6 @@ __device__ __forceinline__ void nb_for_each(const mf_index_view &ix, const uint6
                 wave_sync();
                 if (lane < Rl && ix.compact) dent = mf_index_side_dir(ix, mf_remix32(qm[lane]));
             }
-#if !(NB_ABLATE & 1)
             if (local) {
                 // the four neighbours of a side differ in ONE base at an end: they share their interior (k-2)-mer, the index is
                 // hashed on it, so ONE walk from the interior's home slot to the next empty slot meets all of them.  A key K met
@@ -250,17 +246,12 @@ __device__ __forceinline__ void nb_for_each(const mf_index_view &ix, const uint6
                     }
                 }
             }
-#endif
             if (R) {
                 if (lane < Rl) {
                     uint32_t o4[4], rv = 0;
                     const uint32_t meta = qt[lane];
-#if NB_ABLATE & 2
-                    o4[0] = o4[1] = o4[2] = o4[3] = (qa[lane] == 12345ull && dent.x == 77ull) ? 5u : NB_NONE;
-#else
                     if (ix.compact) mf_index_walk_side_d(ix, dent, qa[lane], qb[lane], meta & 1u, meta >> 1, k, o4, &rv);
                     else mf_index_walk_side(ix, mf_remix32(qm[lane]), qa[lane], qb[lane], meta & 1u, meta >> 1, k, o4, &rv);
-#endif
                     uint32_t *ans = reinterpret_cast<uint32_t *>(&qa[lane]), *ans2 = reinterpret_cast<uint32_t *>(&qb[lane]);      // (the request has been read: its answers take its place)
                     ans[0] = o4[0]; ans[1] = o4[1]; ans2[0] = o4[2]; ans2[1] = o4[3]; qt[lane] = rv;
                 }

@@ -37,16 +37,7 @@ typedef uint32_t skm_v4 __attribute__((ext_vector_type(4)));
 #define SKM_LINE 4                 // records per 64-byte staging line
 #define SKM_QCAP 16
 #define SKM_DIGIT_BITS 22          // digit bits stored in a record (levels after the first)
-#ifdef SKM_BIG_UNITS              /* experiment (round 5): ONE workgroup of 1024 threads per CU with a table of 8192 slots -- units twice as large, half as many.
-                                     Correct (77 parity tests) and SLOWER: k_skm_count 25.9 -> 27.9 ms on the benchmark, 34.9 -> 39.2 without the search for
-                                     identical records, 61.1 -> 77.7 at 5-fold depth, 16.5 -> 18.4 at k = 21 (profiles/r05y_big_units.txt): sixteen waves wait
-                                     longer at a unit's barriers than eight, and a CU with one workgroup has nothing to run while that one compacts.  Not built in. */
-#define SKM_CT 1024
-#elif defined(SKM_SMALL_UNITS)    /* experiment (round 6): workgroups of 256 threads with a table of 2048 slots, three per CU -- units half as large, twice as many */
-#define SKM_CT 256
-#else
-#define SKM_CT 512                 // threads of k_skm_count
-#endif
+#define SKM_CT 512                 // threads of k_skm_count (1024 with a table twice as large: 25.9 -> 27.9 ms, profiles/r05y_big_units.txt; 256 with half: 35.7 ms, profiles/r06c_small_units.json)
 #define SKM_NW (SKM_CT / 64)       // its waves
 
 __device__ __forceinline__ bool skm_rec_valid(const skm_rec &r) { return ((uint32_t)r.y & 63u) != 63u; }
@@ -700,25 +691,16 @@ __device__ __forceinline__ uint32_t skm_pass_of(uint64_t key) {
 // The all-counts histogram of IOUtils.printKmers (src/io/IOUtils.java:45-71, the .stat.txt file) needs the entries the
 // cut drops: their counts (<= thr) are tallied here (count 1 by ballot, the others in a small LDS histogram).
 // =============================================================================================
-#ifdef SKM_BIG_UNITS
-#define C2_SLOTS 8192
-#define C2_FILL 6800
-#define C2_WG_PER_CU 1
-#elif defined(SKM_SMALL_UNITS)
-#define C2_SLOTS 2048
-#define C2_FILL 1700
-#define C2_WG_PER_CU 3
-#else
 #define C2_WG_PER_CU 2
 #define C2_SLOTS 4096            // table slots: at the planned ~800 distinct k-mers per partition the table is 1/5 full.  (2048 slots
                                  // = three workgroups per CU instead of two, but an 80-VGPR budget: 54 ms against 45.)
 #define C2_FILL 3400             // claims beyond which a partition is counted again in several passes
-#endif
+#define C2_PASS_GROWTH 4u        // ... their number x 4 after every overflow (x 2: no difference, profiles/r05x_pass_mult.txt)
 #define C2_QN 128                // queue entries per wave (keys): drained at 64, one push (<= 64 keys) between checks
 #define C2_LH 64                 // bins of the workgroup's dropped-count histogram (a cut with thr >= C2_LH is made after the kernel)
 #define C2_ITEMS 848             // item entries per wave: 64 records x 10 items + two steps of padding (the read-ahead of the last step runs past them, unused) + the dummy area of the item stores
 #define C2_W 2                   // k-mers per item
-#define DD_BITS (SKM_CT > 512 ? 12 : 11)   // bits of a record's index in its unit (the search for identical records: C2_DD * SKM_CT records)
+#define DD_BITS 11               // bits of a record's index in its unit (the search for identical records: C2_DD * SKM_CT records)
 #define C2_DD 4                  // records per thread of a unit whose identical records are counted once (k_skm_count): units of up to C2_DD * SKM_CT records
 static constexpr size_t C2_LDS = (size_t)C2_SLOTS * 12 + (size_t)SKM_CT * 16 + (size_t)(SKM_CT / 64) * (C2_ITEMS * 2 + C2_QN * 8 + C2_QN * 2) + 2 * C2_LH * 4 + 48;
 static_assert(C2_LDS <= 160 * 1024 / C2_WG_PER_CU, "workgroups per CU");
@@ -935,9 +917,7 @@ __device__ __forceinline__ void c2_step(const c2_wave &L, uint32_t i0, uint32_t 
     it = it1; W = W_n; it1 = it2;
 }
 
-// PROF: cycle counters per phase (diagnostics, option ablate & 32; s_memtime perturbs the kernel by about a tenth)
-#define C2_TICK(i) do { if (PROF) { const long long t__ = clock64(); prof[i] += (unsigned long long)(t__ - tlast); tlast = t__; } } while (0)
-template <int K, bool PROF>
+template <int K>
 __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restrict__ recs, const uint64_t *__restrict__ pstart,
                                                            const uint32_t *__restrict__ plen, uint32_t np,
                                                            const uint64_t *__restrict__ toff, uint64_t *__restrict__ tkeys,
@@ -952,7 +932,6 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
     // of a unit is asked for two units ahead, and the claim passes through LDS behind a barrier of the unit before that.  With the
     // fixed stride a workgroup's 1024 units add up to a total that differs by a few per cent from workgroup to workgroup (heavy
     // minimizers counted in several passes among them), and a launch ends when the slowest is done.
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long tlast = PROF ? clock64() : 0;
     // partitions [p0, np); slice of p in tkeys / tcnt starts at toff[p] - tbase; thr >= 0: entries with count <= thr are
     // dropped and tallied in drop_hist[count] (thr < C2_LH); *n_all += distinct k-mers before the cut.
     // (Two neighbouring partitions per table pass, told apart by a tag bit in the key, were tried in round 3: 48.3 ms against
@@ -1090,11 +1069,9 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
         // (LDS operations of one wave execute in order: the reads see the stores above without a wait in between)
         asm volatile("ds_read_u16 %0, %2\n\tds_read_u16 %1, %2 offset:128\n\ts_waitcnt lgkmcnt(0)" : "=&v"(it), "=&v"(it1) : "v"(L.items0 + 2u * lane) : "memory");
         asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(W) : "v"(L.rb0 | (it & 0x3F0u)) : "memory");
-        C2_TICK(1);                                                         // round set-up (incl. the wait for the records)
         for (uint32_t i0 = 0; i0 < NI; i0 += 64) c2_step<K>(L, i0, it, W, it1, qn, won_acc, part_over, P, pass);      // wave-uniform
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // items / rbuf are rewritten in the next round
         __builtin_amdgcn_wave_barrier();
-        C2_TICK(2);                                                         // steps (with the drains inside them)
     };
     // the records of a unit's first C2_DD rounds are in registers before the unit starts (fetched while the unit before it
     // is worked on); a longer unit fetches every further round while the round before it is worked on
@@ -1129,7 +1106,6 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
         const uint64_t start_n = sn.start;
         const uint32_t len_n = sn.len;
         sdirent snn = {0, 0, 0, 0};                                             // the unit after the next (from dnn, once it has landed)
-        C2_TICK(0);                                                             // unit top: directory
         // ---- identical records of the unit: weights wl[i] (0: no record, or counted by another one)
         // (reads without depth have nothing to tell apart: where fewer than a quarter of a unit's records dropped out, the next
         // 15 units of this workgroup go without the search; dedupe & 4: never skip -- tests)
@@ -1213,7 +1189,6 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
             c2_barrier();                                                       // ---- the table is empty again
             if (dd_look && threadIdx.x == 0) { dd_gone = 0; dd_all = 0; }       // (read by everybody before this barrier; added to again a unit later)
         }
-        C2_TICK(7);                                                             // identical records
         // A unit with more distinct k-mers than the table takes (a heavy minimizer: low-complexity sequence between many
         // different flanks) is counted again in P = 4, 16, 64 passes over its records, pass i inserting the k-mers with
         // skm_pass_of(key) mod P = i; the passes append to the same slices.  More than 64 passes: the global overflow flag,
@@ -1295,10 +1270,8 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
         // a crowded table probes slowly: past C2_FILL claims the unit is counted in (more) passes
         if (won_acc) { if (lane == 0) atomicAdd(&blk_claims, won_acc); won_acc = 0; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the LDS operations of the asm blocks are invisible to hipcc's waitcnt pass
-        C2_TICK(3);                                                             // last drains
         if (claim_pending) { claim = 3u * gridDim.x + claimed; claim_pending = false; }
         c2_barrier();                                                           // ---- B1: every insert of the pass is done
-        C2_TICK(4);                                                             // waiting for the other waves
         const bool over = c2_lds_u32(part_over) != 0u || c2_lds_u32(&blk_claims) > (uint32_t)C2_FILL;
         // (the claim is read HERE, one barrier behind thread 0's write and at least one -- B2 of this unit, or the barriers of
         // its further passes -- before thread 0 writes the next unit's; read at the bottom of the unit loop, a wave that lagged behind B2
@@ -1394,9 +1367,7 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
         }
         }
         qn = 0;
-        C2_TICK(5);                                                             // compaction
         c2_barrier();                                                           // ---- B2: the table is clean, the cursors final
-        C2_TICK(6);
         parity ^= 1u;
         if (threadIdx.x == 0) blk_claims = 0;
         bool done = false;
@@ -1406,11 +1377,8 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
             if (threadIdx.x == 0) out_cursor = 0;
             if (thr >= 0) for (uint32_t i = threadIdx.x; i < (uint32_t)C2_LH; i += (uint32_t)SKM_CT) lhist_try[i] = 0;
             if (P >= (uint32_t)SKM_MAX_PASSES) { if (threadIdx.x == 0) atomicExch(overflow, 1u); done = true; abandon = true; }
-#ifndef C2_PASS_MULT
-#define C2_PASS_MULT 4u          /* passes of a unit that overflowed its table: x 4 each time (x 2 measured in round 5: no difference -- 1209 of 2^20 units are redone at all; both unit bounds, distinct k-mers and records, ask for 2^20 units on the benchmark: profiles/r05x_pass_mult.txt) */
-#endif
-            P *= C2_PASS_MULT;
-            if (threadIdx.x == 0 && n_redo && P == C2_PASS_MULT) atomicAdd(n_redo, 1u);    // (statistics: units counted in several passes)
+            P *= C2_PASS_GROWTH;
+            if (threadIdx.x == 0 && n_redo && P == C2_PASS_GROWTH) atomicAdd(n_redo, 1u);    // (statistics: units counted in several passes)
         } else if (++pass == P) {
             done = true;
             // (wave-uniform sums, and told so: in SGPRs they cost nothing across the unit loop, as VGPRs the allocator spilt them to
@@ -1436,7 +1404,6 @@ __global__ __launch_bounds__(SKM_CT, 4) void k_skm_count(const skm_rec *__restri
     {   // distinct k-mers before the cut: one atomic per wave
         if (lane == 0 && n_all && all_acc) atomicAdd(n_all, all_acc);
     }
-    if (PROF && lane == 0 && prof_out) for (int i = 0; i < 8; i++) atomicAdd(&prof_out[i], prof[i]);
     if (thr >= 0 && drop_hist) {
         if (lane == 0 && ones_acc) atomicAdd(&lhist[1], ones_acc);
         __syncthreads();
@@ -1663,7 +1630,7 @@ static int skm_pilot(mf_ctx *ctx, const skm_rec *bufA, const uint64_t *pstart, c
     {
         const unsigned grid = (unsigned)std::min<uint64_t>(nb, (uint64_t)ctx->n_cu * C2_WG_PER_CU);
         // ps: [2] overflow [3] distinct before the cut [4] units redone [8..24) diagnostics
-        k_skm_count<K, false><<<grid, SKM_CT, C2_LDS, st>>>(pr.p, ostart.p, uplen.p, nb, toff.p, tkeys.p, tcnt.p, dcount.p, (unsigned int *)&ps.p[2], 0u, (uint64_t)0, kthr,
+        k_skm_count<K><<<grid, SKM_CT, C2_LDS, st>>>(pr.p, ostart.p, uplen.p, nb, toff.p, tkeys.p, tcnt.p, dcount.p, (unsigned int *)&ps.p[2], 0u, (uint64_t)0, kthr,
                                                          &ps.p[3], (unsigned int *)&ps.p[4], nullptr, &ps.p[8], (uint64_t)tot[1], (uint32_t)ctx->opt_skm_dedupe, nullptr);
     }
     MF_TRY(mf_scan<1>(ctx, dcount.p, ostart.p, nb, (uint64_t *)&ps.p[5]));                // [5] k-mers that survive the cut
@@ -2009,7 +1976,6 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
     mf_buf<uint64_t> &dk = A.dk; mf_buf<uint16_t> &dc = A.dc;
     uint64_t &dused = A.dused, &dcap = A.dcap;
     mf_buf<unsigned long long> &dhist = A.dhist, &c2p = A.c2p;
-    const bool c2prof = K == 31 && (ctx->opt_ablate & 32);
     for (uint32_t b = 0; b < nbatch; b++) {
         const uint32_t p0 = (uint32_t)std::min<uint64_t>((uint64_t)b * PB, np), p1 = (uint32_t)std::min<uint64_t>((uint64_t)(b + 1) * PB, np);
         if (p0 == p1) continue;
@@ -2017,11 +1983,8 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
             const unsigned grid = (unsigned)std::min<uint64_t>(p1 - p0, (uint64_t)ctx->n_cu * C2_WG_PER_CU);      // resident workgroups
             MF_HIP(hipMemsetAsync(&scal[8], 0, 16, st));                     // ([8] units redone, [9] the unit counter)
             mf_ktimer t(ctx, "k_skm_count");
-#define SKM_COUNT_ARGS bufA.p, pstart.p, plen.p, p1, toff.p, tkeys.p, tcnt.p, dcount.p, (unsigned int *)&scal[2], p0, (uint64_t)tb[b], kthr, &scal[7], \
-                       (unsigned int *)&scal[8], dhist.p, c2p.p, (uint64_t)tmax, (uint32_t)ctx->opt_skm_dedupe, (ctx->opt_skm_dynq ? (unsigned int *)&scal[9] : nullptr)
-            if (c2prof) k_skm_count<(K == 31 ? 31 : 20), true><<<grid, SKM_CT, C2_LDS, st>>>(SKM_COUNT_ARGS);
-            else k_skm_count<K, false><<<grid, SKM_CT, C2_LDS, st>>>(SKM_COUNT_ARGS);
-#undef SKM_COUNT_ARGS
+            k_skm_count<K><<<grid, SKM_CT, C2_LDS, st>>>(bufA.p, pstart.p, plen.p, p1, toff.p, tkeys.p, tcnt.p, dcount.p, (unsigned int *)&scal[2], p0, (uint64_t)tb[b], kthr, &scal[7],
+                                                         (unsigned int *)&scal[8], dhist.p, c2p.p, (uint64_t)tmax, (uint32_t)ctx->opt_skm_dedupe, (ctx->opt_skm_dynq ? (unsigned int *)&scal[9] : nullptr));
         }
         MF_DBG(ctx, "k_skm_count");
         MF_TRY(mf_scan<1>(ctx, dcount.p + p0, coff.p + p0, p1 - p0, (uint64_t *)&scal[3]));      // offsets inside the batch
@@ -2036,7 +1999,7 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
         if (ctx->opt_verbose) {
             unsigned long long bad = 0;
             MF_HIP(hipMemcpy(&bad, &c2p.p[7], 8, hipMemcpyDeviceToHost));
-            if (bad && !c2prof) fprintf(stderr, "[mf] skm: batch %u: %llu counter(s) found non-zero under an empty key so far\n", b, bad);
+            if (bad) fprintf(stderr, "[mf] skm: batch %u: %llu counter(s) found non-zero under an empty key so far\n", b, bad);
         }
         if (res[0]) {
             if (ctx->opt_verbose) fprintf(stderr, "[mf] skm: a minimizer partition overflows the LDS table (code %llu), using the k-mer path\n", res[0]);
@@ -2109,8 +2072,7 @@ static int skm_run(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, const 
     // counts of the entries the cut drops (the .stat.txt histogram needs them): drop_hist[c], c <= thr.  The kernel tallies
     // them in a small LDS histogram: a cut above C2_LH - 1 is made afterwards (mf_count_skm)
     const int kthr = thr < C2_LH ? thr : -1;
-    MF_TRY(skm_set_lds(k_skm_count<K, false>, C2_LDS));
-    if (K == 31) MF_TRY(skm_set_lds(k_skm_count<(K == 31 ? 31 : 20), true>, C2_LDS));
+    MF_TRY(skm_set_lds(k_skm_count<K>, C2_LDS));
     // Slices (HBM budget): the records of a run are about a third of the reads' bytes per radix level, two levels ping-pong.
     // Reads, table and index have to fit beside them.  Option skm_slices forces a number (tests); arena_cap_gb stands in for
     // a smaller device.
@@ -2176,7 +2138,7 @@ static int skm_run(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, const 
         skm_acc A;                                              // (A.np_total, A.doff: set by the first slice, once the plan stands)
         A.table_bits = table_bits;
         if (kthr >= 0) { MF_TRY(A.dhist.alloc(ctx, (size_t)MF_MAX_COUNT + 1)); MF_HIP(hipMemsetAsync(A.dhist.p, 0, A.dhist.bytes(), st)); }
-        MF_TRY(A.c2p.alloc(ctx, 16)); MF_HIP(hipMemsetAsync(A.c2p.p, 0, 128, st));     // [0,8) phase cycles (profiling build), [8,16) overflow diagnostics
+        MF_TRY(A.c2p.alloc(ctx, 16)); MF_HIP(hipMemsetAsync(A.c2p.p, 0, 128, st));     // [7] counters found non-zero under an empty key (verbose), [8,16) overflow diagnostics
         MF_HIP(hipMemsetAsync(&scal[7], 0, 8, st));
         int rc = MF_OK;
         for (uint32_t sl = 0; sl < S && rc == MF_OK; sl++)
@@ -2214,14 +2176,6 @@ static int skm_run(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, const 
             return MF_SKM_FALLBACK;
         }
         if (rc != MF_OK) return rc;
-        if (K == 31 && (ctx->opt_ablate & 32)) {
-            unsigned long long h[8];
-            MF_HIP(hipMemcpyAsync(h, A.c2p.p, 64, hipMemcpyDeviceToHost, st));
-            MF_HIP(hipStreamSynchronize(st));
-            unsigned long long tot = 0; for (int i = 0; i < 8; i++) tot += h[i];
-            static const char *nm[8] = {"partition top", "round set-up", "steps", "last drains", "barrier 1", "compaction", "barrier 2", "same records"};
-            for (int i = 0; i < 8; i++) fprintf(stderr, "[mf] k_skm_count wave cycles: %-14s %5.1f %%\n", nm[i], 100.0 * (double)h[i] / (double)(tot ? tot : 1));
-        }
         const uint64_t n_dist = A.dused;
         SH.clear();
         // (the record buffers stay in the arena for the next sample: hipMalloc costs 35 ms per GiB, 5 s for a 150 GiB level 1;

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(WG_T) void k_wide_kmers(const uint8_t *__restrict__
 #define WF_LOCK 0xFFFFFFFFu
 #define WF_EMPTY 0xFFFFFFFFu
 __device__ __forceinline__ uint32_t wide_hash(const wide128 &x) { return (uint32_t)((x.lo * 0x9E3779B97F4A7C15ull ^ x.hi * 0xC2B2AE3D27D4EB4Full) >> 40); }
-__global__ __launch_bounds__(WF_T) void k_wide_finish(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, uint64_t n, int hb_tb, uint32_t big, int dbg,
+__global__ __launch_bounds__(WF_T) void k_wide_finish(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, uint64_t n, int hb_tb, uint32_t big,
                                                       uint64_t *__restrict__ ohi, uint64_t *__restrict__ olo, unsigned long long *__restrict__ tile_big, uint32_t tile_cap,
                                                       uint32_t *__restrict__ tile_cnt) {
     __shared__ uint64_t l_hi[WF_N], l_lo[WF_N];
@@ -257,9 +257,9 @@ __global__ __launch_bounds__(WF_T) void k_wide_finish(const uint64_t *__restrict
     __syncthreads();
     // the representatives: the entries of the bucket below them = the counts of the bucket's smaller representatives (a bucket of 200 repeats of
     // 3 k-mers costs 3 x 3 comparisons, not 3 x 200).  ecnt[]: count in the low half, that number in the high half
-    const uint32_t nreps = s_nreps, nbig = (dbg & 1) ? 0u : s_nbig;
+    const uint32_t nreps = s_nreps, nbig = s_nbig;
     if (tid == 0) tile_cnt[blockIdx.x] = nbig;                                     // (no list with one cursor: 2.3e6 atomics on one address per pass)
-    if (!(dbg & 2)) for (uint32_t r = tid; r < nreps; r += WF_T) {
+    for (uint32_t r = tid; r < nreps; r += WF_T) {
         const uint32_t i = reps[r] & 0xFFFFu, me = reps[r] >> 16, s = bstart[me], e = bstart[me + 1];
         const wide128 x = {l_hi[i], l_lo[i]};
         uint32_t below = 0;
@@ -302,7 +302,7 @@ __global__ void k_wide_big_list(const unsigned long long *__restrict__ tile_big,
 template <int T, int SLOTS>
 __global__ __launch_bounds__(T) void k_wide_big(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, uint64_t n, int hb_tb, const unsigned long long *__restrict__ list,
                                                 uint32_t dlimit, uint64_t *__restrict__ ohi, uint64_t *__restrict__ olo, unsigned long long *__restrict__ over_list,
-                                                unsigned int *__restrict__ n_over, unsigned long long *__restrict__ stats, int dbg) {
+                                                unsigned int *__restrict__ n_over, unsigned long long *__restrict__ stats) {
     constexpr int DCAP = SLOTS * 7 / 8;                                              // dlimit + 2 T <= DCAP: the table never fills
     __shared__ uint64_t t_hi[SLOTS], t_lo[SLOTS];
     __shared__ uint32_t tcnt[SLOTS];
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(T) void k_wide_big(const uint64_t *__restrict__ hi,
             const bool same = e < n && wide_class(cur[c], hb, tb) == p;
             if (!same) { if (e < n) atomicMin(&s_end, (unsigned long long)e); s_stop = 1; }
             uint32_t slot = wide_hash(cur[c]) & (SLOTS - 1);
-            bool done = !same || (dbg & 16);
+            bool done = !same;
             // the lanes of a wave that hold the k-mer of its first lane (twice: the first of the rest) send ONE of them with their number -- most of a
             // large bucket is one abundant k-mer, and 64 lanes adding to one LDS word take turns (50 of 108 ms were the inserts, r05ar)
             uint32_t weight = 1;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(T) void k_wide_big(const uint64_t *__restrict__ hi,
     for (uint32_t c = 0; c < DCAP / T; c++) {
         const uint32_t a = tid + c * T;
         my_rank[c] = 0; my_before[c] = 0;
-        if (a >= D || (dbg & 8)) continue;
+        if (a >= D) continue;
         const wide128 xk = {d_hi[a], d_lo[a]};
         uint32_t rk = 0, bf = 0;
 #pragma unroll 4
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(T) void k_wide_big(const uint64_t *__restrict__ hi,
     for (uint32_t c = 0; c < DCAP / T; c++) if (tid + c * T < D) { order[my_rank[c]] = (uint16_t)(tid + c * T); d_cnt[my_rank[c]] = my_before[c]; }
     __syncthreads();
     // the bucket in order: entry j is the k-mer of the last rank whose run starts at or before j
-    if (!(dbg & 4)) for (uint64_t j = tid; j < len; j += T) {
+    for (uint64_t j = tid; j < len; j += T) {
         uint32_t lo_r = 0, hi_r = D;                                                    // the answer is in [lo_r, hi_r)
         while (hi_r - lo_r > 1) { const uint32_t mid = (lo_r + hi_r) >> 1; if ((uint64_t)d_cnt[mid] <= j) lo_r = mid; else hi_r = mid; }
         const uint32_t a = order[lo_r];
@@ -587,7 +587,7 @@ static int count_wide_impl(mf_ctx *ctx, const void *d_bases, const void *d_offse
             auto fetch = [&](unsigned int *v) { return hipMemcpyAsync(v, n_big.p, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemsetAsync(n_big.p, 0, 4, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess; };
             if (hipMemsetAsync(n_big.p, 0, 4, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
             { mf_ktimer tf(ctx, "k_wide_finish");
-            k_wide_finish<<<(unsigned)n_tiles, WF_T, 0, st>>>(ah, al, n_p, hb_tb, big, (int)ctx->opt_wide_ablate, bh, bl, tile_big.p, tile_cap, tile_cnt.p); }
+            k_wide_finish<<<(unsigned)n_tiles, WF_T, 0, st>>>(ah, al, n_p, hb_tb, big, bh, bl, tile_big.p, tile_cap, tile_cnt.p); }
             if (mf_scan<1>(ctx, tile_cnt.p, tile_off.p, n_tiles, tot.p) < 0) return fail(MF_ERR);
             { uint64_t v = 0;
               if (hipMemcpyAsync(&v, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
@@ -596,13 +596,13 @@ static int count_wide_impl(mf_ctx *ctx, const void *d_bases, const void *d_offse
                 if (bigs.alloc(ctx, nb1) < 0 || list2.alloc(ctx, nb1) < 0) return fail(MF_ERR);
                 { mf_ktimer tf(ctx, "k_wide_big");
                 k_wide_big_list<<<wgrid(n_tiles), 256, 0, st>>>(tile_big.p, tile_cap, tile_cnt.p, tile_off.p, n_tiles, bigs.p);
-                k_wide_big<64, 512><<<nb1, 64, 0, st>>>(ah, al, n_p, hb_tb, bigs.p, std::min<uint32_t>(dlimit, 320u), bh, bl, list2.p, n_big.p, wstats.p, (int)ctx->opt_wide_ablate); }
+                k_wide_big<64, 512><<<nb1, 64, 0, st>>>(ah, al, n_p, hb_tb, bigs.p, std::min<uint32_t>(dlimit, 320u), bh, bl, list2.p, n_big.p, wstats.p); }
                 if (!fetch(&nb2)) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
             }
             if (nb2) {
                 if (list3.alloc(ctx, nb2) < 0) return fail(MF_ERR);
                 { mf_ktimer tf(ctx, "k_wide_big2");
-                k_wide_big<256, 2048><<<nb2, 256, 0, st>>>(ah, al, n_p, hb_tb, list2.p, dlimit, bh, bl, list3.p, n_big.p, wstats.p, (int)ctx->opt_wide_ablate); }
+                k_wide_big<256, 2048><<<nb2, 256, 0, st>>>(ah, al, n_p, hb_tb, list2.p, dlimit, bh, bl, list3.p, n_big.p, wstats.p); }
                 if (!fetch(&nb)) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
             }
             sorted = true;

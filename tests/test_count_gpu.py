@@ -456,3 +456,45 @@ def test_depth_independent_plan_against_the_oracle(gpu_ctx, oracle, scale, sub16
     k3, c3 = t3.export()
     assert np.array_equal(k3, gk) and np.array_equal(c3, gc)
     gpu_ctx.set_option("profile", 0)
+
+
+# the option names of mf_ctx_set_option with their defaults: the contract (a name that goes, or a new one, changes this list)
+OPTION_DEFAULTS = {
+    "l1_bits": -1, "l2_bits": -1, "skm_slices": 0, "skm_dedupe": 1, "skm_unit_records": 0, "wide_finish": 1, "file_cache": 0, "dcc_test_fail": 0,
+    "part_target": 6144, "part_target_long": 256, "part_good": 220, "unit_parts_long": 3, "scatter_staged": 1, "scatter_fast": 1, "l1_blocks": 0,
+    "skm": 1, "skm_dyn": 1, "skm_dynq": 1, "skm_shared": 1, "skm_batches": 0, "skm_pilot": 1, "skm_unit_distinct": 2200, "union_samples": 0,
+    "arena_cap_gb": 0, "profile": 0, "verbose": 0,
+    "stream_reader": 1, "stream_piece_bytes": 8 << 20, "stream_slack_bytes": 1 << 20, "device_parse": 1, "device_parse_min_bytes": 1 << 20,
+    "device_parse_piece_bytes": 8 << 20, "device_parse_threads": 8, "host_pinned": 0, "gz_device_min_bytes": 32 << 20, "gz_piece_bytes": 2 << 20,
+    "stream_count": 1, "stream_count_min_bytes": 512 << 20, "stream_count_piece_bytes": 256 << 20, "stream_count_test_pct": 100,
+    "nbr_global": 0, "ut_double_after": 4, "ut_plain_rounds": 3, "cc_compress": 1, "cc_sparse": 1, "dcc_sparse": 0, "stats_slices": 0,
+    "wide_skm": 1, "wide_skm_min": 1 << 20, "wide_skm_lazy_order": 1, "wide_skm_fine": 8, "wide_skm_pack": 1, "wide_skm_merge": 1,
+    "wide_skm_lead": 1, "wide_skm_unit": 2400, "wide_big_bucket": 256, "wide_distinct": 1280, "wide_passes": 0,
+}
+# option -> (a value just outside what it takes, the edge values it takes)
+OPTION_EDGES = {
+    "l1_bits": (12, [11]), "skm_slices": (3, [0, 64]), "skm_dedupe": (2, [0, 1, 5]), "part_good": (15, [16, 4096]),
+    "unit_parts_long": (5, [0, 4]), "skm_unit_records": (63, [0, 64, 1 << 20]), "skm_unit_distinct": (3401, [64, 3400]),
+    "stats_slices": (4097, [0, 4096]), "gz_piece_bytes": (4095, [4096]), "ut_double_after": (0, [1, 64]),
+    "wide_big_bucket": (257, [1, 256]), "wide_distinct": (1281, [1, 1280]), "wide_passes": (65537, [0, 65536]),
+}
+
+
+def test_option_names_and_ranges(gpu_ctx):
+    """every option is taken at its default; the retired timing switches are unknown; a value outside an option's range is refused
+    with a message that names the option, the values at the range's edges are taken (no kernel runs: the setter alone)"""
+    from metafast_amd.lib import MetafastError
+    try:
+        for name in ("ablate", "wide_ablate"):
+            with pytest.raises(MetafastError, match="unknown option"):
+                gpu_ctx.set_option(name, 0)
+        for name, (bad, edges) in OPTION_EDGES.items():
+            assert name in OPTION_DEFAULTS
+            with pytest.raises(MetafastError, match=name):
+                gpu_ctx.set_option(name, bad)
+            for v in edges:
+                gpu_ctx.set_option(name, v)
+    finally:
+        for name, v in OPTION_DEFAULTS.items():
+            gpu_ctx.set_option(name, v)
+        _reset(gpu_ctx)          # (the shared context as the other tests of this module leave it)

@@ -1,4 +1,4 @@
-"""k_ut_flags ablations on one synthetic sample: python3 tools/prof_flags.py [reads]"""
+"""k_ut_flags with the neighbour lookups through the HBM index only and partition-local (option nbr_global), on one synthetic sample: python3 tools/prof_flags.py [reads]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,10 +12,8 @@ torch.cuda.synchronize()
 ctx.synth_reads_device(0x4D45544146415354, 0, 0, n_reads, rl, 1_000_000, bases.data_ptr(), offsets.data_ptr())
 good, n_all = ctx.count_device_above(bases.data_ptr(), offsets.data_ptr(), n_reads, n_reads * rl, 31, 1)
 ctx.set_option("profile", 1)
-for name, opts in (("global index only", {"nbr_global": 1}), ("partition-local", {}), ("no remote probes", {"ablate": 1}), ("no local probes", {"ablate": 2}),
-                   ("no LDS build, no local probes", {"ablate": 6}), ("no probes at all", {"ablate": 7})):
-    ctx.set_option("nbr_global", 0); ctx.set_option("ablate", 0)
-    for k_, v in opts.items(): ctx.set_option(k_, v)
+for name, nbr_global in (("global index only", 1), ("partition-local", 0)):
+    ctx.set_option("nbr_global", nbr_global)
     for rep in range(2):
         ctx.reset_timers()
         try:
