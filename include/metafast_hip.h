@@ -471,6 +471,41 @@ int mf_kmers_samples_count_tables(mf_ctx *ctx, mf_table *const *t, int n, int ma
 int mf_kmers_samples_count(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
                            uint64_t *n_kmers);
 
+/* ---- set operations over cohorts on the same join (pipelines 2 and 3 of the reference's Pipelines.md; mf_stats.hip) ----------------
+ * Keys, slices and result tables as above; b = max_bad >= 0 (a negative one is an error); the counts of the tables are 1 .. MF_MAX_COUNT.
+ *
+ * UniqueKmersMultipleSamplesFinder.runImpl (src/tools/UniqueKmersMultipleSamplesFinder.java:84-185): over the inputs' entries with
+ * count > b, cnt(x) = number of inputs that hold x and sum(x) = the sum of their counts WRAPPED to a Java short ((short)(a + b), not a
+ * saturating add: 3 x 20000 -> -5536); an x that a filter table holds with count > b while sum(x) > b is knocked out (sum(x) := 0);
+ * *n_union = distinct keys of the inputs, knocked-out ones included.  For i = min_samples, min_samples + 1, ... max_samples: out[i -
+ * min_samples] = the records (x, sum(x)) with sum(x) > b and cnt(x) >= i, counts[i - min_samples] = their number; the list ends with the
+ * first empty table (included).  *n_out = tables returned (each to be destroyed by the caller); out and counts must hold
+ * min(max_samples, max(min_samples, n_inputs + 1)) - min_samples + 1 entries.  Errors: min_samples > max_samples (the reference's
+ * message), more than 32767 inputs (cnt is a Java short), a key >= 2^62 in an input or a filter table (every filter table is read,
+ * whatever the inputs hold), more than 2^32 - 1 union k-mers in one hash slice (raise "stats_slices"). */
+int mf_unique_kmers_multi_tables(mf_ctx *ctx, mf_table *const *inputs, int n_inputs, mf_table *const *filters, int n_filters, int max_bad,
+                                 int min_samples, int max_samples, mf_table **out, int *n_out, uint64_t *n_union, uint64_t *counts);
+/* File form: .kmers.bin files, each loaded like IOUtils.loadKmers(file, b) (duplicate records of a k-mer in one file: saturating sum of
+ * those > b) -> <out_dir>/filtered_<i>.kmers.bin for the i above */
+int mf_unique_kmers_multi(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters, int max_bad,
+                          int k, int min_samples, int max_samples, const char *out_dir, int *n_out, uint64_t *n_union, uint64_t *counts);
+/* IOUtils.MultipleFiltersAndPrintKmers (src/io/IOUtils.java:125-213) for one input table: every entry (x, v) with v > b gets the triple
+ * (cd(x), uc(x), nonibd(x)) of the three filter tables' counts (entries with count > 0; absent = 0); *kept = the entries with a non-zero
+ * triple.  The distinct triples, packed cd << 32 | uc << 16 | nonibd, come in ascending order (Triple.compareTo) with the number of
+ * entries of each.  *n_triples = the number of ALL distinct triples (<= entries of `table`), whatever `cap` is; only the first
+ * min(cap, *n_triples) are written to triples / triple_counts, so a caller that finds *n_triples > cap calls again with a larger cap
+ * (cap = entries of `table` always suffices; cap = 0 with NULL arrays asks for the number alone).  found_kept[2] = entries with
+ * v > b, entries kept.  Errors: a key >= 2^62 in any of the four tables, an input of more than 2^32 - 1 entries. */
+int mf_kmers_multiple_filters_tables(mf_ctx *ctx, mf_table *table, mf_table *cd, mf_table *uc, mf_table *nonibd, int max_bad, mf_table **kept,
+                                     uint64_t *triples, uint64_t *triple_counts, uint64_t cap, uint64_t *n_triples, uint64_t *found_kept);
+/* File form (KmersMultipleFilters.runImpl, src/tools/KmersMultipleFilters.java:77-133): the three filter tables are
+ * IOUtils.loadKmers(list, 0) of their file lists (a list may be empty), built once; input j (loaded at threshold b) ->
+ * out_kmers[j] and the triples' histogram out_stats[j] (out_stats or an entry of it may be NULL); found_kept (may be NULL) gets
+ * 2 * n_inputs values: found and kept of each input. */
+int mf_kmers_multiple_filters(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *cd_files, int n_cd,
+                              const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
+                              const char *const *out_kmers, const char *const *out_stats, uint64_t *found_kept);
+
 /* ---- A13  Bray-Curtis ---------------------------------------------------------------- */
 /* replaces DistanceMatrixCalculatorMain.brayCurtisDistance (src/tools/DistanceMatrixCalculatorMain.java:
  * 140-152): d = sum|a-b| / sum(|a|+|b|) on raw vectors; vecs is row-major [n_samples][n_comp]. */

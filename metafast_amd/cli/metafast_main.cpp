@@ -35,6 +35,10 @@
 extern "C" int mf_stats_kmers(mf_ctx *, const char *const *, int, const char *const *, int, int, double, double, const char *, uint64_t *)
     __attribute__((weak));
 extern "C" int mf_kmers_samples_count(mf_ctx *, const char *const *, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_unique_kmers_multi(mf_ctx *, const char *const *, int, const char *const *, int, int, int, int, int, const char *, int *, uint64_t *,
+                                     uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_multiple_filters(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int,
+                                         int, int, const char *const *, const char *const *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -149,6 +153,8 @@ static const OptDef OPTS[] = {
     {"use-reads-for-calculating-features", "", false, true}, {"device", "", false, false}, {"devices", "", false, false},
     {"positiveReads", "pos", true, false}, {"negativeReads", "neg", true, false}, {"filter-kmers", "", true, false}, {"max-thresh", "", false, false},
     {"a-kmers", "A", true, false}, {"b-kmers", "B", true, false}, {"p-value-chi2", "pchi2", false, false}, {"p-value-mw", "pmw", false, false},
+    {"min-samples", "", false, false}, {"max-samples", "", false, false}, {"cd-filter-kmers", "cd", true, false}, {"uc-filter-kmers", "uc", true, false},
+    {"nonibd-filter-kmers", "nonibd", true, false},
 };
 // `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
@@ -159,11 +165,13 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
     auto long_of_short = [&](const string &s) -> string {
         if (s == "i") {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
-            if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers") return "k-mers";
+            if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
+                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters") return "k-mers";
             if (tool == "component-cutter") return "sequences";
             return "reads";
         }
-        if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers")
+        if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
+                              tool == "unique-kmers-multi" || tool == "kmers-multiple-filters")
                                  ? "maximal-bad-frequence" : "maximal-bad-frequency";
         if (s == "l") return (tool == "seq-builder" || tool == "seq-builder-many") ? "sequence-len" : "min-seq-len";
         if (s == "o") return (tool == "view" || tool == "bin2fasta") ? "output-file" : "output-dir";
@@ -856,6 +864,8 @@ static const char *TOOLS_TEXT =
     "kmers-filter\t\tFilter k-mers from test set according to known samples\n"
     "kmers-samples-counter\tCount number of samples containing k-mers from multiple samples\n"
     "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
+    "unique-kmers-multi\tOutput k-mers present in one dataset in fixed number of samples and missing in other\n"
+    "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -912,6 +922,16 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
         v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV("p-value-chi2", a.get("p-value-chi2", "0.05")),
              PV("p-value-mw", a.get("p-value-mw", "0.05")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")),
              PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
+    } else if (tool == "unique-kmers-multi") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
+             PV("min-samples", a.get("min-samples", "1")), PV("max-samples", a.get("max-samples", "1")),
+             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
+             PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
+    } else if (tool == "kmers-multiple-filters") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("cd-filter-kmers", a.list("cd-filter-kmers")),
+             PV::files("uc-filter-kmers", a.list("uc-filter-kmers")), PV::files("nonibd-filter-kmers", a.list("nonibd-filter-kmers")),
+             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
+             PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -936,7 +956,7 @@ int main(int argc, char **argv) {
     }
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
-                                  "kmers-samples-counter", "stats-kmers"};
+                                  "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1008,6 +1028,10 @@ int main(int argc, char **argv) {
     else if (tool == "kmers-filter") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
     else if (tool == "kmers-samples-counter") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "stats-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
+    else if (tool == "unique-kmers-multi") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
+    else if (tool == "kmers-multiple-filters") {
+        need("k", "k"); need("k-mers", "i"); need("cd-filter-kmers", "cd"); need("uc-filter-kmers", "uc"); need("nonibd-filter-kmers", "nonibd");
+    }
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1126,6 +1150,62 @@ int main(int argc, char **argv) {
         logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
         logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
         outs = {PV::files("resulting-kmers-file", {out_dir + "/filtered_groupA.kmers.bin"})};
+    } else if (tool == "unique-kmers-multi") {
+        // UniqueKmersMultipleSamplesFinder.java:84-185: the k-mers that enough input files hold and no filter file does
+        check_k(k);
+        const int mn = a.geti("min-samples", 1), mx = a.geti("max-samples", 1), b = a.geti("maximal-bad-frequence", 1);
+        if (mn > mx) die("--min-samples parameter cannot be greater than --max-samples parameter.");
+        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
+        const vector<string> files = a.list("k-mers"), filt = a.list("filter-kmers");
+        if (!mf_unique_kmers_multi) die("unique-kmers-multi: this build of the library has no mf_unique_kmers_multi");
+        mf_ctx *ctx = ctx_of(e, a);
+        mkdirs(out_dir); mkdirs(st_dir);
+        auto fp = cptrs(files), ff = cptrs(filt);
+        const int64_t top = std::min<int64_t>(mx, std::max<int64_t>(mn, (int64_t)files.size() + 1));
+        vector<uint64_t> c((size_t)std::max<int64_t>(1, top - mn + 1), 0);
+        int n_out = 0; uint64_t n_union = 0;
+        check(mf_unique_kmers_multi(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, mn, mx, out_dir.c_str(), &n_out, &n_union, c.data()));
+        for (int q = 0; q < n_out; q++) {
+            const string out = out_dir + "/filtered_" + std::to_string(mn + q) + ".kmers.bin";
+            char pct[64];
+            if (n_union) snprintf(pct, sizeof pct, "%.1f", c[(size_t)q] * 100.0 / n_union); else snprintf(pct, sizeof pct, "NaN");
+            logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n_union).c_str(),
+                   group_digits(c[(size_t)q]).c_str(), pct);
+            if (c[(size_t)q] == 0) { logmsg("INFO", "No good k-mers found. Stop at maxSamples=%d", mn + q); break; }
+            logmsg("INFO", "Good k-mers printed to %s", out.c_str());
+        }
+        outs = {PV::files("resulting-kmers-file", {out_dir + "/filtered_" + std::to_string(mn) + ".kmers.bin"})};
+    } else if (tool == "kmers-multiple-filters") {
+        // KmersMultipleFilters.java:77-133: every input file against the CD, UC and nonIBD sets of n_samples files
+        check_k(k);
+        const int b = a.geti("maximal-bad-frequence", 1);
+        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
+        const vector<string> files = a.list("k-mers"), cd = a.list("cd-filter-kmers"), uc = a.list("uc-filter-kmers"), ni = a.list("nonibd-filter-kmers");
+        if (!mf_kmers_multiple_filters) die("kmers-multiple-filters: this build of the library has no mf_kmers_multiple_filters");
+        mf_ctx *ctx = ctx_of(e, a);
+        mkdirs(out_dir); mkdirs(st_dir);
+        vector<string> ok, os;
+        for (auto &f : files) {
+            // file.getName().replaceAll(".kmers.bin", ""): a regular expression, every '.' matches any character but a line end
+            const string base = basename_of(f), pat = ".kmers.bin";
+            string name;
+            for (size_t q = 0; q < base.size();) {
+                bool m = q + pat.size() <= base.size();
+                for (size_t r = 0; m && r < pat.size(); r++) m = pat[r] == '.' ? (base[q + r] != '\n' && base[q + r] != '\r') : base[q + r] == pat[r];
+                if (m) q += pat.size(); else name.push_back(base[q++]);
+            }
+            ok.push_back(out_dir + "/" + name + ".kmers.bin"); os.push_back(st_dir + "/" + name + ".stat.txt");
+        }
+        auto fp = cptrs(files), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni), pok = cptrs(ok), pos = cptrs(os);
+        vector<uint64_t> fk(2 * files.size() + 2, 0);
+        check(mf_kmers_multiple_filters(ctx, fp.data(), (int)fp.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(),
+                                        b, k, pok.data(), pos.data(), fk.data()));
+        for (size_t j = 0; j < files.size(); j++) {
+            char pct[64];
+            if (fk[2 * j]) snprintf(pct, sizeof pct, "%.1f", fk[2 * j + 1] * 100.0 / fk[2 * j]); else snprintf(pct, sizeof pct, "NaN");
+            logmsg("INFO", "%s k-mers found, %s (%s%%) of them survived after filtering", group_digits(fk[2 * j]).c_str(), group_digits(fk[2 * j + 1]).c_str(), pct);
+            logmsg("INFO", "Filtered k-mers printed to %s", ok[j].c_str());
+        }
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

@@ -39,19 +39,28 @@ __device__ __forceinline__ uint32_t mf_stats_slice(uint64_t h, uint32_t S) { ret
 // ---------------------------------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ void k_stats_init(mf_uslot *__restrict__ slots, uint64_t cap) {
+__global__ void k_stats_init(mf_uslot *__restrict__ slots, uint64_t cap, uint64_t y) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {
-        ulonglong2 v; v.x = MF_EMPTY; v.y = (uint64_t)MF_NO_ROW << 32;
+        ulonglong2 v; v.x = MF_EMPTY; v.y = y;
         *reinterpret_cast<ulonglong2 *>(&slots[i]) = v;
     }
 }
 
+// What a sample's entry adds to its key's slot:
+//   MF_UNION_PRESENCE  `add` to the presence word (stats-kmers, kmers-samples-counter)
+//   MF_UNION_SUM       the entry's value to the second word and 1 to the first (unique-kmers-multi: two words, so that the sum's carry
+//                      never reaches the sample count; sum <= 32767 * 65535 < 2^31)
+//   MF_UNION_FIELD     the entry's value to the 16-bit field number `add` of the slot (kmers-multiple-filters: cd, uc, nonibd; each
+//                      field is written by one table, whose keys are distinct, so no add carries)
+enum { MF_UNION_PRESENCE = 0, MF_UNION_SUM = 1, MF_UNION_FIELD = 2 };
 // flags: bit 0 = a key >= 2^62, bit 1 = the table is full (never with the sizes the host picks; an error, never a write out of bounds)
+template <int MODE>
 __global__ __launch_bounds__(256) void k_stats_union(mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
                                                      const uint16_t *__restrict__ cnts, uint64_t n, int thr, uint32_t add, uint32_t S, uint32_t s,
                                                      unsigned long long *__restrict__ n_union, unsigned int *__restrict__ flags) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        if ((int)cnts[i] <= thr) continue;
+        const uint32_t c = cnts[i];
+        if ((int)c <= thr) continue;
         const uint64_t key = keys[i];
         if (key >= MF_STATS_KEY_LIMIT) { atomicOr(flags, 1u); continue; }
         const uint64_t h = mf_hash64(key);
@@ -63,7 +72,10 @@ __global__ __launch_bounds__(256) void k_stats_union(mf_uslot *__restrict__ slot
                                                      (unsigned long long)key);
             if (old == MF_EMPTY || old == key) {
                 if (old == MF_EMPTY) atomicAdd(n_union, 1ull);
-                atomicAdd(&slots[p].cnt, add);
+                if (MODE == MF_UNION_PRESENCE) atomicAdd(&slots[p].cnt, add);
+                else if (MODE == MF_UNION_SUM) { atomicAdd(&slots[p].cnt, 1u); atomicAdd(&slots[p].row, c); }
+                else if (add == 2u) atomicAdd(&slots[p].row, c);
+                else atomicAdd(&slots[p].cnt, c << (16u * add));
                 done = true;
                 break;
             }
@@ -359,7 +371,7 @@ static unsigned grid_for(mf_ctx *ctx, uint64_t n) { return (unsigned)std::max<ui
 
 // union of one slice: every sample's entries with count > b; adds: add_of(j)
 static int union_slice(mf_ctx *ctx, const stats_get &get, int N, int b, uint32_t S, uint32_t s, uint64_t cap, mf_buf<mf_uslot> &slots,
-                       const std::function<uint32_t(int)> &add_of, uint64_t *n_union) {
+                       const std::function<uint32_t(int)> &add_of, uint64_t *n_union, int mode = MF_UNION_PRESENCE) {
     MF_TRY(slots.alloc(ctx, cap));
     mf_buf<unsigned long long> nu; MF_TRY(nu.alloc(ctx, 1));
     mf_buf<unsigned int> flags; MF_TRY(flags.alloc(ctx, 1));
@@ -367,14 +379,18 @@ static int union_slice(mf_ctx *ctx, const stats_get &get, int N, int b, uint32_t
     MF_HIP(hipMemsetAsync(flags.p, 0, 4, ctx->stream));
     {
         mf_ktimer tm(ctx, "k_stats_init");
-        k_stats_init<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap);
+        k_stats_init<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap, mode == MF_UNION_PRESENCE ? (uint64_t)MF_NO_ROW << 32 : 0ull);
     }
     for (int j = 0; j < N; j++) {
         mf_table *t = nullptr; bool own = false; uint64_t F = 0;
         MF_TRY(get(j, 0, &t, &own, &F));
         if (t->n) {
             mf_ktimer tm(ctx, "k_stats_union");
-            k_stats_union<<<grid_for(ctx, t->n), 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add_of(j), S, s, nu.p, flags.p);
+            const unsigned g = grid_for(ctx, t->n);
+            const uint32_t add = add_of(j);
+            if (mode == MF_UNION_PRESENCE) k_stats_union<MF_UNION_PRESENCE><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
+            else if (mode == MF_UNION_SUM) k_stats_union<MF_UNION_SUM><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
+            else k_stats_union<MF_UNION_FIELD><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
         }
         const hipError_t e = hipStreamSynchronize(ctx->stream);
         if (own) mf_table_destroy(t);
@@ -690,4 +706,485 @@ extern "C" int mf_kmers_samples_count(mf_ctx *ctx, const char *const *files, int
     mf_table_destroy(t);
     if (rc == MF_OK && n_kmers) *n_kmers = w;
     return rc;
+}
+
+// ===========================================================================================================================
+// unique-kmers-multi (src/tools/UniqueKmersMultipleSamplesFinder.java:84-185) and kmers-multiple-filters
+// (src/tools/KmersMultipleFilters.java:77-133, IOUtils.MultipleFiltersAndPrintKmers src/io/IOUtils.java:125-213) on the same union
+// table.
+//   unique-kmers-multi      union (MF_UNION_SUM) of the inputs; the filter samples' keys knock slots out (bit 31 of the sum word);
+//                           one select of (key, (short)sum, samples) with (short)sum > b; one sort by key; filtered_<i> = the
+//                           subsequence with samples >= i, by an order-keeping compaction.
+//   kmers-multiple-filters  probe table {key, cd, uc, nonibd} (MF_UNION_FIELD) of the three filter tables; per input sample one
+//                           probe per entry: the kept records and every entry's triple packed into 48 bits; the histogram is the
+//                           sort of the packed triples and a run-length pass.
+// ===========================================================================================================================
+int mf_sort_u64_u32(mf_ctx *ctx, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint32_t *d_vals_out);
+int mf_select_by(mf_ctx *ctx, const uint64_t *keys, const uint16_t *sel, const uint16_t *vals, uint64_t n, int thr, mf_buf<uint64_t> &ok,
+                 mf_buf<uint16_t> &oc, uint64_t *n_out);
+static constexpr uint64_t MF_JOIN_CURSOR_MAX = 0xFFFFFFFFull;      // the compaction cursors of the join's kernels are 32-bit
+
+static constexpr uint32_t MF_UKM_KNOCKED = 0x80000000u;
+
+// a filter sample's entries (count > thr): the slot of a key whose wrapped sum is > thr is knocked out
+__global__ __launch_bounds__(256) void k_ukm_knock(mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
+                                                   const uint16_t *__restrict__ cnts, uint64_t n, int thr, uint32_t S, uint32_t s,
+                                                   unsigned int *__restrict__ flags) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if ((int)cnts[i] <= thr) continue;
+        const uint64_t key = keys[i];
+        if (key >= MF_STATS_KEY_LIMIT) { atomicOr(flags, 1u); continue; }
+        const uint64_t h = mf_hash64(key);
+        if (mf_stats_slice(h, S) != s) continue;
+        uint64_t p = h & mask;
+        for (uint64_t probe = 0; probe <= mask; probe++) {
+            const ulonglong2 raw = *reinterpret_cast<const ulonglong2 *>(&slots[p]);
+            if (raw.x == key) {
+                if ((int)(int16_t)(uint16_t)(raw.y >> 32) > thr) atomicOr(&slots[p].row, MF_UKM_KNOCKED);
+                break;
+            }
+            if (raw.x == MF_EMPTY) break;
+            p = (p + 1) & mask;
+        }
+    }
+}
+
+// survivors: not knocked out and (short)sum > thr -> (key, (uint16)sum | samples << 16)   (uniform trip count: mf_wave_reserve)
+__global__ __launch_bounds__(256) void k_ukm_select(const mf_uslot *__restrict__ slots, uint64_t cap, int thr, uint64_t *__restrict__ okeys,
+                                                    uint32_t *__restrict__ ovals, unsigned int *__restrict__ cursor) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < cap; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        bool keep = false;
+        ulonglong2 raw; raw.x = MF_EMPTY; raw.y = 0;
+        if (i < cap) {
+            raw = *reinterpret_cast<const ulonglong2 *>(&slots[i]);
+            const uint32_t sw = (uint32_t)(raw.y >> 32);
+            keep = raw.x != MF_EMPTY && !(sw & MF_UKM_KNOCKED) && (int)(int16_t)(uint16_t)sw > thr;
+        }
+        const uint32_t r = mf_wave_reserve(cursor, keep ? 1u : 0u);
+        if (keep) { okeys[r] = raw.x; ovals[r] = (uint32_t)((raw.y >> 32) & 0xFFFFu) | ((uint32_t)raw.y << 16); }
+    }
+}
+
+// the sorted survivors' payload (uint16)sum | samples << 16 -> two 16-bit arrays (what the order-keeping selection of mf_table.hip takes)
+__global__ __launch_bounds__(256) void k_ukm_split(const uint32_t *__restrict__ v, uint64_t n, uint16_t *__restrict__ sums, uint16_t *__restrict__ cnts) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t x = v[i];
+        sums[i] = (uint16_t)x; cnts[i] = (uint16_t)(x >> 16);
+    }
+}
+
+// kmers-multiple-filters: every entry (count > thr) of an input sample in slice s probes {key, cd | uc << 16, nonibd}: its triple, packed
+// cd << 32 | uc << 16 | nonibd, goes to tri; the entry itself to (okeys, ovals) when a value of the triple is > 0.
+// cursor: [0] kept, [1] found.  (uniform trip count: mf_wave_reserve)
+__global__ __launch_bounds__(256) void k_kmf_probe(const mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
+                                                   const uint16_t *__restrict__ cnts, uint64_t n, int thr, uint32_t S, uint32_t s,
+                                                   uint64_t *__restrict__ okeys, uint16_t *__restrict__ ovals, uint64_t *__restrict__ tri,
+                                                   unsigned int *__restrict__ cursor, unsigned int *__restrict__ flags) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        bool found = false;
+        uint64_t key = 0, t = 0;
+        uint16_t c = 0;
+        if (i < n) {
+            c = cnts[i];
+            if ((int)c > thr) {
+                key = keys[i];
+                if (key >= MF_STATS_KEY_LIMIT) atomicOr(flags, 1u);
+                else {
+                    const uint64_t h = mf_hash64(key);
+                    if (mf_stats_slice(h, S) == s) {
+                        found = true;
+                        uint64_t p = h & mask;
+                        for (uint64_t probe = 0; probe <= mask; probe++) {
+                            const ulonglong2 raw = *reinterpret_cast<const ulonglong2 *>(&slots[p]);
+                            if (raw.x == key) { t = ((raw.y & 0xFFFFull) << 32) | (((raw.y >> 16) & 0xFFFFull) << 16) | ((raw.y >> 32) & 0xFFFFull); break; }
+                            if (raw.x == MF_EMPTY) break;
+                            p = (p + 1) & mask;
+                        }
+                    }
+                }
+            }
+        }
+        const bool keep = found && t != 0;
+        const uint32_t rk = mf_wave_reserve(&cursor[0], keep ? 1u : 0u);
+        const uint32_t rf = mf_wave_reserve(&cursor[1], found ? 1u : 0u);
+        if (keep) { okeys[rk] = key; ovals[rk] = c; }
+        if (found) tri[rf] = t;
+    }
+}
+
+// run heads of the sorted packed triples -> (triple, index of its first occurrence), in any order
+__global__ __launch_bounds__(256) void k_kmf_runs(const uint64_t *__restrict__ tri, uint64_t n, uint64_t *__restrict__ vals, uint64_t *__restrict__ starts,
+                                                  unsigned int *__restrict__ cursor) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        const bool head = i < n && (i == 0 || tri[i] != tri[i - 1]);
+        const uint32_t r = mf_wave_reserve(cursor, head ? 1u : 0u);
+        if (head) { vals[r] = tri[i]; starts[r] = i; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------------------------
+// a sample for a pass over a slice: *own: destroy after use
+using set_get = std::function<int(int j, mf_table **t, bool *own)>;
+
+static int read_flags(mf_ctx *ctx, mf_buf<unsigned int> &flags, const char *what) {
+    unsigned int fl = 0;
+    MF_HIP(hipMemcpyAsync(&fl, flags.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    if (fl & 1u) return mf_set_error("%s: a k-mer key >= 2^62 (k-mers files hold k <= 31)", what);
+    return MF_OK;
+}
+
+static int ukm_check(int n_in, int max_bad, int min_samples, int max_samples) {
+    if (max_bad < 0) return mf_set_error("unique-kmers-multi: maximal-bad-frequence = %d is negative", max_bad);
+    if (n_in > 32767) return mf_set_error("unique-kmers-multi: %d input files, at most 32767 (the number of samples is a Java short)", n_in);
+    if (min_samples > max_samples) return mf_set_error("--min-samples parameter cannot be greater than --max-samples parameter.");
+    return MF_OK;
+}
+
+// -> outs: one table per i = min_samples, min_samples + 1, ... up to max_samples or the first empty one (included); counts: their sizes
+static int ukm_join(mf_ctx *ctx, const set_get &get_in, int n_in, const set_get &get_f, int n_f, uint64_t total, int b, int min_samples, int max_samples,
+                    std::vector<mf_table *> &outs, std::vector<uint64_t> &counts, uint64_t *n_union) {
+    uint32_t S = 1; uint64_t cap = 0;
+    MF_TRY(plan_slices(ctx, total, &S, &cap));
+    std::vector<std::unique_ptr<mf_buf<uint64_t>>> pk;
+    std::vector<std::unique_ptr<mf_buf<uint32_t>>> pv;
+    std::vector<uint64_t> ns;
+    mf_buf<unsigned int> flags; MF_TRY(flags.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(flags.p, 0, 4, ctx->stream));
+    *n_union = 0;
+    const stats_get in_pass = [&](int j, int, mf_table **t, bool *own, uint64_t *) -> int { return get_in(j, t, own); };
+    for (uint32_t s = 0; s < S; s++) {
+        mf_buf<mf_uslot> slots; uint64_t nu = 0;
+        MF_TRY(union_slice(ctx, in_pass, n_in, b, S, s, cap, slots, [](int) { return 0u; }, &nu, MF_UNION_SUM));
+        *n_union += nu;
+        for (int j = 0; j < n_f; j++) {
+            mf_table *t = nullptr; bool own = false;
+            MF_TRY(get_f(j, &t, &own));
+            if (t->n) {
+                mf_ktimer tm(ctx, "k_ukm_knock");
+                k_ukm_knock<<<grid_for(ctx, t->n), 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, S, s, flags.p);
+            }
+            const hipError_t e = hipStreamSynchronize(ctx->stream);
+            if (own) mf_table_destroy(t);
+            if (e != hipSuccess) return mf_set_error("unique-kmers-multi: filter pass failed: %s", hipGetErrorString(e));
+        }
+        if (nu > MF_JOIN_CURSOR_MAX)
+            return mf_set_error("unique-kmers-multi: %llu union k-mers in one slice, at most 2^32 - 1 (raise option stats_slices)", (unsigned long long)nu);
+        pk.emplace_back(new mf_buf<uint64_t>()); pv.emplace_back(new mf_buf<uint32_t>());
+        MF_TRY(pk.back()->alloc(ctx, nu)); MF_TRY(pv.back()->alloc(ctx, nu));
+        mf_buf<unsigned int> cur; MF_TRY(cur.alloc(ctx, 1));
+        MF_HIP(hipMemsetAsync(cur.p, 0, 4, ctx->stream));
+        {
+            mf_ktimer tm(ctx, "k_ukm_select");
+            k_ukm_select<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap, b, pk.back()->p, pv.back()->p, cur.p);
+        }
+        unsigned int m = 0;
+        MF_HIP(hipMemcpyAsync(&m, cur.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+        if (m > nu) return mf_set_error("unique-kmers-multi: %u survivors of %llu union entries", m, (unsigned long long)nu);
+        ns.push_back(m);
+    }
+    MF_TRY(read_flags(ctx, flags, "unique-kmers-multi"));
+    // one sorted list of the survivors
+    mf_buf<uint64_t> keys, sk; mf_buf<uint32_t> vals, sv; uint64_t n = 0, n2 = 0;
+    {
+        std::vector<mf_buf<uint64_t> *> kp; std::vector<mf_buf<uint32_t> *> vp;
+        for (auto &x : pk) kp.push_back(x.get());
+        for (auto &x : pv) vp.push_back(x.get());
+        MF_TRY(concat(ctx, kp, ns, keys, &n));
+        MF_TRY(concat(ctx, vp, ns, vals, &n2));
+        pk.clear(); pv.clear();
+    }
+    MF_TRY(sk.alloc(ctx, n)); MF_TRY(sv.alloc(ctx, n));
+    if (n) MF_TRY(mf_sort_u64_u32(ctx, keys.p, vals.p, n, 62, sk.p, sv.p));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    keys.reset(); vals.reset();
+    // filtered_<i>: the subsequence with samples > i - 1 (the order-keeping selection of mf_table.hip)
+    mf_buf<uint16_t> sums, scnt;
+    MF_TRY(sums.alloc(ctx, n)); MF_TRY(scnt.alloc(ctx, n));
+    if (n) {
+        mf_ktimer tm(ctx, "k_ukm_split");
+        k_ukm_split<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(sv.p, n, sums.p, scnt.p);
+    }
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    sv.reset();
+    for (int64_t i = min_samples; i <= (int64_t)max_samples; i++) {
+        mf_buf<uint64_t> ok; mf_buf<uint16_t> ov; uint64_t m = 0;
+        // (no key is held by more than n_in samples, and every survivor by at least one)
+        if (i > n_in) { MF_TRY(ok.alloc(ctx, 0)); MF_TRY(ov.alloc(ctx, 0)); }
+        else MF_TRY(mf_select_by(ctx, sk.p, scnt.p, sums.p, n, (int)std::max<int64_t>(i - 1, -1), ok, ov, &m));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+        mf_table *t = nullptr;
+        const size_t kb = ok.bytes(), vb = ov.bytes();
+        MF_TRY(mf_table_adopt(ctx, 31, m, 0, ok.take(), kb, ov.take(), vb, &t));
+        outs.push_back(t);
+        counts.push_back(m);
+        if (!m) break;
+    }
+    return MF_OK;
+}
+
+static void destroy_all(std::vector<mf_table *> &v) { for (mf_table *t : v) mf_table_destroy(t); v.clear(); }
+
+static int tables_total(mf_ctx *ctx, mf_table *const *t, int n, const char *what, uint64_t *total) {
+    for (int j = 0; j < n; j++) {
+        if (!t[j]) return mf_set_error("%s: table %d is NULL", what, j);
+        if (t[j]->ctx != ctx) return mf_set_error("%s: table %d belongs to another context", what, j);
+        if (total) *total += t[j]->n;
+    }
+    return MF_OK;
+}
+
+extern "C" int mf_unique_kmers_multi_tables(mf_ctx *ctx, mf_table *const *inputs, int n_inputs, mf_table *const *filters, int n_filters, int max_bad,
+                                            int min_samples, int max_samples, mf_table **out, int *n_out, uint64_t *n_union, uint64_t *counts) {
+    mf_range rng_("mf:unique_kmers_multi");
+    if (!ctx || !out || !n_out || !n_union || !counts || (n_inputs && !inputs) || (n_filters && !filters) || n_inputs < 0 || n_filters < 0)
+        return mf_set_error("mf_unique_kmers_multi_tables: NULL argument");
+    *n_out = 0;
+    MF_TRY(ukm_check(n_inputs, max_bad, min_samples, max_samples));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    MF_TRY(tables_total(ctx, inputs, n_inputs, "mf_unique_kmers_multi_tables (inputs)", &total));
+    MF_TRY(tables_total(ctx, filters, n_filters, "mf_unique_kmers_multi_tables (filters)", nullptr));
+    const set_get gi = [&](int j, mf_table **t, bool *own) -> int { *t = inputs[j]; *own = false; return MF_OK; };
+    const set_get gf = [&](int j, mf_table **t, bool *own) -> int { *t = filters[j]; *own = false; return MF_OK; };
+    std::vector<mf_table *> outs; std::vector<uint64_t> cs;
+    const int rc = ukm_join(ctx, gi, n_inputs, gf, n_filters, total, max_bad, min_samples, max_samples, outs, cs, n_union);
+    if (rc != MF_OK) { destroy_all(outs); return rc; }
+    for (size_t i = 0; i < outs.size(); i++) { out[i] = outs[i]; counts[i] = cs[i]; }
+    *n_out = (int)outs.size();
+    return MF_OK;
+}
+
+extern "C" int mf_unique_kmers_multi(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters, int max_bad,
+                                     int k, int min_samples, int max_samples, const char *out_dir, int *n_out, uint64_t *n_union, uint64_t *counts) {
+    mf_range rng_("mf:unique_kmers_multi(files)");
+    if (!ctx || !out_dir || !n_out || !n_union || !counts || (n_inputs && !in_files) || (n_filters && !filter_files) || n_inputs < 0 || n_filters < 0)
+        return mf_set_error("mf_unique_kmers_multi: NULL argument");
+    *n_out = 0;
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    MF_TRY(ukm_check(n_inputs, max_bad, min_samples, max_samples));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0, tf = 0;
+    MF_TRY(file_records(in_files, n_inputs, &total));
+    MF_TRY(file_records(filter_files, n_filters, &tf));
+    auto loader = [&](const char *const *files) {
+        return [=](int j, mf_table **t, bool *own) -> int {
+            const char *one[1] = {files[j]};
+            *own = true;
+            return mf_table_load_kmers_sum(ctx, one, 1, max_bad, k, t, nullptr);
+        };
+    };
+    const set_get gi = loader(in_files), gf = loader(filter_files);
+    std::vector<mf_table *> outs; std::vector<uint64_t> cs;
+    int rc = ukm_join(ctx, gi, n_inputs, gf, n_filters, total, max_bad, min_samples, max_samples, outs, cs, n_union);
+    for (size_t i = 0; i < outs.size() && rc == MF_OK; i++) {
+        uint64_t w = 0;
+        rc = mf_table_write_kmers(outs[i], -1, (std::string(out_dir) + "/filtered_" + std::to_string((long long)min_samples + (long long)i) + ".kmers.bin").c_str(), nullptr, &w);
+    }
+    if (rc == MF_OK) { for (size_t i = 0; i < cs.size(); i++) counts[i] = cs[i]; *n_out = (int)cs.size(); }
+    destroy_all(outs);
+    return rc;
+}
+
+// ---- kmers-multiple-filters ----
+struct kmf_result { mf_table *kept = nullptr; std::vector<uint64_t> triples, counts; uint64_t found = 0; };
+using kmf_sink = std::function<int(int j, kmf_result &r)>;          // takes r.kept over (destroys it)
+
+// the packed triples of one (input, slice) -> added to hist
+static int kmf_histogram(mf_ctx *ctx, mf_buf<uint64_t> &tri, uint64_t m, std::map<uint64_t, uint64_t> &hist) {
+    if (!m) return MF_OK;
+    mf_buf<uint64_t> st; mf_buf<uint16_t> d0, d1;
+    MF_TRY(st.alloc(ctx, m)); MF_TRY(d0.alloc(ctx, m)); MF_TRY(d1.alloc(ctx, m));
+    MF_HIP(hipMemsetAsync(d0.p, 0, d0.bytes(), ctx->stream));
+    MF_TRY(mf_sort_pairs(ctx, tri.p, d0.p, m, 48, st.p, d1.p));
+    d0.reset(); d1.reset();
+    mf_buf<unsigned int> cur; MF_TRY(cur.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(cur.p, 0, 4, ctx->stream));
+    // (the run heads reuse tri: it has been sorted into st)
+    mf_buf<uint64_t> starts; MF_TRY(starts.alloc(ctx, m));
+    {
+        mf_ktimer tm(ctx, "k_kmf_runs");
+        k_kmf_runs<<<grid_for(ctx, m), 256, 0, ctx->stream>>>(st.p, m, tri.p, starts.p, cur.p);
+    }
+    unsigned int r = 0;
+    MF_HIP(hipMemcpyAsync(&r, cur.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    if (r > m) return mf_set_error("kmers-multiple-filters: %u runs in %llu triples", r, (unsigned long long)m);
+    std::vector<uint64_t> hv(r), hs(r);
+    if (r) {
+        MF_HIP(hipMemcpyAsync(hv.data(), tri.p, (size_t)r * 8, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipMemcpyAsync(hs.data(), starts.p, (size_t)r * 8, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    std::vector<uint32_t> order(r);
+    for (uint32_t i = 0; i < r; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return hs[x] < hs[y]; });
+    for (uint32_t i = 0; i < r; i++) {
+        const uint64_t end = i + 1 < r ? hs[order[i + 1]] : m;
+        hist[hv[order[i]]] += end - hs[order[i]];
+    }
+    return MF_OK;
+}
+
+// filter tables 0 = CD, 1 = UC, 2 = NONIBD (threshold 0), `total_f` an upper bound of their entries; inputs at threshold b
+static int kmf_join(mf_ctx *ctx, const set_get &get_filter, uint64_t total_f, const set_get &get_in, int n_in, int b, const kmf_sink &sink) {
+    uint32_t S = 1; uint64_t cap = 0;
+    MF_TRY(plan_slices(ctx, total_f, &S, &cap));
+    struct per_input {
+        std::vector<std::unique_ptr<mf_buf<uint64_t>>> pk; std::vector<std::unique_ptr<mf_buf<uint16_t>>> pv; std::vector<uint64_t> ns;
+        std::map<uint64_t, uint64_t> hist; uint64_t found = 0;
+    };
+    std::vector<per_input> acc((size_t)n_in);
+    mf_buf<unsigned int> flags; MF_TRY(flags.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(flags.p, 0, 4, ctx->stream));
+    const stats_get f_pass = [&](int j, int, mf_table **t, bool *own, uint64_t *) -> int { return get_filter(j, t, own); };
+    for (uint32_t s = 0; s < S; s++) {
+        mf_buf<mf_uslot> slots; uint64_t nu = 0;
+        MF_TRY(union_slice(ctx, f_pass, 3, 0, S, s, cap, slots, [](int j) { return (uint32_t)j; }, &nu, MF_UNION_FIELD));
+        for (int j = 0; j < n_in; j++) {
+            per_input &a = acc[(size_t)j];
+            mf_table *t = nullptr; bool own = false;
+            MF_TRY(get_in(j, &t, &own));
+            const uint64_t n = t->n;
+            mf_buf<uint64_t> ok, tri; mf_buf<uint16_t> ov; mf_buf<unsigned int> cur;
+            int rc = n > MF_JOIN_CURSOR_MAX ? mf_set_error("kmers-multiple-filters: input %d has %llu entries, at most 2^32 - 1", j, (unsigned long long)n) : MF_OK;
+            if (rc == MF_OK) rc = ok.alloc(ctx, n);
+            if (rc == MF_OK) rc = ov.alloc(ctx, n);
+            if (rc == MF_OK) rc = tri.alloc(ctx, n);
+            if (rc == MF_OK) rc = cur.alloc(ctx, 2);
+            unsigned int cc[2] = {0, 0};
+            if (rc == MF_OK) {
+                hipError_t e = hipMemsetAsync(cur.p, 0, 8, ctx->stream);
+                if (e == hipSuccess && n) {
+                    mf_ktimer tm(ctx, "k_kmf_probe");
+                    k_kmf_probe<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, n, b, S, s, ok.p, ov.p, tri.p, cur.p, flags.p);
+                }
+                if (e == hipSuccess) e = hipMemcpyAsync(cc, cur.p, 8, hipMemcpyDeviceToHost, ctx->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                if (e != hipSuccess) rc = mf_set_error("kmers-multiple-filters: probe pass failed: %s", hipGetErrorString(e));
+            }
+            if (own) mf_table_destroy(t);
+            MF_TRY(rc);
+            if (cc[0] > n || cc[1] > n) return mf_set_error("kmers-multiple-filters: %u kept and %u found of %llu entries", cc[0], cc[1], (unsigned long long)n);
+            MF_TRY(read_flags(ctx, flags, "kmers-multiple-filters"));
+            a.found += cc[1];
+            MF_TRY(kmf_histogram(ctx, tri, cc[1], a.hist));
+            tri.reset();
+            // the kept records of this slice, in buffers of their size
+            a.pk.emplace_back(new mf_buf<uint64_t>()); a.pv.emplace_back(new mf_buf<uint16_t>());
+            MF_TRY(a.pk.back()->alloc(ctx, cc[0])); MF_TRY(a.pv.back()->alloc(ctx, cc[0]));
+            if (cc[0]) {
+                MF_HIP(hipMemcpyAsync(a.pk.back()->p, ok.p, (size_t)cc[0] * 8, hipMemcpyDeviceToDevice, ctx->stream));
+                MF_HIP(hipMemcpyAsync(a.pv.back()->p, ov.p, (size_t)cc[0] * 2, hipMemcpyDeviceToDevice, ctx->stream));
+                MF_HIP(hipStreamSynchronize(ctx->stream));
+            }
+            a.ns.push_back(cc[0]);
+            if (s + 1 < S) continue;
+            // last slice: this input is complete
+            std::vector<mf_buf<uint64_t> *> kp; std::vector<mf_buf<uint16_t> *> vp;
+            for (auto &x : a.pk) kp.push_back(x.get());
+            for (auto &x : a.pv) vp.push_back(x.get());
+            ok.reset(); ov.reset();
+            mf_buf<uint64_t> keys; mf_buf<uint16_t> vals; uint64_t nk = 0, nk2 = 0;
+            MF_TRY(concat(ctx, kp, a.ns, keys, &nk));
+            MF_TRY(concat(ctx, vp, a.ns, vals, &nk2));
+            a.pk.clear(); a.pv.clear();
+            kmf_result r;
+            MF_TRY(pairs_to_table(ctx, keys, vals, nk, &r.kept));
+            r.found = a.found;
+            for (auto &kv : a.hist) { r.triples.push_back(kv.first); r.counts.push_back(kv.second); }
+            a.hist.clear();
+            MF_TRY(sink(j, r));
+        }
+    }
+    return MF_OK;
+}
+
+static int empty_table(mf_ctx *ctx, mf_table **out) {
+    mf_buf<uint64_t> k; mf_buf<uint16_t> v;
+    MF_TRY(k.alloc(ctx, 0)); MF_TRY(v.alloc(ctx, 0));
+    return pairs_to_table(ctx, k, v, 0, out);
+}
+
+extern "C" int mf_kmers_multiple_filters_tables(mf_ctx *ctx, mf_table *table, mf_table *cd, mf_table *uc, mf_table *nonibd, int max_bad, mf_table **kept,
+                                                uint64_t *triples, uint64_t *triple_counts, uint64_t cap, uint64_t *n_triples, uint64_t *found_kept) {
+    mf_range rng_("mf:kmers_multiple_filters");
+    if (!ctx || !table || !cd || !uc || !nonibd || !kept || !n_triples || !found_kept || (cap && (!triples || !triple_counts)))
+        return mf_set_error("mf_kmers_multiple_filters_tables: NULL argument");
+    *kept = nullptr;
+    if (max_bad < 0) return mf_set_error("kmers-multiple-filters: maximal-bad-frequence = %d is negative", max_bad);
+    MF_HIP(hipSetDevice(ctx->device));
+    mf_table *all[4] = {cd, uc, nonibd, table};
+    uint64_t total = 0;
+    MF_TRY(tables_total(ctx, all, 4, "mf_kmers_multiple_filters_tables", &total));
+    total -= table->n;
+    const set_get gf = [&](int j, mf_table **t, bool *own) -> int { *t = all[j]; *own = false; return MF_OK; };
+    const set_get gi = [&](int, mf_table **t, bool *own) -> int { *t = table; *own = false; return MF_OK; };
+    const kmf_sink sink = [&](int, kmf_result &r) -> int {
+        *kept = r.kept;
+        *n_triples = r.triples.size();
+        for (size_t i = 0; i < r.triples.size() && i < cap; i++) { triples[i] = r.triples[i]; triple_counts[i] = r.counts[i]; }
+        found_kept[0] = r.found; found_kept[1] = r.kept->n;
+        return MF_OK;
+    };
+    const int rc = kmf_join(ctx, gf, total, gi, 1, max_bad, sink);
+    if (rc != MF_OK && *kept) { mf_table_destroy(*kept); *kept = nullptr; }
+    return rc;
+}
+
+extern "C" int mf_kmers_multiple_filters(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *cd_files, int n_cd,
+                                         const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
+                                         const char *const *out_kmers, const char *const *out_stats, uint64_t *found_kept) {
+    mf_range rng_("mf:kmers_multiple_filters(files)");
+    if (!ctx || (n_inputs && (!in_files || !out_kmers)) || (n_cd && !cd_files) || (n_uc && !uc_files) || (n_nonibd && !nonibd_files) || n_inputs < 0 ||
+        n_cd < 0 || n_uc < 0 || n_nonibd < 0)
+        return mf_set_error("mf_kmers_multiple_filters: NULL argument");
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    if (max_bad < 0) return mf_set_error("kmers-multiple-filters: maximal-bad-frequence = %d is negative", max_bad);
+    MF_HIP(hipSetDevice(ctx->device));
+    const char *const *lists[3] = {cd_files, uc_files, nonibd_files};
+    const int nl[3] = {n_cd, n_uc, n_nonibd};
+    uint64_t total = 0, ti = 0;
+    for (int g = 0; g < 3; g++) { uint64_t x = 0; MF_TRY(file_records(lists[g], nl[g], &x)); total += x; }
+    MF_TRY(file_records(in_files, n_inputs, &ti));
+    for (int j = 0; j < n_inputs; j++) if (!out_kmers[j]) return mf_set_error("mf_kmers_multiple_filters: output path %d is NULL", j);
+    const set_get gf = [&](int g, mf_table **t, bool *own) -> int {
+        *own = true;
+        if (!nl[g]) return empty_table(ctx, t);
+        return mf_table_load_kmers_sum(ctx, lists[g], nl[g], 0, k, t, nullptr);
+    };
+    const set_get gi = [&](int j, mf_table **t, bool *own) -> int {
+        const char *one[1] = {in_files[j]};
+        *own = true;
+        return mf_table_load_kmers_sum(ctx, one, 1, max_bad, k, t, nullptr);
+    };
+    const kmf_sink sink = [&](int j, kmf_result &r) -> int {
+        uint64_t w = 0;
+        int rc = mf_table_write_kmers(r.kept, -1, out_kmers[j], nullptr, &w);
+        if (rc == MF_OK && out_stats && out_stats[j]) {
+            FILE *f = fopen(out_stats[j], "w");
+            if (!f) rc = mf_set_error("can't write '%s'", out_stats[j]);
+            else {
+                fprintf(f, "# cd k-mer samples\tuc k-mer samples\tnonIBD k-mer samples\tnumber of such k-mers\n");
+                for (size_t i = 0; i < r.triples.size(); i++)
+                    fprintf(f, "%u\t%u\t%u\t%llu\n", (unsigned)(r.triples[i] >> 32) & 0xFFFFu, (unsigned)(r.triples[i] >> 16) & 0xFFFFu,
+                            (unsigned)r.triples[i] & 0xFFFFu, (unsigned long long)r.counts[i]);
+                fprintf(f, "\n");
+                if (fclose(f) != 0) rc = mf_set_error("can't write '%s'", out_stats[j]);
+            }
+        }
+        if (found_kept) { found_kept[2 * j] = r.found; found_kept[2 * j + 1] = w; }
+        mf_table_destroy(r.kept); r.kept = nullptr;
+        return rc;
+    };
+    return kmf_join(ctx, gf, total, gi, n_inputs, max_bad, sink);
 }

@@ -163,10 +163,11 @@ __global__ __launch_bounds__(256) void k_part_selcount(const uint16_t *__restric
 
 // ---- stable stream compaction in two passes: select entries with pred(i) ----
 // MODE 0: table entries with count > thr.   MODE 1: non-empty index slots (val clamped to 32767).
+// MODE 2: entries with count > thr, written with the value of a second array (vals) instead of the count.
 template <int MODE>
 __device__ __forceinline__ bool mf_sel_pred(const uint64_t *keys, const uint16_t *cnts, const mf_slot *slots, uint64_t i,
                                             int thr) {
-    if (MODE == 0) return (int)cnts[i] > thr;
+    if (MODE == 0 || MODE == 2) return (int)cnts[i] > thr;
     return slots[i].key != MF_EMPTY;
 }
 template <int MODE>
@@ -185,7 +186,7 @@ template <int MODE>
 __global__ __launch_bounds__(1024) void k_select_write(const uint64_t *__restrict__ keys, const uint16_t *__restrict__ cnts,
                                                         const mf_slot *__restrict__ slots, uint64_t n, uint64_t per_block,
                                                         int thr, const uint64_t *__restrict__ boff,
-                                                        uint64_t *__restrict__ ok, uint16_t *__restrict__ oc) {
+                                                        uint64_t *__restrict__ ok, uint16_t *__restrict__ oc, const uint16_t *__restrict__ vals) {
     __shared__ uint32_t scratch[17];
     uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = lo + per_block < n ? lo + per_block : n;
     uint64_t base = boff[blockIdx.x];
@@ -196,6 +197,7 @@ __global__ __launch_bounds__(1024) void k_select_write(const uint64_t *__restric
         uint32_t ex = mf_block_excl_scan(sel ? 1u : 0u, scratch, &tot);
         if (sel) {
             if (MODE == 0) { ok[base + ex] = keys[i]; oc[base + ex] = cnts[i]; }
+            else if (MODE == 2) { ok[base + ex] = keys[i]; oc[base + ex] = vals[i]; }
             else {
                 uint32_t v = slots[i].val;
                 ok[base + ex] = slots[i].key;
@@ -362,7 +364,7 @@ extern "C" int mf_table_device_view(const mf_table *t, const void **d_keys, cons
 // device-side selection into fresh dense arrays
 template <int MODE>
 static int select_entries(mf_ctx *ctx, const uint64_t *keys, const uint16_t *cnts, const mf_slot *slots, uint64_t n, int thr,
-                          mf_buf<uint64_t> &ok, mf_buf<uint16_t> &oc, uint64_t *n_out) {
+                          mf_buf<uint64_t> &ok, mf_buf<uint16_t> &oc, uint64_t *n_out, const uint16_t *vals = nullptr) {
     *n_out = 0;
     if (!n) { MF_TRY(ok.alloc(ctx, 0)); MF_TRY(oc.alloc(ctx, 0)); return MF_OK; }
     uint64_t nb = std::min<uint64_t>((n + 1023) / 1024, 2048);
@@ -382,10 +384,15 @@ static int select_entries(mf_ctx *ctx, const uint64_t *keys, const uint16_t *cnt
     MF_TRY(ok.alloc(ctx, m)); MF_TRY(oc.alloc(ctx, m));
     if (m) {
         mf_ktimer t(ctx, "k_select");
-        k_select_write<MODE><<<(unsigned)nb, 1024, 0, ctx->stream>>>(keys, cnts, slots, n, per, thr, boff.p, ok.p, oc.p);
+        k_select_write<MODE><<<(unsigned)nb, 1024, 0, ctx->stream>>>(keys, cnts, slots, n, per, thr, boff.p, ok.p, oc.p, vals);
     }
     *n_out = m;
     return MF_OK;
+}
+// the (keys[i], vals[i]) with sel[i] > thr, order kept (the join of mf_stats.hip: one sorted list, one subsequence per threshold)
+int mf_select_by(mf_ctx *ctx, const uint64_t *keys, const uint16_t *sel, const uint16_t *vals, uint64_t n, int thr, mf_buf<uint64_t> &ok,
+                 mf_buf<uint16_t> &oc, uint64_t *n_out) {
+    return select_entries<2>(ctx, keys, sel, nullptr, n, thr, ok, oc, n_out, vals);
 }
 
 extern "C" int mf_table_filter(const mf_table *t, int threshold, mf_table **out) {

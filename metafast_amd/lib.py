@@ -147,6 +147,11 @@ _SIGS = {
     "mf_stats_kmers": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, C.c_double, C.c_double, cp, vp]),
     "mf_kmers_samples_count_tables": (i32, [vp, vp, i32, i32, pvp]),
     "mf_kmers_samples_count": (i32, [vp, C.POINTER(cp), i32, i32, i32, cp, cp, pu64]),
+    "mf_unique_kmers_multi_tables": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, C.POINTER(C.c_int), pu64, vp]),
+    "mf_unique_kmers_multi": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, i32, i32, cp, C.POINTER(C.c_int), pu64, vp]),
+    "mf_kmers_multiple_filters_tables": (i32, [vp, vp, vp, vp, vp, i32, pvp, vp, vp, u64, pu64, vp]),
+    "mf_kmers_multiple_filters": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32,
+                                        C.POINTER(cp), C.POINTER(cp), vp]),
 }
 
 STATS_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "unique_left")
@@ -462,6 +467,56 @@ class Context:
         n = C.c_uint64()
         _check(lib().mf_kmers_samples_count(self.h, _cfiles(files), len(files), max_bad, k, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
         return n.value
+
+    @staticmethod
+    def _ukm_slots(n_inputs, min_samples, max_samples):
+        return max(1, min(max_samples, max(min_samples, n_inputs + 1)) - min_samples + 1)
+
+    def unique_kmers_multi(self, inputs, filters, max_bad=1, min_samples=1, max_samples=1):
+        """UniqueKmersMultipleSamplesFinder (src/tools/UniqueKmersMultipleSamplesFinder.java:84-185) on resident tables ->
+        ([Table of filtered_<i> for i = min_samples ... up to the first empty one], n_union, [c_i])"""
+        hi = (C.c_void_p * max(len(inputs), 1))(*[t.h for t in inputs])
+        hf = (C.c_void_p * max(len(filters), 1))(*[t.h for t in filters])
+        slots = self._ukm_slots(len(inputs), min_samples, max_samples)
+        out = (C.c_void_p * slots)()
+        counts = np.zeros(slots, dtype=np.uint64)
+        n_out, n_union = C.c_int(), C.c_uint64()
+        _check(lib().mf_unique_kmers_multi_tables(self.h, hi, len(inputs), hf, len(filters), max_bad, min_samples, max_samples, out,
+                                                  C.byref(n_out), C.byref(n_union), counts.ctypes.data))
+        return [Table(self, C.c_void_p(out[i])) for i in range(n_out.value)], n_union.value, [int(c) for c in counts[:n_out.value]]
+
+    def unique_kmers_multi_files(self, in_files, filter_files, k, out_dir, max_bad=1, min_samples=1, max_samples=1):
+        """the same from .kmers.bin files -> out_dir/filtered_<i>.kmers.bin; returns (n_union, [c_i])"""
+        slots = self._ukm_slots(len(in_files), min_samples, max_samples)
+        counts = np.zeros(slots, dtype=np.uint64)
+        n_out, n_union = C.c_int(), C.c_uint64()
+        _check(lib().mf_unique_kmers_multi(self.h, _cfiles(in_files), len(in_files), _cfiles(filter_files), len(filter_files), max_bad, k,
+                                           min_samples, max_samples, os.fsencode(out_dir), C.byref(n_out), C.byref(n_union), counts.ctypes.data))
+        return n_union.value, [int(c) for c in counts[:n_out.value]]
+
+    def kmers_multiple_filters(self, table, cd, uc, nonibd, max_bad=1):
+        """IOUtils.MultipleFiltersAndPrintKmers (src/io/IOUtils.java:125-213) on resident tables -> (Table of the kept entries,
+        int64[m][3] distinct (cd, uc, nonibd) triples in ascending order, uint64[m] entries of each, found, kept)"""
+        cap = max(len(table), 1)
+        tri = np.zeros(cap, dtype=np.uint64)
+        cnt = np.zeros(cap, dtype=np.uint64)
+        fk = np.zeros(2, dtype=np.uint64)
+        kept, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mf_kmers_multiple_filters_tables(self.h, table.h, cd.h, uc.h, nonibd.h, max_bad, C.byref(kept), tri.ctypes.data,
+                                                      cnt.ctypes.data, cap, C.byref(n), fk.ctypes.data))
+        tri = tri[:n.value]
+        triples = np.stack([(tri >> np.uint64(32)) & np.uint64(0xFFFF), (tri >> np.uint64(16)) & np.uint64(0xFFFF), tri & np.uint64(0xFFFF)],
+                           axis=1).astype(np.int64)
+        return Table(self, kept), triples, cnt[:n.value], int(fk[0]), int(fk[1])
+
+    def kmers_multiple_filters_files(self, in_files, cd_files, uc_files, nonibd_files, k, out_kmers, out_stats=None, max_bad=1):
+        """KmersMultipleFilters (src/tools/KmersMultipleFilters.java:77-133): input j -> out_kmers[j] (+ out_stats[j]); returns
+        [(found, kept)] per input"""
+        fk = np.zeros(2 * max(len(in_files), 1), dtype=np.uint64)
+        _check(lib().mf_kmers_multiple_filters(self.h, _cfiles(in_files), len(in_files), _cfiles(cd_files), len(cd_files), _cfiles(uc_files),
+                                               len(uc_files), _cfiles(nonibd_files), len(nonibd_files), max_bad, k, _cfiles(out_kmers),
+                                               _cfiles(out_stats) if out_stats else None, fk.ctypes.data))
+        return [(int(fk[2 * j]), int(fk[2 * j + 1])) for j in range(len(in_files))]
 
     # ---- synthetic reads ----
     def synth_reads_device(self, seed, sample, first_read, n_reads, read_len, genome_scale_bp, d_bases, d_offsets, sub_per_16384=82):
