@@ -667,36 +667,79 @@ int mf_cc_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_counts, const 
     return MF_OK;
 }
 
+// The adjacency of a table whose index is built.  local: the partition-local lookups of mf_nbr.h (the table must have minimizer partitions and
+// their index: cc_adjacency_has_parts), MODE 1 then MODE 2; else eight lookups per vertex in the HBM index.
+static bool cc_adjacency_has_parts(const mf_table *t) { return t->index.skm_k && t->index.part_bits && t->d_part_off; }
+static void cc_adjacency_launch(mf_ctx *ctx, const mf_table *t, bool local, uint32_t *nbr) {
+    hipStream_t st = ctx->stream;
+    const uint64_t n = t->n;
+    const int k = t->k;
+    if (local) {
+        const uint32_t np = 1u << t->part_bits;
+        const unsigned grid = (unsigned)std::min<uint64_t>((np + NB_WAVES - 1) / NB_WAVES, (uint64_t)ctx->n_cu * 64);
+        const unsigned grid2 = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * 16);
+#define CC_ADJ_K(KK) case KK: k_cc_adjacency_part<1, KK><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr); \
+                      k_cc_adjacency_part<2, KK><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr); break;
+        switch (k) {                                                    // (k as a compile-time constant: see k_ut_flags_part's dispatch, mf_unitig.hip)
+            CC_ADJ_K(21) CC_ADJ_K(23) CC_ADJ_K(25) CC_ADJ_K(27) CC_ADJ_K(29) CC_ADJ_K(31)
+            default:
+                k_cc_adjacency_part<1><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr);
+                k_cc_adjacency_part<2><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr);
+        }
+#undef CC_ADJ_K
+    } else
+        k_cc_adjacency<<<cgrid(n), 256, 0, st>>>(mf_view(t->index), t->d_keys, n, k, nbr);
+}
+
 extern "C" int mf_cut_components_device(mf_ctx *ctx, mf_table *t, int b1, int b2, mf_comps **out) {
     mf_range rng_("mf:components");
     if (!ctx || !t || !out) return mf_set_error("mf_cut_components_device: NULL argument");
     *out = nullptr;
     MF_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     const uint64_t n = t->n;
     const int k = t->k;
     if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
     if (n) MF_TRY(mf_table_ensure_index(t));
     return mf_cc_build(ctx, n, k, t->d_counts, t->d_keys, b1, b2, [&](uint32_t *nbr) -> int {
-        {
-            if (t->index.skm_k && t->index.part_bits && t->d_part_off && !ctx->opt_nbr_global && (n >> t->part_bits) >= 100) {      // (small partitions: the set-up per partition outweighs the local lookups)
-                const uint32_t np = 1u << t->part_bits;
-                const unsigned grid = (unsigned)std::min<uint64_t>((np + NB_WAVES - 1) / NB_WAVES, (uint64_t)ctx->n_cu * 64);
-                const unsigned grid2 = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * 16);
-#define CC_ADJ_K(KK) case KK: k_cc_adjacency_part<1, KK><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr); \
-                              k_cc_adjacency_part<2, KK><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr); break;
-                switch (k) {                                                    // (k as a compile-time constant: see k_ut_flags_part's dispatch, mf_unitig.hip)
-                    CC_ADJ_K(21) CC_ADJ_K(23) CC_ADJ_K(25) CC_ADJ_K(27) CC_ADJ_K(29) CC_ADJ_K(31)
-                    default:
-                        k_cc_adjacency_part<1><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr);
-                        k_cc_adjacency_part<2><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(t->index), t->d_keys, t->d_part_off, np, k, nbr);
-                }
-#undef CC_ADJ_K
-            } else
-            k_cc_adjacency<<<cgrid(n), 256, 0, st>>>(mf_view(t->index), t->d_keys, n, k, nbr);
-        }
+        // (small partitions: the set-up per partition outweighs the local lookups; nbr_global = -1 takes them all the same, 1 never)
+        const bool local = cc_adjacency_has_parts(t) && ctx->opt_nbr_global <= 0 && (ctx->opt_nbr_global < 0 || (n >> t->part_bits) >= 100);
+        cc_adjacency_launch(ctx, t, local, nbr);
         return MF_OK;
     }, out);
+}
+
+// For the tests (not in include/metafast_hip.h): the adjacency alone, by one chosen path, with the table's layout.  path 0: k_cc_adjacency; path 1: the
+// launches of k_cc_adjacency_part as mf_cut_components_device makes them -- an error where the table has no minimizer partitions or
+// their index.  keys_out[n]: the keys in table order; nbr_out[8 n]: table positions or 0xFFFFFFFF; *part_bits and part_off_out[2^part_bits + 1]:
+// the partitions of the table (0 and untouched: it has none).
+extern "C" int mf_debug_neighbours(mf_ctx *ctx, mf_table *t, int path, uint64_t *keys_out, uint32_t *nbr_out, int *part_bits, uint64_t *part_off_out,
+                                   uint64_t part_off_cap) {
+    if (!ctx || !t || !keys_out || !nbr_out || !part_bits) return mf_set_error("mf_debug_neighbours: NULL argument");
+    if (t->ctx != ctx) return mf_set_error("mf_debug_neighbours: the table belongs to another context");
+    if (path != 0 && path != 1) return mf_set_error("mf_debug_neighbours: path %d", path);
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = t->n;
+    if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
+    const bool parts = t->part_bits > 0 && t->d_part_off;
+    *part_bits = parts ? t->part_bits : 0;
+    if (parts && part_off_out) {
+        const uint64_t need = (1ull << t->part_bits) + 1;
+        if (part_off_cap < need) return mf_set_error("mf_debug_neighbours: room for %llu partition offsets, the table has %llu", (unsigned long long)part_off_cap, (unsigned long long)need);
+        MF_HIP(hipMemcpyAsync(part_off_out, t->d_part_off, need * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (n) MF_TRY(mf_table_ensure_index(t));
+    if (path == 1 && !cc_adjacency_has_parts(t))
+        return mf_set_error("mf_debug_neighbours: the table has no index over minimizer partitions (the partition-local lookup cannot run on it)");
+    if (n) {
+        mf_buf<uint32_t> nbr; MF_TRY(nbr.alloc(ctx, n * 8));
+        cc_adjacency_launch(ctx, t, path == 1, nbr.p);
+        MF_HIP(hipGetLastError());
+        MF_HIP(hipMemcpyAsync(nbr_out, nbr.p, n * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(keys_out, t->d_keys, n * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipStreamSynchronize(st));                  // (nbr is released below)
+    } else MF_HIP(hipStreamSynchronize(st));
+    return MF_OK;
 }
 
 extern "C" void mf_comps_destroy(mf_comps *c) {

@@ -809,7 +809,7 @@ extern "C" int mf_build_unitigs_device(mf_ctx *ctx, mf_table *t, int freq_thresh
                     100.0 * b[3] / n, 100.0 * b[4] / n, 100.0 * b[5] / n);
         }
         {
-            if (g->index.skm_k && g->index.part_bits && g->d_part_off && !ctx->opt_nbr_global && (n >> g->part_bits) >= 100) {      // (small partitions: the set-up per partition outweighs the local lookups)
+            if (g->index.skm_k && g->index.part_bits && g->d_part_off && ctx->opt_nbr_global <= 0 && (ctx->opt_nbr_global < 0 || (n >> g->part_bits) >= 100)) {      // (small partitions: the set-up per partition outweighs the local lookups; nbr_global = -1 takes them all the same)
                 const uint32_t np = 1u << g->part_bits;
                 const unsigned grid = (unsigned)std::min<uint64_t>((np + NB_WAVES - 1) / NB_WAVES, (uint64_t)ctx->n_cu * 64);
                 const unsigned grid2 = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * 16);      // partitions of 353 .. 1408 keys: a workgroup each
