@@ -519,7 +519,7 @@ int mf_comps_materialize(mf_comps *C) {
 }
 
 int mf_cc_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_counts, const uint64_t *d_keys, int b1, int b2,
-                const std::function<int(uint32_t *)> &adjacency, mf_comps **out) {
+                const std::function<int(uint32_t *)> &adjacency, mf_comps **out, std::vector<mf_cc_level> *trace) {
     hipStream_t st = ctx->stream;
     if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
     if (b1 < 0) b1 = 0;
@@ -578,7 +578,9 @@ int mf_cc_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_counts, const 
                 if (span) k_cc_classify<<<cgrid(span), 256, 0, st>>>(alive.p, root.p, csize.p, cweight.p, span, (uint32_t)b1, (uint32_t)b2, keptslot.p, K, counters.p, L);
             }
             unsigned int cnt[4];
+            unsigned long long ecnt[2] = {0, 0};
             MF_HIP(hipMemcpyAsync(cnt, counters.p, 16, hipMemcpyDeviceToHost, st));
+            if (trace && !sparse) MF_HIP(hipMemcpyAsync(ecnt, ecount.p, 16, hipMemcpyDeviceToHost, st));
             MF_HIP(hipStreamSynchronize(st));
             const uint32_t nkept = cnt[0], nkm = cnt[1], nbig = cnt[2];
             auto lv = std::make_unique<level_buf>();
@@ -619,6 +621,13 @@ int mf_cc_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_counts, const 
             if (ctx->opt_verbose)
                 fprintf(stderr, "[mf] components: thr=%d (%s, %llu vertices) kept=%u (%u k-mers) big=%u, %u vertices go on to the next level\n", thr, sparse ? "sparse" : "dense",
                         (unsigned long long)(sparse ? m : n), nkept, nkm, nbig, na);
+            if (trace) {
+                mf_cc_level tl;
+                tl.thr = thr; tl.sparse = sparse ? 1 : 0; tl.visited = sparse ? m : n; tl.ecount0 = ecnt[0]; tl.ecount1 = ecnt[1];
+                tl.nkept = nkept; tl.nkm = nkm; tl.nbig = nbig; tl.na = na;
+                tl.want_list = NL ? 1 : 0; tl.list_stands = nbig && NL && (sparse || (uint64_t)na <= lcap) ? 1 : 0;
+                trace->push_back(tl);
+            }
             if (!nbig) break;
             if (thr > MF_MAX_COUNT) return mf_set_error("components: threshold loop did not terminate");
             if (sparse) { cur ^= 1; m = na; }
@@ -739,6 +748,52 @@ extern "C" int mf_debug_neighbours(mf_ctx *ctx, mf_table *t, int path, uint64_t 
         MF_HIP(hipMemcpyAsync(keys_out, t->d_keys, n * 8, hipMemcpyDeviceToHost, st));
         MF_HIP(hipStreamSynchronize(st));                  // (nbr is released below)
     } else MF_HIP(hipStreamSynchronize(st));
+    return MF_OK;
+}
+
+// For the tests (not in include/metafast_hip.h): C2 .. C5 alone, on an adjacency the caller made up.  nbr[8 n]: vertex ids or 0xFFFFFFFF, in
+// any order, an id more than once and the vertex's own id allowed; vals[n]: 1 .. MF_MAX_COUNT; keys[n]: the vertices' k-mers (all different,
+// below 2^62; the components come out with k = 31) or NULL: the id stands for the k-mer, as the 128-bit front end has it (k = 16).  THE
+// ADJACENCY MUST BE SYMMETRIC -- u among the eight of v exactly when v is among the eight of u: the kernels look at every edge from its larger
+// end only, and nothing here checks it; it is the caller's duty.  trace[trace_cap][MF_CC_TRACE_FIELDS] (may be NULL): one row per threshold
+// level, the fields of mf_cc_level in their order; *n_levels: the levels that ran (rows beyond trace_cap are not written).
+#define MF_CC_TRACE_FIELDS 11
+extern "C" int mf_debug_components(mf_ctx *ctx, uint64_t n, const uint32_t *nbr, const uint16_t *vals, const uint64_t *keys, int b1, int b2, mf_comps **out,
+                                   uint64_t *trace, uint64_t trace_cap, int *n_levels) {
+    if (!ctx || !out || (n && (!nbr || !vals))) return mf_set_error("mf_debug_components: NULL argument");
+    *out = nullptr;
+    if (n_levels) *n_levels = 0;
+    if (n >= 0xFFFFFFFFull) return mf_set_error("mf_debug_components: %llu vertices (fewer than 2^32 - 1 are supported)", (unsigned long long)n);
+    if (trace_cap && !trace) return mf_set_error("mf_debug_components: NULL trace with room for %llu levels", (unsigned long long)trace_cap);
+    for (uint64_t i = 0; i < n * 8; i++)
+        if (nbr[i] != CC_NONE && nbr[i] >= n) return mf_set_error("mf_debug_components: neighbour %llu of vertex %llu is %u (not a vertex id below %llu, not 0xFFFFFFFF)",
+                                                                  (unsigned long long)(i & 7), (unsigned long long)(i >> 3), nbr[i], (unsigned long long)n);
+    for (uint64_t v = 0; v < n; v++) {
+        if (vals[v] < 1 || vals[v] > MF_MAX_COUNT) return mf_set_error("mf_debug_components: value %u of vertex %llu (1 .. %d)", (unsigned)vals[v], (unsigned long long)v, MF_MAX_COUNT);
+        if (keys && keys[v] >> 62) return mf_set_error("mf_debug_components: key of vertex %llu does not fit 62 bits", (unsigned long long)v);
+    }
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    mf_buf<uint32_t> d_nbr; mf_buf<uint16_t> d_vals; mf_buf<uint64_t> d_keys;
+    if (n) {
+        MF_TRY(d_nbr.alloc(ctx, n * 8)); MF_TRY(d_vals.alloc(ctx, n));
+        MF_HIP(hipMemcpyAsync(d_nbr.p, nbr, n * 8 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(d_vals.p, vals, n * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        if (keys) { MF_TRY(d_keys.alloc(ctx, n)); MF_HIP(hipMemcpyAsync(d_keys.p, keys, n * 8, hipMemcpyHostToDevice, st)); }
+        MF_HIP(hipStreamSynchronize(st));                  // (the host arrays are the caller's, pageable)
+    }
+    std::vector<mf_cc_level> tr;
+    MF_TRY(mf_cc_build(ctx, n, keys ? 31 : 16, d_vals.p, keys ? d_keys.p : nullptr, b1, b2, [&](uint32_t *dst) -> int {
+        MF_HIP(hipMemcpyAsync(dst, d_nbr.p, n * 8 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        return MF_OK;
+    }, out, &tr));
+    if (n_levels) *n_levels = (int)tr.size();
+    for (size_t i = 0; i < tr.size() && i < trace_cap; i++) {
+        const mf_cc_level &l = tr[i];
+        const uint64_t row[MF_CC_TRACE_FIELDS] = {(uint64_t)l.thr, (uint64_t)l.sparse, l.visited, l.ecount0, l.ecount1, l.nkept, l.nkm, l.nbig, l.na,
+                                                  (uint64_t)l.want_list, (uint64_t)l.list_stands};
+        memcpy(trace + i * MF_CC_TRACE_FIELDS, row, sizeof row);
+    }
     return MF_OK;
 }
 
