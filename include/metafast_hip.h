@@ -506,6 +506,43 @@ int mf_kmers_multiple_filters(mf_ctx *ctx, const char *const *in_files, int n_in
                               const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
                               const char *const *out_kmers, const char *const *out_stats, uint64_t *found_kept);
 
+/* ---- colored metagenomic features (pipeline 4 of the reference's Pipelines.md; mf_stats.hip, mf_cc.hip) ---------------------------
+ * mf_ctable: k-mer -> 64-bit value (BigLong2LongHashMap), ascending keys, resident in HBM.  The values of kmers-color are three 20-bit
+ * fields, class c in bits 20c .. 20c + 19. */
+typedef struct mf_ctable mf_ctable;
+/* host pairs in any order; the values of a key that comes more than once are added, saturating at 2^63 - 1; a value with the sign bit
+ * set and a key that does not fit 2k bits are errors */
+int  mf_ctable_from_host(mf_ctx *ctx, const uint64_t *keys, const uint64_t *values, uint64_t n, int k, mf_ctable **out);
+/* IOUtils.loadLongKmers (src/io/IOUtils.java:260-281): files of 16-byte big-endian (k-mer, value) records; a record is kept iff its
+ * value is > min_value (one with the sign bit set never is); the kept values of a key are added, saturating at 2^63 - 1 */
+int  mf_ctable_load(mf_ctx *ctx, const char *const *files, int nfiles, int64_t min_value, int k, mf_ctable **out);
+int  mf_ctable_stats(const mf_ctable *t, uint64_t *n, int *k);
+/* keys[n], values[n] in ascending key order; cap = 0: *n only */
+int  mf_ctable_export(const mf_ctable *t, uint64_t *keys, uint64_t *values, uint64_t cap, uint64_t *n);
+/* IOUtils.printKmers of a long map at threshold 0 (src/tools/ColorKmersMain.java:126-135): the 16-byte records in ascending key order and
+ * the .stat.txt over the distinct values (may be NULL); *n_written may be NULL */
+int  mf_ctable_write(const mf_ctable *t, const char *kmers_bin, const char *stat_txt, uint64_t *n_written);
+void mf_ctable_destroy(mf_ctable *t);
+/* ColorKmersMain.runImpl (src/tools/ColorKmersMain.java:89-136, src/algo/ColoredKmerOperations.java): every sample whose count of x is
+ * > max_bad adds 1 (count_values != 0: its count) to the field of its class in x's packed value, each add saturating at 2^20 - 1.
+ * classes[n] in {0, 1, 2}; at most 1024 samples; keys below 2^62. */
+int  mf_kmers_color_tables(mf_ctx *ctx, mf_table *const *t, const int *classes, int n, int max_bad, int count_values, mf_ctable **out);
+/* File form: each .kmers.bin loaded like IOUtils.loadKmers([file], max_bad) -> kmers_bin + stat_txt (may be NULL) */
+int  mf_kmers_color(mf_ctx *ctx, const char *const *files, const int *classes, int n, int max_bad, int count_values, int k,
+                    const char *kmers_bin, const char *stat_txt, uint64_t *n_kmers);
+/* ColoredComponentsBuilder (src/algo/ColoredComponentsBuilder.java:85-124, 250-280), default and --separate modes: colour of a value =
+ * the first c in 0, 1, 2 with (double)f_c / (f_0 + f_1 + f_2) >= perc, else neutral (ColoredKmerOperations.getColor).  separate != 0:
+ * for each colour the connected components (8 neighbours, src/algo/KmerOperations.java:9-26) of the k-mers of that colour; else the
+ * components of (colour c or neutral) that hold a k-mer of colour c, neutral k-mers included.  out[n_groups]: one mf_comps per colour
+ * (size = weight = k-mers; ordered by size descending, then smallest k-mer; k-mers ascending inside), counts[n_groups] (may be NULL)
+ * their numbers.  A k-mer whose colour is >= n_groups is an error. */
+int  mf_colored_components_device(mf_ctx *ctx, const mf_ctable *t, int k, int n_groups, int separate, double perc, mf_comps **out,
+                                  uint64_t *counts);
+/* File form (ColoredComponentMain.runImpl, src/tools/ColoredComponentMain.java:83-119; the reference passes k as min_value) ->
+ * <out_dir>/components_color_<c>.bin for c < n_groups and stat_txt (may be NULL) */
+int  mf_colored_components(mf_ctx *ctx, const char *const *files, int nfiles, int k, int64_t min_value, int n_groups, int separate,
+                           double perc, const char *out_dir, const char *stat_txt, uint64_t *counts);
+
 /* ---- A13  Bray-Curtis ---------------------------------------------------------------- */
 /* replaces DistanceMatrixCalculatorMain.brayCurtisDistance (src/tools/DistanceMatrixCalculatorMain.java:
  * 140-152): d = sum|a-b| / sum(|a|+|b|) on raw vectors; vecs is row-major [n_samples][n_comp]. */

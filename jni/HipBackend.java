@@ -94,4 +94,9 @@ public final class HipBackend {
     public static native long[] featuresAllgather(long comm, long[] rows, int nRows, int nComp);
 
     private HipBackend() {}
+    /** ColorKmersMain.runImpl: classes[i] = class (0, 1, 2) of kmersFiles[i]; returns the number of records written */
+    public static native long kmersColor(long ctx, String[] kmersFiles, int[] classes, int maxBad, boolean countValues, int k, String kmersBin, String statTxt);
+    /** ColoredComponentMain.runImpl, default and --separate modes (the reference passes k as minValue); returns the components per colour */
+    public static native long[] coloredComponents(long ctx, String[] kmersFiles, int k, long minValue, int nGroups, boolean separate, double perc, String outDir,
+                                                  String statTxt);
 }

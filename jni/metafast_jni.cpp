@@ -334,5 +334,29 @@ JNIEXPORT jlongArray JNICALL Java_io_HipBackend_featuresAllgather(JNIEnv *e, jcl
     if (r) e->SetLongArrayRegion(r, 0, (jsize)(n_all * (uint64_t)nComp), (const jlong *)all.data());
     return r;
 }
+// ColorKmersMain.runImpl (src/tools/ColorKmersMain.java:89-136): classes[i] = the class of kmersFiles[i] -> records written
+JNIEXPORT jlong JNICALL Java_io_HipBackend_kmersColor(JNIEnv *e, jclass, jlong ctx, jobjectArray kmersFiles, jintArray classes, jint maxBad, jboolean countValues, jint k,
+                                                      jstring kmersBin, jstring statTxt) {
+    utf_array f(e, kmersFiles);
+    if (e->GetArrayLength(classes) != (jsize)f.p.size()) { bad_length(e, "kmersColor: one class per k-mers file"); return 0; }
+    std::vector<jint> cl(f.p.size() + 1);
+    e->GetIntArrayRegion(classes, 0, (jsize)f.p.size(), cl.data());
+    utf kb(e, kmersBin), st(e, statTxt);
+    uint64_t n = 0;
+    if (mf_kmers_color((mf_ctx *)(intptr_t)ctx, f.p.data(), (const int *)cl.data(), (int)f.p.size(), maxBad, countValues ? 1 : 0, k, kb.p, st.p, &n) < 0) { raise(e); return 0; }
+    return (jlong)n;
+}
+// ColoredComponentMain.runImpl (src/tools/ColoredComponentMain.java:83-119), default and --separate modes -> components per colour
+JNIEXPORT jlongArray JNICALL Java_io_HipBackend_coloredComponents(JNIEnv *e, jclass, jlong ctx, jobjectArray kmersFiles, jint k, jlong minValue, jint nGroups, jboolean separate,
+                                                                  jdouble perc, jstring outDir, jstring statTxt) {
+    if (nGroups < 1 || nGroups > 64) { bad_length(e, "coloredComponents: nGroups must be 1 .. 64"); return nullptr; }
+    utf_array f(e, kmersFiles);
+    utf od(e, outDir), st(e, statTxt);
+    std::vector<uint64_t> cnt((size_t)nGroups, 0);
+    if (mf_colored_components((mf_ctx *)(intptr_t)ctx, f.p.data(), (int)f.p.size(), k, (int64_t)minValue, nGroups, separate ? 1 : 0, perc, od.p, st.p, cnt.data()) < 0) { raise(e); return nullptr; }
+    jlongArray r = e->NewLongArray((jsize)nGroups);
+    if (r) e->SetLongArrayRegion(r, 0, (jsize)nGroups, (const jlong *)cnt.data());
+    return r;
+}
 }
 #endif

@@ -39,6 +39,9 @@ extern "C" int mf_unique_kmers_multi(mf_ctx *, const char *const *, int, const c
                                      uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_multiple_filters(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int,
                                          int, int, const char *const *, const char *const *, uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_color(mf_ctx *, const char *const *, const int *, int, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
+    __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -155,6 +158,8 @@ static const OptDef OPTS[] = {
     {"a-kmers", "A", true, false}, {"b-kmers", "B", true, false}, {"p-value-chi2", "pchi2", false, false}, {"p-value-mw", "pmw", false, false},
     {"min-samples", "", false, false}, {"max-samples", "", false, false}, {"cd-filter-kmers", "cd", true, false}, {"uc-filter-kmers", "uc", true, false},
     {"nonibd-filter-kmers", "nonibd", true, false},
+    {"class", "", false, false}, {"val", "val", false, true}, {"n_groups", "group", false, false}, {"separate", "", false, true},
+    {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false},
 };
 // `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
@@ -166,7 +171,7 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
         if (s == "i") {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
             if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters") return "k-mers";
+                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored") return "k-mers";
             if (tool == "component-cutter") return "sequences";
             return "reads";
         }
@@ -175,6 +180,7 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
                                  ? "maximal-bad-frequence" : "maximal-bad-frequency";
         if (s == "l") return (tool == "seq-builder" || tool == "seq-builder-many") ? "sequence-len" : "min-seq-len";
         if (s == "o") return (tool == "view" || tool == "bin2fasta") ? "output-file" : "output-dir";
+        if (s == "kf" && tool == "kmers-color") return "k-mers";            // ColorKmersMain.java:39-43 (view, bin2fasta: kmers-file)
         if (s == "cf") return "components-file";                           // ViewMain.java:45, BinaryToFasta.java:47
         for (auto &o : OPTS) if (o.sht[0] && s == o.sht) return o.lng;
         return "";
@@ -866,6 +872,8 @@ static const char *TOOLS_TEXT =
     "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
     "unique-kmers-multi\tOutput k-mers present in one dataset in fixed number of samples and missing in other\n"
     "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
+    "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
+    "component-colored\tExtract graph components from tangled graph based on k-mers coloring\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -932,6 +940,12 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
              PV::files("uc-filter-kmers", a.list("uc-filter-kmers")), PV::files("nonibd-filter-kmers", a.list("nonibd-filter-kmers")),
              PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
              PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
+    } else if (tool == "kmers-color") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), opt_f("class"), PV("maximal-bad-frequency", a.get("maximal-bad-frequency", "1")), flag("val"),
+             PV::file("output-dir", a.get("output-dir", wd + "/colored-kmers"))};
+    } else if (tool == "component-colored") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("n_groups", a.get("n_groups", "3")), flag("separate"), flag("linear"),
+             PV("n_comps", a.get("n_comps", "-1")), PV("perc", a.get("perc", "0.9")), PV::file("output-dir", a.get("output-dir", wd + "/colored-components"))};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -956,7 +970,7 @@ int main(int argc, char **argv) {
     }
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
-                                  "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters"};
+                                  "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1032,6 +1046,8 @@ int main(int argc, char **argv) {
     else if (tool == "kmers-multiple-filters") {
         need("k", "k"); need("k-mers", "i"); need("cd-filter-kmers", "cd"); need("uc-filter-kmers", "uc"); need("nonibd-filter-kmers", "nonibd");
     }
+    else if (tool == "kmers-color") { need("k", "k"); need("k-mers", "kf"); if (!a.has("class")) die("Mandatory argument --class not set"); }
+    else if (tool == "component-colored") { need("k", "k"); need("k-mers", "i"); }
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1206,6 +1222,84 @@ int main(int argc, char **argv) {
             logmsg("INFO", "%s k-mers found, %s (%s%%) of them survived after filtering", group_digits(fk[2 * j]).c_str(), group_digits(fk[2 * j + 1]).c_str(), pct);
             logmsg("INFO", "Filtered k-mers printed to %s", ok[j].c_str());
         }
+    } else if (tool == "kmers-color") {
+        // ColorKmersMain.java:89-136: per k-mer and class 0 / 1 / 2 the number of samples that hold it (-val: their summed coverage)
+        check_k(k);
+        const int b = a.geti("maximal-bad-frequency", 1);
+        const bool val = a.get("val", "false") == "true";
+        const string out_dir = a.get("output-dir", wd + "/colored-kmers"), cls = a.get("class");
+        const vector<string> files = a.list("k-mers");
+        logmsg("INFO", "Loading class file...");
+        // readFileToColor :70-82: tab-separated lines, name (the file name without .kmers.bin) and class
+        std::map<string, int> color;
+        {
+            FILE *f = fopen(cls.c_str(), "r");
+            if (!f) die("Cannot read file: %s", cls.c_str());
+            char line[8192]; int ln = 0;
+            while (fgets(line, sizeof line, f)) {
+                ln++;
+                string l(line);
+                while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+                const size_t t1 = l.find('\t');
+                if (t1 == string::npos) { fclose(f); die("class file %s, line %d: no tab-separated class after '%s'", cls.c_str(), ln, l.c_str()); }
+                const size_t t2 = l.find('\t', t1 + 1);
+                const string name = l.substr(0, t1), cv = l.substr(t1 + 1, t2 == string::npos ? string::npos : t2 - t1 - 1);
+                char *end; const long c = strtol(cv.c_str(), &end, 10);
+                if (cv.empty() || *end) { fclose(f); die("class file %s, line %d: can't parse class '%s' of sample '%s'", cls.c_str(), ln, cv.c_str(), name.c_str()); }
+                if (c < 0 || c > 2) { fclose(f); die("class file %s, line %d: sample '%s' has class %ld (the classes are 0, 1 and 2)", cls.c_str(), ln, name.c_str(), c); }
+                color[name] = (int)c;
+            }
+            fclose(f);
+        }
+        vector<int> classes;
+        for (auto &fn : files) {
+            const string name = remove_ext(basename_of(fn), {".kmers.bin"});
+            auto it = color.find(name);
+            if (it == color.end()) die("class file %s has no line for sample '%s' (%s)", cls.c_str(), name.c_str(), fn.c_str());
+            classes.push_back(it->second);
+        }
+        if (files.size() > 1024) die("kmers-color: %zu k-mers files, at most 1024 (a field of the packed value holds 20 bits)", files.size());
+        mkdirs(out_dir);
+        if (!mf_kmers_color) die("kmers-color: this build of the library has no mf_kmers_color");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("INFO", "Loading kmers files...");
+        auto fp = cptrs(files);
+        const string out = out_dir + "/colored_kmers.kmers.bin", st = out_dir + "/colored_kmers.stat.txt";
+        uint64_t c = 0;
+        check(mf_kmers_color(ctx, fp.data(), classes.data(), (int)fp.size(), b, val ? 1 : 0, k, out.c_str(), st.c_str(), &c));
+        logmsg("INFO", "%s colored k-mers printed to %s", group_digits(c).c_str(), out.c_str());
+        outs = {PV::file("resulting-kmers-file", out)};
+    } else if (tool == "component-colored") {
+        // ColoredComponentMain.java:83-119, default and --separate modes of ColoredComponentsBuilder
+        check_k(k);
+        const int groups = a.geti("n_groups", 3), ncomps = a.geti("n_comps", -1);
+        const bool separate = a.get("separate", "false") == "true";
+        const double perc = a.getd("perc", 0.9);
+        if (a.get("linear", "false") == "true")
+            die("component-colored: --linear is not supported: its result depends on the iteration order of the reference's hash map");
+        if (ncomps != -1)
+            die("component-colored: --n_comps %d is not supported (only -1, all components): which components are selected depends on the iteration order of the reference's hash map", ncomps);
+        if (groups < 1) die("component-colored: --n_groups %d: at least 1", groups);
+        const string out_dir = a.get("output-dir", wd + "/colored-components"), stat = wd + "/components-stat.txt";
+        const vector<string> files = a.list("k-mers");
+        mkdirs(out_dir);
+        if (!mf_colored_components) die("component-colored: this build of the library has no mf_colored_components");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("DEBUG", "Loading colored k-mers...");
+        logmsg("INFO", "Searching for colored components...");
+        auto fp = cptrs(files);
+        vector<uint64_t> cnt((size_t)groups, 0);
+        // (IOUtils.loadLongKmers(files, k, ...): the reference passes k where the loader takes its value threshold)
+        check(mf_colored_components(ctx, fp.data(), (int)fp.size(), k, (int64_t)k, groups, separate ? 1 : 0, perc, out_dir.c_str(), stat.c_str(), cnt.data()));
+        uint64_t total = 0;
+        vector<string> written;
+        for (int c = 0; c < groups; c++) {
+            total += cnt[(size_t)c];
+            logmsg("INFO", "%s components were found for class %d", group_digits(cnt[(size_t)c]).c_str(), c);
+            written.push_back(out_dir + "/components_color_" + std::to_string(c) + ".bin");
+        }
+        logmsg("INFO", "Total %s components were found", group_digits(total).c_str());
+        outs = {PV::files("components-files", written)};
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

@@ -700,6 +700,13 @@ static void cc_adjacency_launch(mf_ctx *ctx, const mf_table *t, bool local, uint
         k_cc_adjacency<<<cgrid(n), 256, 0, st>>>(mf_view(t->index), t->d_keys, n, k, nbr);
 }
 
+// ... by the path the table and option nbr_global ask for
+static void cc_adjacency_auto(mf_ctx *ctx, const mf_table *t, uint32_t *nbr) {
+    // (small partitions: the set-up per partition outweighs the local lookups; nbr_global = -1 takes them all the same, 1 never)
+    const bool local = cc_adjacency_has_parts(t) && ctx->opt_nbr_global <= 0 && (ctx->opt_nbr_global < 0 || (t->n >> t->part_bits) >= 100);
+    cc_adjacency_launch(ctx, t, local, nbr);
+}
+
 extern "C" int mf_cut_components_device(mf_ctx *ctx, mf_table *t, int b1, int b2, mf_comps **out) {
     mf_range rng_("mf:components");
     if (!ctx || !t || !out) return mf_set_error("mf_cut_components_device: NULL argument");
@@ -709,12 +716,7 @@ extern "C" int mf_cut_components_device(mf_ctx *ctx, mf_table *t, int b1, int b2
     const int k = t->k;
     if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
     if (n) MF_TRY(mf_table_ensure_index(t));
-    return mf_cc_build(ctx, n, k, t->d_counts, t->d_keys, b1, b2, [&](uint32_t *nbr) -> int {
-        // (small partitions: the set-up per partition outweighs the local lookups; nbr_global = -1 takes them all the same, 1 never)
-        const bool local = cc_adjacency_has_parts(t) && ctx->opt_nbr_global <= 0 && (ctx->opt_nbr_global < 0 || (n >> t->part_bits) >= 100);
-        cc_adjacency_launch(ctx, t, local, nbr);
-        return MF_OK;
-    }, out);
+    return mf_cc_build(ctx, n, k, t->d_counts, t->d_keys, b1, b2, [&](uint32_t *nbr) -> int { cc_adjacency_auto(ctx, t, nbr); return MF_OK; }, out);
 }
 
 // For the tests (not in include/metafast_hip.h): the adjacency alone, by one chosen path, with the table's layout.  path 0: k_cc_adjacency; path 1: the
@@ -1736,4 +1738,217 @@ extern "C" int mf_dcc_finish(mf_dcc *D, const void *d_keys, const void *d_roots,
     }
     *out = C.release();
     return MF_OK;
+}
+
+// ===========================================================================================================================
+// component-colored (src/tools/ColoredComponentMain.java:83-119, src/algo/ColoredComponentsBuilder.java:85-124, 250-280; DESIGN.md
+// section 7c): connected components of the de Bruijn graph restricted by colour.
+//   classify   packed value -> colour code (1 + colour, 4 = neutral: ColoredKmerOperations.getColor), on the ascending table
+//   graph      the k-mers become an mf_table whose counts are the codes (they travel with the keys into the minimizer partitions), so
+//              the adjacency is the launch of the component cutter, by either lookup path
+//   per colour alive = colour c (--separate) or colour c and neutral (default); the hook, compress and flatten kernels of the cutter
+//              on that mask; default mode: a root is flagged when a k-mer of colour c points at it and the components without a flag
+//              die; every alive root is a component: classify and member extraction as in the cutter with the window [1, 2^32 - 1]
+// size = weight = number of k-mers.  Order: size descending, then smallest k-mer ascending.
+// ===========================================================================================================================
+int mf_table_from_device_pairs(mf_ctx *ctx, const uint64_t *d_keys, const uint16_t *d_vals, uint64_t n, int k, mf_table **out);
+#define CC_COLOR_NEUTRAL 4u
+
+// first: the smallest position whose colour is not below n_groups (~0: none)
+__global__ void k_color_classify(const uint64_t *__restrict__ vals, uint64_t n, double perc, uint32_t n_groups, uint16_t *__restrict__ code,
+                                 unsigned long long *__restrict__ first) {
+#pragma clang fp contract(off)
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t v = vals[i];
+    const long long f0 = (long long)(v & 0xFFFFFull), f1 = (long long)((v >> 20) & 0xFFFFFull), f2 = (long long)((v >> 40) & 0xFFFFFull);
+    const double sum = (double)(f0 + f1 + f2);
+    uint32_t c = CC_COLOR_NEUTRAL;
+    if ((double)f0 / sum >= perc) c = 1;
+    else if ((double)f1 / sum >= perc) c = 2;
+    else if ((double)f2 / sum >= perc) c = 3;
+    code[i] = (uint16_t)c;
+    if (c != CC_COLOR_NEUTRAL && c > n_groups) atomicMin(first, (unsigned long long)i);
+}
+__global__ void k_color_alive(const uint16_t *__restrict__ code, uint64_t n, uint32_t want, int with_neutral, uint8_t *__restrict__ alive) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const uint32_t c = code[v];
+    alive[v] = (c == want || (with_neutral && c == CC_COLOR_NEUTRAL)) ? 1 : 0;
+}
+// a root holds a k-mer of the colour (every thread stores the same byte)
+__global__ void k_color_mark(const uint16_t *__restrict__ code, const uint8_t *__restrict__ alive, const uint32_t *__restrict__ root, uint64_t n, uint32_t want,
+                             uint8_t *__restrict__ has) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n && alive[v] && code[v] == want) has[root[v]] = 1;
+}
+__global__ void k_color_prune(uint8_t *__restrict__ alive, const uint32_t *__restrict__ root, uint64_t n, const uint8_t *__restrict__ has) {
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n && alive[v] && !has[root[v]]) alive[v] = 0;
+}
+
+static int comps_empty(mf_ctx *ctx, int k, mf_comps **out) {
+    std::unique_ptr<mf_comps, void (*)(mf_comps *)> C(new mf_comps(), [](mf_comps *c) { mf_comps_destroy(c); });
+    C->ctx = ctx; C->k = k;
+    void *p = nullptr;
+    MF_TRY(mf_alloc(ctx, 8, &p)); C->d_kmers = (uint64_t *)p; C->kmers_bytes = 8;
+    MF_TRY(mf_alloc(ctx, 4, &p)); C->d_comp = (uint32_t *)p; C->comp_bytes = 4;
+    *out = C.release();
+    return MF_OK;
+}
+
+// t: the graph's table, counts = colour codes.  out[n_groups]
+static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate, mf_comps **out) {
+    hipStream_t st = ctx->stream;
+    const uint64_t n = t->n;
+    const int k = t->k;
+    if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
+    if (!n) { for (int c = 0; c < n_groups; c++) MF_TRY(comps_empty(ctx, k, &out[c])); return MF_OK; }
+    MF_TRY(mf_table_ensure_index(t));
+    mf_buf<uint32_t> nbr, parent, root, csize, keptslot, slot_fill, k_root, k_size; mf_buf<unsigned long long> cweight, k_weight, k_minkey;
+    mf_buf<uint8_t> alive, has; mf_buf<unsigned int> counters; mf_buf<uint64_t> slot_off, tot;
+    const uint64_t max_kept = n + 1;
+    MF_TRY(nbr.alloc(ctx, n * 8)); MF_TRY(parent.alloc(ctx, n)); MF_TRY(root.alloc(ctx, n)); MF_TRY(csize.alloc(ctx, n));
+    MF_TRY(keptslot.alloc(ctx, n)); MF_TRY(cweight.alloc(ctx, n)); MF_TRY(alive.alloc(ctx, n)); MF_TRY(has.alloc(ctx, n)); MF_TRY(counters.alloc(ctx, 4));
+    MF_TRY(k_root.alloc(ctx, max_kept)); MF_TRY(k_size.alloc(ctx, max_kept)); MF_TRY(k_weight.alloc(ctx, max_kept));
+    MF_TRY(k_minkey.alloc(ctx, max_kept)); MF_TRY(slot_off.alloc(ctx, max_kept + 1)); MF_TRY(slot_fill.alloc(ctx, max_kept));
+    MF_TRY(tot.alloc(ctx, 1));
+    mf_buf<uint2> edges; mf_buf<unsigned long long> ecount;
+    const uint64_t ecap = n / 2 + 1024;
+    MF_TRY(edges.alloc(ctx, ecap)); MF_TRY(ecount.alloc(ctx, 2));
+    cc_kept_arrays K; K.root = k_root.p; K.size = k_size.p; K.weight = k_weight.p; K.minkey = k_minkey.p;
+    {
+        mf_ktimer tm(ctx, "k_cc_adjacency");
+        cc_adjacency_auto(ctx, t, nbr.p);
+    }
+    for (int c = 0; c < n_groups; c++) {
+        if (c > 2) { MF_TRY(comps_empty(ctx, k, &out[c])); continue; }          // (a value has three fields)
+        const uint32_t want = (uint32_t)c + 1;
+        MF_HIP(hipMemsetAsync(counters.p, 0, 16, st));
+        MF_HIP(hipMemsetAsync(ecount.p, 0, 16, st));
+        {
+            mf_ktimer tm(ctx, "k_color_hook");
+            k_color_alive<<<cgrid(n), 256, 0, st>>>(t->d_counts, n, want, separate ? 0 : 1, alive.p);
+            k_cc_hook_tile<<<cgrid(n, CC_TILE), 256, 0, st>>>(nbr.p, alive.p, parent.p, csize.p, cweight.p, n, edges.p, ecount.p, ecap);
+            k_cc_hook_edges<<<cgrid(ecap), 256, 0, st>>>(edges.p, ecount.p, ecap, alive.p, parent.p);
+            k_cc_hook<<<cgrid(n), 256, 0, st>>>(nbr.p, alive.p, parent.p, n, nullptr, ecount.p);      // (only if the list overflowed)
+        }
+        {
+            mf_ktimer tm(ctx, "k_color_stats");
+            k_cc_compress<<<cgrid(n), 256, 0, st>>>(alive.p, parent.p, n);
+            k_cc_flatten_stats<<<cgrid(n, CC_TILE), 256, 0, st>>>(alive.p, parent.p, root.p, t->d_counts, csize.p, cweight.p, n);
+            if (!separate) {
+                MF_HIP(hipMemsetAsync(has.p, 0, n, st));
+                k_color_mark<<<cgrid(n), 256, 0, st>>>(t->d_counts, alive.p, root.p, n, want, has.p);
+                k_color_prune<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, n, has.p);
+            }
+            k_cc_classify<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, csize.p, cweight.p, n, 1u, 0xFFFFFFFFu, keptslot.p, K, counters.p, nullptr);
+        }
+        unsigned int cnt[4];
+        MF_HIP(hipMemcpyAsync(cnt, counters.p, 16, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipStreamSynchronize(st));
+        const uint32_t nkept = cnt[0], nkm = cnt[1];
+        std::unique_ptr<mf_comps, void (*)(mf_comps *)> C(new mf_comps(), [](mf_comps *p) { mf_comps_destroy(p); });
+        C->ctx = ctx; C->k = k; C->n = nkept; C->n_kmers = nkm;
+        void *p = nullptr;
+        MF_TRY(mf_alloc(ctx, (nkm ? (size_t)nkm : 1) * 8, &p)); C->d_kmers = (uint64_t *)p; C->kmers_bytes = (nkm ? (size_t)nkm : 1) * 8;
+        MF_TRY(mf_alloc(ctx, (nkm ? (size_t)nkm : 1) * 4, &p)); C->d_comp = (uint32_t *)p; C->comp_bytes = (nkm ? (size_t)nkm : 1) * 4;
+        if (nkept) {
+            MF_TRY(mf_scan<1>(ctx, k_size.p, slot_off.p, (uint64_t)nkept, tot.p));
+            MF_HIP(hipMemsetAsync(slot_fill.p, 0, (size_t)nkept * 4, st));
+            {
+                mf_ktimer tm(ctx, "k_color_members");
+                k_cc_members<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, csize.p, t->d_counts, t->d_keys, n, 1u, 0xFFFFFFFFu, 0u, keptslot.p, slot_off.p, slot_fill.p, 0u,
+                                                       k_minkey.p, C->d_kmers, C->d_comp, &counters.p[3], nullptr, nullptr, 0u);
+            }
+            std::vector<uint32_t> hs(nkept); std::vector<unsigned long long> hm(nkept);
+            MF_HIP(hipMemcpyAsync(hs.data(), k_size.p, (size_t)nkept * 4, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipMemcpyAsync(hm.data(), k_minkey.p, (size_t)nkept * 8, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipStreamSynchronize(st));
+            std::vector<uint32_t> order(nkept), rank(nkept);
+            std::iota(order.begin(), order.end(), 0u);
+            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hs[a] != hs[b] ? hs[a] > hs[b] : hm[a] < hm[b]; });
+            for (uint32_t i = 0; i < nkept; i++) {
+                rank[order[i]] = i;
+                C->sizes.push_back(hs[order[i]]); C->weights.push_back((int64_t)hs[order[i]]); C->thr.push_back(0);
+            }
+            mf_buf<uint32_t> d_rank; MF_TRY(d_rank.alloc(ctx, nkept));
+            MF_HIP(hipMemcpyAsync(d_rank.p, rank.data(), (size_t)nkept * 4, hipMemcpyHostToDevice, st));
+            k_cc_remap<<<cgrid(nkm), 256, 0, st>>>(C->d_comp, nkm, d_rank.p);
+            MF_HIP(hipStreamSynchronize(st));
+        }
+        if (ctx->opt_verbose) fprintf(stderr, "[mf] coloured components: colour %d: %u components, %u k-mers\n", c, nkept, nkm);
+        out[c] = C.release();
+    }
+    return MF_OK;
+}
+
+extern "C" int mf_colored_components_device(mf_ctx *ctx, const mf_ctable *ct, int k, int n_groups, int separate, double perc, mf_comps **out, uint64_t *counts) {
+    mf_range rng_("mf:colored_components");
+    if (!ctx || !ct || !out) return mf_set_error("mf_colored_components_device: NULL argument");
+    if (ct->ctx != ctx) return mf_set_error("mf_colored_components_device: the table belongs to another context");
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    if (n_groups < 1 || n_groups > 64) return mf_set_error("component-colored: n_groups = %d (1 .. 64)", n_groups);
+    for (int c = 0; c < n_groups; c++) out[c] = nullptr;
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = ct->n;
+    if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
+    mf_table *t = nullptr;
+    struct tguard { mf_table *&t; ~tguard() { if (t) mf_table_destroy(t); } } tg{t};
+    {
+        mf_buf<uint16_t> code; MF_TRY(code.alloc(ctx, n));
+        mf_buf<unsigned long long> first; MF_TRY(first.alloc(ctx, 1));
+        MF_HIP(hipMemsetAsync(first.p, 0xFF, 8, st));
+        unsigned long long bad = ~0ull, last = 0;
+        if (n) {
+            mf_ktimer tm(ctx, "k_color_classify");
+            k_color_classify<<<cgrid(n), 256, 0, st>>>(ct->d_vals, n, perc, (uint32_t)n_groups, code.p, first.p);
+            MF_HIP(hipMemcpyAsync(&last, ct->d_keys + (n - 1), 8, hipMemcpyDeviceToHost, st));
+        }
+        MF_HIP(hipMemcpyAsync(&bad, first.p, 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipStreamSynchronize(st));
+        if (n && (last >> (2 * k))) return mf_set_error("component-colored: k-mer %llu does not fit k = %d", last, k);
+        if (bad != ~0ull) {
+            unsigned long long key = 0; uint16_t cd = 0;
+            MF_HIP(hipMemcpyAsync(&key, ct->d_keys + bad, 8, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipMemcpyAsync(&cd, code.p + bad, 2, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipStreamSynchronize(st));
+            return mf_set_error("component-colored: k-mer %llu has colour %d, but n_groups = %d (colours 0 .. %d)", key, (int)cd - 1, n_groups, n_groups - 1);
+        }
+        MF_TRY(mf_table_from_device_pairs(ctx, ct->d_keys, code.p, n, k, &t));
+        MF_HIP(hipStreamSynchronize(st));
+    }
+    const int rc = cc_colored_build(ctx, t, n_groups, separate, out);
+    if (rc < 0) { for (int c = 0; c < n_groups; c++) { mf_comps_destroy(out[c]); out[c] = nullptr; } return rc; }
+    if (counts) for (int c = 0; c < n_groups; c++) counts[c] = out[c]->n;
+    return MF_OK;
+}
+
+extern "C" int mf_colored_components(mf_ctx *ctx, const char *const *files, int nfiles, int k, int64_t min_value, int n_groups, int separate, double perc,
+                                     const char *out_dir, const char *stat_txt, uint64_t *counts) {
+    mf_range rng_("mf:colored_components(files)");
+    if (!ctx || !out_dir || nfiles < 0 || (nfiles && !files)) return mf_set_error("mf_colored_components: NULL argument");
+    if (n_groups < 1 || n_groups > 64) return mf_set_error("component-colored: n_groups = %d (1 .. 64)", n_groups);
+    mf_ctable *ct = nullptr;
+    MF_TRY(mf_ctable_load(ctx, files, nfiles, min_value, k, &ct));
+    std::vector<mf_comps *> cs((size_t)n_groups, nullptr);
+    int rc = mf_colored_components_device(ctx, ct, k, n_groups, separate, perc, cs.data(), counts);
+    mf_ctable_destroy(ct);
+    for (int c = 0; c < n_groups && rc == MF_OK; c++)
+        rc = mf_comps_write(cs[(size_t)c], (std::string(out_dir) + "/components_color_" + std::to_string(c) + ".bin").c_str(), nullptr);
+    if (rc == MF_OK && stat_txt) {
+        FILE *f = fopen(stat_txt, "w");
+        if (!f) rc = mf_set_error("can't write '%s'", stat_txt);
+        else {
+            fprintf(f, "# component.no\tcomponent.size\tcomponent.weight\tcomponent.color\n");
+            unsigned long long no = 0;
+            for (int c = 0; c < n_groups; c++)
+                for (uint64_t i = 0; i < cs[(size_t)c]->n; i++)
+                    fprintf(f, "%llu\t%llu\t%lld\t%d\n", ++no, (unsigned long long)cs[(size_t)c]->sizes[i], (long long)cs[(size_t)c]->weights[i], c);
+            if (fclose(f) != 0) rc = mf_set_error("can't write '%s'", stat_txt);
+        }
+    }
+    for (mf_comps *c : cs) mf_comps_destroy(c);
+    return rc;
 }

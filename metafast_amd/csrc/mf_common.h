@@ -263,6 +263,17 @@ struct mf_comps {
     mf_index index; size_t index_bytes = 0;
 };
 
+// ascending k-mers with 64-bit values (BigLong2LongHashMap): the packed class counts of kmers-color, the input of component-colored
+struct mf_ctable {
+    mf_ctx *ctx = nullptr;
+    int k = 0;
+    uint64_t n = 0;
+    uint64_t *d_keys = nullptr, *d_vals = nullptr;   // [n], ascending keys
+    size_t keys_bytes = 0, vals_bytes = 0;
+};
+// takes the two device arrays over (ascending keys, all different)
+int mf_ctable_adopt(mf_ctx *ctx, int k, uint64_t n, uint64_t *d_keys, size_t kb, uint64_t *d_vals, size_t vb, mf_ctable **out);
+
 // ---- files this process has just written, kept as the objects they were written from (option file_cache, mf_io.hip): the next step of a
 // matrix-builder run asks for the file and gets the table / the components that are still in HBM
 struct mf_file_entry {

@@ -52,7 +52,10 @@ __global__ void k_stats_init(mf_uslot *__restrict__ slots, uint64_t cap, uint64_
 //                      never reaches the sample count; sum <= 32767 * 65535 < 2^31)
 //   MF_UNION_FIELD     the entry's value to the 16-bit field number `add` of the slot (kmers-multiple-filters: cd, uc, nonibd; each
 //                      field is written by one table, whose keys are distinct, so no add carries)
-enum { MF_UNION_PRESENCE = 0, MF_UNION_SUM = 1, MF_UNION_FIELD = 2 };
+//   MF_UNION_COLOR     kmers-color: 1 (or, bit 2 of `add` set, the entry's value) to the 20-bit field number `add & 3` of the 64-bit payload,
+//                      saturating at 2^20 - 1 (ColoredKmerOperations.addValue) by a compare-and-swap on the payload word
+enum { MF_UNION_PRESENCE = 0, MF_UNION_SUM = 1, MF_UNION_FIELD = 2, MF_UNION_COLOR = 3 };
+static constexpr uint64_t MF_COLOR_FIELD_MAX = (1ull << 20) - 1;
 // flags: bit 0 = a key >= 2^62, bit 1 = the table is full (never with the sizes the host picks; an error, never a write out of bounds)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_stats_union(mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
@@ -74,6 +77,21 @@ __global__ __launch_bounds__(256) void k_stats_union(mf_uslot *__restrict__ slot
                 if (old == MF_EMPTY) atomicAdd(n_union, 1ull);
                 if (MODE == MF_UNION_PRESENCE) atomicAdd(&slots[p].cnt, add);
                 else if (MODE == MF_UNION_SUM) { atomicAdd(&slots[p].cnt, 1u); atomicAdd(&slots[p].row, c); }
+                else if (MODE == MF_UNION_COLOR) {
+                    const uint32_t sh = 20u * (add & 3u);
+                    const uint64_t inc = (add & 4u) ? (uint64_t)c : 1ull;
+                    unsigned long long *w = reinterpret_cast<unsigned long long *>(&slots[p].cnt);
+                    unsigned long long cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    for (;;) {
+                        const uint64_t f = (cur >> sh) & MF_COLOR_FIELD_MAX;
+                        const uint64_t nf = f + inc < MF_COLOR_FIELD_MAX ? f + inc : MF_COLOR_FIELD_MAX;
+                        const unsigned long long nw = (cur & ~(MF_COLOR_FIELD_MAX << sh)) | (nf << sh);
+                        if (nw == cur) break;
+                        const unsigned long long old = atomicCAS(w, cur, nw);
+                        if (old == cur) break;
+                        cur = old;
+                    }
+                }
                 else if (add == 2u) atomicAdd(&slots[p].row, c);
                 else atomicAdd(&slots[p].cnt, c << (16u * add));
                 done = true;
@@ -390,6 +408,7 @@ static int union_slice(mf_ctx *ctx, const stats_get &get, int N, int b, uint32_t
             const uint32_t add = add_of(j);
             if (mode == MF_UNION_PRESENCE) k_stats_union<MF_UNION_PRESENCE><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
             else if (mode == MF_UNION_SUM) k_stats_union<MF_UNION_SUM><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
+            else if (mode == MF_UNION_COLOR) k_stats_union<MF_UNION_COLOR><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
             else k_stats_union<MF_UNION_FIELD><<<g, 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, add, S, s, nu.p, flags.p);
         }
         const hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -1000,12 +1019,12 @@ struct kmf_result { mf_table *kept = nullptr; std::vector<uint64_t> triples, cou
 using kmf_sink = std::function<int(int j, kmf_result &r)>;          // takes r.kept over (destroys it)
 
 // the packed triples of one (input, slice) -> added to hist
-static int kmf_histogram(mf_ctx *ctx, mf_buf<uint64_t> &tri, uint64_t m, std::map<uint64_t, uint64_t> &hist) {
+static int kmf_histogram(mf_ctx *ctx, mf_buf<uint64_t> &tri, uint64_t m, std::map<uint64_t, uint64_t> &hist, int bits = 48) {
     if (!m) return MF_OK;
     mf_buf<uint64_t> st; mf_buf<uint16_t> d0, d1;
     MF_TRY(st.alloc(ctx, m)); MF_TRY(d0.alloc(ctx, m)); MF_TRY(d1.alloc(ctx, m));
     MF_HIP(hipMemsetAsync(d0.p, 0, d0.bytes(), ctx->stream));
-    MF_TRY(mf_sort_pairs(ctx, tri.p, d0.p, m, 48, st.p, d1.p));
+    MF_TRY(mf_sort_pairs(ctx, tri.p, d0.p, m, bits, st.p, d1.p));
     d0.reset(); d1.reset();
     mf_buf<unsigned int> cur; MF_TRY(cur.alloc(ctx, 1));
     MF_HIP(hipMemsetAsync(cur.p, 0, 4, ctx->stream));
@@ -1187,4 +1206,262 @@ extern "C" int mf_kmers_multiple_filters(mf_ctx *ctx, const char *const *in_file
         return rc;
     };
     return kmf_join(ctx, gf, total, gi, n_inputs, max_bad, sink);
+}
+
+// ===========================================================================================================================
+// kmers-color (src/tools/ColorKmersMain.java:89-136, src/algo/ColoredKmerOperations.java) on the same union table (DESIGN.md
+// section 7c): the slot's 64-bit payload IS the packed value -- three 20-bit fields, class c in bits 20c .. 20c + 19 -- and a sample's
+// entry adds 1 (or its value, -val) to its class's field with the reference's saturation (MF_UNION_COLOR).  Read-out, one sort by
+// key, and the distinct-value histogram for the .stat.txt.  The result is an mf_ctable: ascending keys with 64-bit values.
+// ===========================================================================================================================
+#define MF_COLOR_MAX_N 1024
+
+// every union entry -> (key, packed value)   (uniform trip count: mf_wave_reserve)
+__global__ __launch_bounds__(256) void k_color_read(const mf_uslot *__restrict__ slots, uint64_t cap, uint64_t *__restrict__ okeys,
+                                                    uint64_t *__restrict__ ovals, unsigned int *__restrict__ cursor) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < cap; i0 += stride) {
+        const uint64_t i = i0 + threadIdx.x;
+        ulonglong2 raw; raw.x = MF_EMPTY; raw.y = 0;
+        if (i < cap) raw = *reinterpret_cast<const ulonglong2 *>(&slots[i]);
+        const bool here = raw.x != MF_EMPTY;
+        const uint32_t r = mf_wave_reserve(cursor, here ? 1u : 0u);
+        if (here) { okeys[r] = raw.x; ovals[r] = raw.y; }
+    }
+}
+int mf_sort_u64_u64(mf_ctx *ctx, const uint64_t *d_keys_in, const uint64_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint64_t *d_vals_out);
+
+int mf_ctable_adopt(mf_ctx *ctx, int k, uint64_t n, uint64_t *d_keys, size_t kb, uint64_t *d_vals, size_t vb, mf_ctable **out) {
+    mf_ctable *t = new mf_ctable();
+    t->ctx = ctx; t->k = k; t->n = n; t->d_keys = d_keys; t->keys_bytes = kb; t->d_vals = d_vals; t->vals_bytes = vb;
+    *out = t;
+    return MF_OK;
+}
+extern "C" void mf_ctable_destroy(mf_ctable *t) {
+    if (!t) return;
+    if (t->d_keys) mf_release(t->ctx, t->d_keys, t->keys_bytes);
+    if (t->d_vals) mf_release(t->ctx, t->d_vals, t->vals_bytes);
+    delete t;
+}
+extern "C" int mf_ctable_stats(const mf_ctable *t, uint64_t *n, int *k) {
+    if (!t) return mf_set_error("mf_ctable_stats: NULL table");
+    if (n) *n = t->n;
+    if (k) *k = t->k;
+    return MF_OK;
+}
+extern "C" int mf_ctable_export(const mf_ctable *t, uint64_t *keys, uint64_t *values, uint64_t cap, uint64_t *n) {
+    if (!t || !n) return mf_set_error("mf_ctable_export: NULL argument");
+    *n = t->n;
+    if (!cap) return MF_OK;
+    if (cap < t->n || !keys || !values) return mf_set_error("mf_ctable_export: room for %llu entries, the table has %llu", (unsigned long long)cap, (unsigned long long)t->n);
+    mf_ctx *ctx = t->ctx;
+    MF_HIP(hipSetDevice(ctx->device));
+    if (t->n) {
+        MF_HIP(hipMemcpyAsync(keys, t->d_keys, t->n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipMemcpyAsync(values, t->d_vals, t->n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    return MF_OK;
+}
+
+// host pairs, any order, duplicates allowed -> ascending table; the values of a key are added as 64-bit integers, saturating at
+// 2^63 - 1 (BigLong2LongHashMap.addAndBound)
+static int ctable_from_pairs(mf_ctx *ctx, std::vector<std::pair<uint64_t, uint64_t>> &pr, int k, mf_ctable **out) {
+    std::sort(pr.begin(), pr.end());
+    const uint64_t VMAX = 0x7FFFFFFFFFFFFFFFull;
+    std::vector<uint64_t> keys, vals;
+    for (size_t i = 0; i < pr.size(); i++) {
+        if (!keys.empty() && keys.back() == pr[i].first) { uint64_t &v = vals.back(); v = v > VMAX - pr[i].second ? VMAX : v + pr[i].second; }
+        else { keys.push_back(pr[i].first); vals.push_back(pr[i].second); }
+    }
+    if (!keys.empty() && k < 32 && (keys.back() >> (2 * k)))
+        return mf_set_error("colored k-mers: key %llu does not fit %d-mers (2k = %d bits)", (unsigned long long)keys.back(), k, 2 * k);
+    const uint64_t n = keys.size();
+    mf_buf<uint64_t> dk, dv;
+    MF_TRY(dk.alloc(ctx, n)); MF_TRY(dv.alloc(ctx, n));
+    if (n) {
+        MF_HIP(hipMemcpyAsync(dk.p, keys.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+        MF_HIP(hipMemcpyAsync(dv.p, vals.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t kb = dk.bytes(), vb = dv.bytes();
+    return mf_ctable_adopt(ctx, k, n, dk.take(), kb, dv.take(), vb, out);
+}
+
+extern "C" int mf_ctable_from_host(mf_ctx *ctx, const uint64_t *keys, const uint64_t *values, uint64_t n, int k, mf_ctable **out) {
+    if (!ctx || !out || (n && (!keys || !values))) return mf_set_error("mf_ctable_from_host: NULL argument");
+    *out = nullptr;
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    MF_HIP(hipSetDevice(ctx->device));
+    std::vector<std::pair<uint64_t, uint64_t>> pr((size_t)n);
+    for (uint64_t i = 0; i < n; i++) {
+        if (values[i] >> 63) return mf_set_error("mf_ctable_from_host: value of entry %llu has the sign bit set", (unsigned long long)i);
+        pr[(size_t)i] = {keys[i], values[i]};
+    }
+    return ctable_from_pairs(ctx, pr, k, out);
+}
+
+static inline uint64_t be64(const unsigned char *p) {
+    uint64_t x = 0;
+    for (int i = 0; i < 8; i++) x = (x << 8) | p[i];
+    return x;
+}
+// IOUtils.loadLongKmers (src/io/IOUtils.java:260-281, 403-440): 16-byte big-endian records (key, value); a record is kept iff its value
+// is > min_value (signed: one with the sign bit set never is)
+extern "C" int mf_ctable_load(mf_ctx *ctx, const char *const *files, int nfiles, int64_t min_value, int k, mf_ctable **out) {
+    mf_range rng_("mf:ctable_load");
+    if (!ctx || !out || nfiles < 0 || (nfiles && !files)) return mf_set_error("mf_ctable_load: NULL argument");
+    *out = nullptr;
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    MF_HIP(hipSetDevice(ctx->device));
+    std::vector<std::pair<uint64_t, uint64_t>> pr;
+    for (int j = 0; j < nfiles; j++) {
+        if (!files[j]) return mf_set_error("mf_ctable_load: file %d is NULL", j);
+        FILE *f = fopen(files[j], "rb");
+        if (!f) return mf_set_error("can't open '%s'", files[j]);
+        std::vector<unsigned char> buf(1 << 20);
+        size_t got, carry = 0;
+        while ((got = fread(buf.data() + carry, 1, buf.size() - carry, f)) > 0) {
+            const size_t have = carry + got, whole = have / 16 * 16;
+            for (size_t o = 0; o < whole; o += 16) {
+                const uint64_t key = be64(&buf[o]); const int64_t v = (int64_t)be64(&buf[o + 8]);
+                if (v > min_value && v >= 0) pr.push_back({key, (uint64_t)v});
+            }
+            carry = have - whole;
+            memmove(buf.data(), buf.data() + whole, carry);
+        }
+        fclose(f);
+        if (carry) return mf_set_error("'%s' is not a file of 16-byte (k-mer, value) records: %llu bytes are left over", files[j], (unsigned long long)carry);
+    }
+    return ctable_from_pairs(ctx, pr, k, out);
+}
+
+// the distinct values with the number of k-mers of each, ascending
+static int ctable_hist(const mf_ctable *t, std::map<uint64_t, uint64_t> &hist) {
+    mf_ctx *ctx = t->ctx;
+    if (!t->n) return MF_OK;
+    mf_buf<uint64_t> v; MF_TRY(v.alloc(ctx, t->n));
+    MF_HIP(hipMemcpyAsync(v.p, t->d_vals, t->n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return kmf_histogram(ctx, v, t->n, hist, 63);
+}
+
+extern "C" int mf_ctable_write(const mf_ctable *t, const char *kmers_bin, const char *stat_txt, uint64_t *n_written) {
+    mf_range rng_("mf:ctable_write");
+    if (!t || !kmers_bin) return mf_set_error("mf_ctable_write: NULL argument");
+    mf_ctx *ctx = t->ctx;
+    MF_HIP(hipSetDevice(ctx->device));
+    std::vector<uint64_t> keys((size_t)t->n), vals((size_t)t->n);
+    uint64_t n = 0;
+    MF_TRY(mf_ctable_export(t, keys.data(), vals.data(), t->n, &n));
+    FILE *f = fopen(kmers_bin, "wb");
+    if (!f) return mf_set_error("can't write '%s'", kmers_bin);
+    std::vector<unsigned char> buf;
+    buf.reserve(1 << 20);
+    uint64_t w = 0;
+    bool ok = true;
+    for (uint64_t i = 0; i < n && ok; i++) {
+        if (vals[(size_t)i] == 0) continue;                   // (printKmers writes the entries with value > 0)
+        for (int s = 56; s >= 0; s -= 8) buf.push_back((unsigned char)(keys[(size_t)i] >> s));
+        for (int s = 56; s >= 0; s -= 8) buf.push_back((unsigned char)(vals[(size_t)i] >> s));
+        w++;
+        if (buf.size() >= (1 << 20) - 16) { ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); }
+    }
+    if (ok && !buf.empty()) ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    if (fclose(f) != 0 || !ok) return mf_set_error("can't write '%s'", kmers_bin);
+    if (stat_txt) {
+        std::map<uint64_t, uint64_t> hist;
+        MF_TRY(ctable_hist(t, hist));
+        FILE *g = fopen(stat_txt, "w");
+        if (!g) return mf_set_error("can't write '%s'", stat_txt);
+        fprintf(g, "# k-mer frequency\tnumber of such k-mers\n");
+        for (auto &kv : hist) fprintf(g, "%llu\t%llu\n", (unsigned long long)kv.first, (unsigned long long)kv.second);
+        fprintf(g, "\n");
+        if (fclose(g) != 0) return mf_set_error("can't write '%s'", stat_txt);
+    }
+    if (n_written) *n_written = w;
+    return MF_OK;
+}
+
+static int color_check(int n, const int *classes, int max_bad) {
+    if (n > MF_COLOR_MAX_N) return mf_set_error("kmers-color: %d samples, at most %d (a field of the packed value holds 20 bits)", n, MF_COLOR_MAX_N);
+    if (max_bad < 0) return mf_set_error("kmers-color: maximal-bad-frequency = %d is negative", max_bad);
+    for (int j = 0; j < n; j++)
+        if (classes[j] < 0 || classes[j] > 2) return mf_set_error("kmers-color: sample %d has class %d (the classes are 0, 1 and 2)", j, classes[j]);
+    return MF_OK;
+}
+
+static int color_join(mf_ctx *ctx, const stats_get &get, int N, const int *classes, uint64_t total, int b, int count_values, int k, mf_ctable **out) {
+    uint32_t S = 1; uint64_t cap = 0;
+    MF_TRY(plan_slices(ctx, total, &S, &cap));
+    std::vector<std::unique_ptr<mf_buf<uint64_t>>> pk, pv;
+    std::vector<uint64_t> ns;
+    for (uint32_t s = 0; s < S; s++) {
+        mf_buf<mf_uslot> slots; uint64_t nu = 0;
+        MF_TRY(union_slice(ctx, get, N, b, S, s, cap, slots, [&](int j) { return (uint32_t)classes[j] | (count_values ? 4u : 0u); }, &nu, MF_UNION_COLOR));
+        if (nu > MF_JOIN_CURSOR_MAX) return mf_set_error("kmers-color: %llu union k-mers in one slice, at most 2^32 - 1 (raise option stats_slices)", (unsigned long long)nu);
+        pk.emplace_back(new mf_buf<uint64_t>()); pv.emplace_back(new mf_buf<uint64_t>());
+        MF_TRY(pk.back()->alloc(ctx, nu)); MF_TRY(pv.back()->alloc(ctx, nu));
+        mf_buf<unsigned int> cur; MF_TRY(cur.alloc(ctx, 1));
+        MF_HIP(hipMemsetAsync(cur.p, 0, 4, ctx->stream));
+        {
+            mf_ktimer tm(ctx, "k_color_read");
+            k_color_read<<<grid_for(ctx, cap), 256, 0, ctx->stream>>>(slots.p, cap, pk.back()->p, pv.back()->p, cur.p);
+        }
+        unsigned int m = 0;
+        MF_HIP(hipMemcpyAsync(&m, cur.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipStreamSynchronize(ctx->stream));
+        if (m != nu) return mf_set_error("kmers-color: %u union entries written, %llu claimed", m, (unsigned long long)nu);
+        ns.push_back(m);
+    }
+    std::vector<mf_buf<uint64_t> *> kp, vp;
+    for (auto &x : pk) kp.push_back(x.get());
+    for (auto &x : pv) vp.push_back(x.get());
+    mf_buf<uint64_t> keys, vals; uint64_t n = 0, n2 = 0;
+    MF_TRY(concat(ctx, kp, ns, keys, &n));
+    MF_TRY(concat(ctx, vp, ns, vals, &n2));
+    pk.clear(); pv.clear();
+    if (n > MF_JOIN_CURSOR_MAX) return mf_set_error("kmers-color: %llu k-mers, at most 2^32 - 1", (unsigned long long)n);
+    // one sort by key
+    mf_buf<uint64_t> sk, sv;
+    MF_TRY(sk.alloc(ctx, n)); MF_TRY(sv.alloc(ctx, n));
+    if (n) MF_TRY(mf_sort_u64_u64(ctx, keys.p, vals.p, n, 62, sk.p, sv.p));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t kb = sk.bytes(), vb = sv.bytes();
+    return mf_ctable_adopt(ctx, k, n, sk.take(), kb, sv.take(), vb, out);
+}
+
+extern "C" int mf_kmers_color_tables(mf_ctx *ctx, mf_table *const *t, const int *classes, int n, int max_bad, int count_values, mf_ctable **out) {
+    mf_range rng_("mf:kmers_color");
+    if (!ctx || !out || n < 0 || (n && (!t || !classes))) return mf_set_error("mf_kmers_color_tables: NULL argument");
+    *out = nullptr;
+    MF_TRY(color_check(n, classes, max_bad));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    MF_TRY(tables_total(ctx, t, n, "mf_kmers_color_tables", &total));
+    const int k = n ? t[0]->k : 31;
+    stats_get get = [&](int j, int, mf_table **tt, bool *own, uint64_t *) -> int { *tt = t[j]; *own = false; return MF_OK; };
+    return color_join(ctx, get, n, classes, total, max_bad, count_values, k, out);
+}
+
+extern "C" int mf_kmers_color(mf_ctx *ctx, const char *const *files, const int *classes, int n, int max_bad, int count_values, int k,
+                              const char *kmers_bin, const char *stat_txt, uint64_t *n_kmers) {
+    mf_range rng_("mf:kmers_color(files)");
+    if (!ctx || !kmers_bin || n < 0 || (n && (!files || !classes))) return mf_set_error("mf_kmers_color: NULL argument");
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    MF_TRY(color_check(n, classes, max_bad));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    MF_TRY(file_records(files, n, &total));
+    stats_get get = [&](int j, int, mf_table **tt, bool *own, uint64_t *) -> int {
+        const char *one[1] = {files[j]};
+        *own = true;
+        return mf_table_load_kmers_sum(ctx, one, 1, max_bad, k, tt, nullptr);
+    };
+    mf_ctable *t = nullptr;
+    MF_TRY(color_join(ctx, get, n, classes, total, max_bad, count_values, k, &t));
+    uint64_t w = 0;
+    const int rc = mf_ctable_write(t, kmers_bin, stat_txt, &w);
+    mf_ctable_destroy(t);
+    if (rc == MF_OK && n_kmers) *n_kmers = w;
+    return rc;
 }

@@ -152,6 +152,16 @@ _SIGS = {
     "mf_kmers_multiple_filters_tables": (i32, [vp, vp, vp, vp, vp, i32, pvp, vp, vp, u64, pu64, vp]),
     "mf_kmers_multiple_filters": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32,
                                         C.POINTER(cp), C.POINTER(cp), vp]),
+    "mf_ctable_from_host": (i32, [vp, vp, vp, u64, i32, pvp]),
+    "mf_ctable_load": (i32, [vp, C.POINTER(cp), i32, i64, i32, pvp]),
+    "mf_ctable_stats": (i32, [vp, pu64, C.POINTER(C.c_int)]),
+    "mf_ctable_export": (i32, [vp, vp, vp, u64, pu64]),
+    "mf_ctable_write": (i32, [vp, cp, cp, pu64]),
+    "mf_ctable_destroy": (None, [vp]),
+    "mf_kmers_color_tables": (i32, [vp, vp, vp, i32, i32, i32, pvp]),
+    "mf_kmers_color": (i32, [vp, C.POINTER(cp), vp, i32, i32, i32, i32, cp, cp, pu64]),
+    "mf_colored_components_device": (i32, [vp, vp, i32, i32, i32, C.c_double, vp, vp]),
+    "mf_colored_components": (i32, [vp, C.POINTER(cp), i32, i32, i64, i32, i32, C.c_double, cp, cp, vp]),
 }
 
 STATS_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "unique_left")
@@ -518,6 +528,52 @@ class Context:
                                                _cfiles(out_stats) if out_stats else None, fk.ctypes.data))
         return [(int(fk[2 * j]), int(fk[2 * j + 1])) for j in range(len(in_files))]
 
+    # ---- colored metagenomic features (pipeline 4) ----
+    def kmers_color(self, tables, classes, b=1, val=False):
+        """ColorKmersMain (src/tools/ColorKmersMain.java:89-136) on resident tables -> CTable of (k-mer, packed class counts)"""
+        h = (C.c_void_p * max(len(tables), 1))(*[t.h for t in tables])
+        cl = np.ascontiguousarray(classes, dtype=np.int32)
+        if len(cl) != len(tables):
+            raise MetafastError("kmers_color: %d tables, %d classes" % (len(tables), len(cl)))
+        t = C.c_void_p()
+        _check(lib().mf_kmers_color_tables(self.h, h, cl.ctypes.data, len(tables), b, 1 if val else 0, C.byref(t)))
+        return CTable(self, t)
+
+    def kmers_color_files(self, files, classes, k, kmers_bin, stat_txt=None, b=1, val=False):
+        cl = np.ascontiguousarray(classes, dtype=np.int32)
+        if len(cl) != len(files):
+            raise MetafastError("kmers_color_files: %d files, %d classes" % (len(files), len(cl)))
+        n = C.c_uint64()
+        _check(lib().mf_kmers_color(self.h, _cfiles(files), cl.ctypes.data, len(files), b, 1 if val else 0, k, os.fsencode(kmers_bin),
+                                    _opt(stat_txt), C.byref(n)))
+        return n.value
+
+    def ctable_from_host(self, keys, values, k):
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        t = C.c_void_p()
+        _check(lib().mf_ctable_from_host(self.h, keys.ctypes.data, values.ctypes.data, len(keys), k, C.byref(t)))
+        return CTable(self, t)
+
+    def load_ctable(self, files, min_value, k):
+        """IOUtils.loadLongKmers (src/io/IOUtils.java:260-281): the records with value > min_value"""
+        t = C.c_void_p()
+        _check(lib().mf_ctable_load(self.h, _cfiles(files), len(files), min_value, k, C.byref(t)))
+        return CTable(self, t)
+
+    def colored_components(self, ct, n_groups=3, separate=False, perc=0.9, k=None):
+        """ColoredComponentsBuilder, default and --separate modes -> [Comps of colour 0 .. n_groups - 1]"""
+        out = (C.c_void_p * max(n_groups, 1))()
+        _check(lib().mf_colored_components_device(self.h, ct.h, ct.k if k is None else k, n_groups, 1 if separate else 0, perc, out, None))
+        return [Comps(self, C.c_void_p(out[c])) for c in range(n_groups)]
+
+    def colored_components_files(self, files, k, out_dir, stat_txt=None, n_groups=3, separate=False, perc=0.9, min_value=None):
+        """ColoredComponentMain (src/tools/ColoredComponentMain.java:83-119); min_value defaults to k, as in the reference"""
+        counts = np.zeros(max(n_groups, 1), dtype=np.uint64)
+        _check(lib().mf_colored_components(self.h, _cfiles(files), len(files), k, k if min_value is None else min_value, n_groups,
+                                           1 if separate else 0, perc, os.fsencode(out_dir), _opt(stat_txt), counts.ctypes.data))
+        return [int(c) for c in counts[:n_groups]]
+
     # ---- synthetic reads ----
     def synth_reads_device(self, seed, sample, first_read, n_reads, read_len, genome_scale_bp, d_bases, d_offsets, sub_per_16384=82):
         """sub_per_16384: substitutions per 16384 bases (82 = 0.5 %, the benchmark's; 164 = 1 %, BASELINE config 5)"""
@@ -863,6 +919,51 @@ class Table:
         t = C.c_void_p()
         _check(lib().mf_table_filter(self.h, threshold, C.byref(t)))
         return Table(self.ctx, t)
+
+
+class CTable:
+    """BigLong2LongHashMap stand-in: k-mer -> 64-bit value, ascending keys, resident in HBM."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None and getattr(self.ctx, "h", None):
+            _lib.mf_ctable_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        n, k = C.c_uint64(), C.c_int()
+        _check(lib().mf_ctable_stats(self.h, C.byref(n), C.byref(k)))
+        return n.value, k.value
+
+    def __len__(self):
+        return self.stats()[0]
+
+    @property
+    def k(self):
+        return self.stats()[1]
+
+    def export(self):
+        """-> (keys uint64[n] ascending, values uint64[n])"""
+        n = len(self)
+        keys = np.empty(n, dtype=np.uint64)
+        vals = np.empty(n, dtype=np.uint64)
+        m = C.c_uint64()
+        if n:
+            _check(lib().mf_ctable_export(self.h, keys.ctypes.data, vals.ctypes.data, n, C.byref(m)))
+        return keys, vals
+
+    def write(self, kmers_bin, stat_txt=None):
+        w = C.c_uint64()
+        _check(lib().mf_ctable_write(self.h, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(w)))
+        return w.value
 
 
 class Seqs:
