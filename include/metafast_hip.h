@@ -444,7 +444,7 @@ int mf_features_reads_device_selected(mf_ctx *ctx, mf_comps *c, const void *d_ba
 int mf_features_reads_selected(mf_ctx *ctx, const char *components_bin, const char *const *files, int nfiles, int k, int threshold,
                                mf_table *selected, const char *vec_path, const char *breadth_path);
 
-/* ---- group comparison: the multi-sample join (pipelines 3 and 5 of the reference's Pipelines.md; mf_stats.hip) -------------------
+/* ---- group comparison: the multi-sample join (pipelines 3 and 5 of the reference's Pipelines.md; mf_stats.hip on mf_join.hip) ------
  * Each k-mer of the union of N samples gets its row of per-sample presence / counts and a decision is made over the row.  Keys are the
  * 64-bit values of the tables / files (below 2^62, as for any k <= 31; a larger one is an error); result tables have k = 31 and come in
  * ascending key order.  Option "stats_slices" (mf_ctx_set_option) forces the number of hash slices of the key space (0: as many as
@@ -471,7 +471,7 @@ int mf_kmers_samples_count_tables(mf_ctx *ctx, mf_table *const *t, int n, int ma
 int mf_kmers_samples_count(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
                            uint64_t *n_kmers);
 
-/* ---- set operations over cohorts on the same join (pipelines 2 and 3 of the reference's Pipelines.md; mf_stats.hip) ----------------
+/* ---- set operations over cohorts on the same join (pipelines 2 and 3 of the reference's Pipelines.md; mf_kmersets.hip) -------------
  * Keys, slices and result tables as above; b = max_bad >= 0 (a negative one is an error); the counts of the tables are 1 .. MF_MAX_COUNT.
  *
  * UniqueKmersMultipleSamplesFinder.runImpl (src/tools/UniqueKmersMultipleSamplesFinder.java:84-185): over the inputs' entries with
@@ -506,7 +506,7 @@ int mf_kmers_multiple_filters(mf_ctx *ctx, const char *const *in_files, int n_in
                               const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
                               const char *const *out_kmers, const char *const *out_stats, uint64_t *found_kept);
 
-/* ---- colored metagenomic features (pipeline 4 of the reference's Pipelines.md; mf_stats.hip, mf_cc.hip) ---------------------------
+/* ---- colored metagenomic features (pipeline 4 of the reference's Pipelines.md; mf_color.hip, mf_ctable.hip, mf_cc.hip) ------------
  * mf_ctable: k-mer -> 64-bit value (BigLong2LongHashMap), ascending keys, resident in HBM.  The values of kmers-color are three 20-bit
  * fields, class c in bits 20c .. 20c + 19. */
 typedef struct mf_ctable mf_ctable;

@@ -98,7 +98,7 @@ struct mf_ctx {
     int64_t opt_cc_compress = 1;   // a pass that points every vertex at its root before the components' sizes are added up (mf_cc.hip, k_cc_compress)
     int64_t opt_cc_sparse = 1;     // component cutter: threshold levels that few vertices reach run on a list of them (0: every level visits all vertices)
     int64_t opt_dcc_sparse = 0;    // sharded cutter, levels after the first: 1 = always the sparse set-up of the arrays over all vertex ids (tests)
-    int64_t opt_stats_slices = 0;  // multi-sample join (mf_stats.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
+    int64_t opt_stats_slices = 0;  // multi-sample join (mf_join.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
     // ... the count for k = 32..63
     int64_t opt_wide_skm = 1;      // mf_count_wide_device: super-k-mer records + LDS tables (mf_wskm.hip) instead of sorting every occurrence (0: the sort path, mf_wide.hip)
     int64_t opt_wide_skm_min = 1 << 20;     // ... from this many k-mer occurrences on (tests: 1)
@@ -490,9 +490,16 @@ int mf_sort_u32_pairs(mf_ctx *ctx, const uint32_t *d_keys_in, const uint32_t *d_
                       uint32_t *d_vals_out);
 int mf_sort_u32_u64(mf_ctx *ctx, const uint32_t *d_keys_in, const uint64_t *d_vals_in, uint64_t n, int bits, uint32_t *d_keys_out,
                     uint64_t *d_vals_out);
+int mf_sort_u64_u32(mf_ctx *ctx, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint32_t *d_vals_out);
 int mf_sort_u64_u64(mf_ctx *ctx, const uint64_t *d_keys_in, const uint64_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint64_t *d_vals_out);
 int mf_sort_u64_u64_pingpong(mf_ctx *ctx, uint64_t *k0, uint64_t *v0, uint64_t n, int first_bit, int bits, uint64_t *k1, uint64_t *v1, int *in_second);
 int mf_sort_u64_u64_range(mf_ctx *ctx, const uint64_t *d_keys_in, const uint64_t *d_vals_in, uint64_t n, int first_bit, int bits, uint64_t *d_keys_out, uint64_t *d_vals_out);
+// the (keys[i], vals[i]) with sel[i] > thr, order kept (mf_table.hip); the sum of a count array (mf_count.hip); mf_table_load_kmers that
+// also adds up the kept records' count fields (mf_io.hip)
+int mf_select_by(mf_ctx *ctx, const uint64_t *keys, const uint16_t *sel, const uint16_t *vals, uint64_t n, int thr, mf_buf<uint64_t> &ok,
+                 mf_buf<uint16_t> &oc, uint64_t *n_out);
+int mf_sum_counts(mf_ctx *ctx, const uint16_t *d_counts, uint64_t n, uint64_t *total);
+int mf_table_load_kmers_sum(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_table **out, uint64_t *freq_sum);
 int mf_sort_kmers_by_comp(mf_ctx *ctx, const uint32_t *d_comp, const uint64_t *d_kmers, uint64_t n, int key_bits, uint32_t n_comps,
                           uint64_t *d_out);
 // the canonical INTERIOR of a k-mer: its middle k-2 bases or their reverse complement, whichever is smaller (rcx = mf_revcomp(x, k)).

@@ -659,7 +659,6 @@ extern "C" int mf_table_write_kmers(const mf_table *t, int threshold, const char
 // the files go to HBM as they are and are decoded there; records with freq <= freq_threshold are dropped; a k-mer that
 // occurs in several files gets the (saturating) sum
 int mf_table_from_device_pairs(mf_ctx *ctx, const uint64_t *d_keys, const uint16_t *d_vals, uint64_t n, int k, mf_table **out);
-int mf_sum_counts(mf_ctx *ctx, const uint16_t *d_counts, uint64_t n, uint64_t *total);
 // freq_sum (may be NULL): the sum of the count fields of the records with count > freq_threshold, before duplicates are summed with
 // saturation -- IOUtils.loadKmersFreq(...).second() (src/io/IOUtils.java:403-435) for freq_threshold = 0; such a load reads the files
 // themselves (a table of the file cache has summed them already)

@@ -7,8 +7,6 @@
 #include <algorithm>
 #include <numeric>
 
-int mf_sum_counts(mf_ctx *ctx, const uint16_t *d_counts, uint64_t n, uint64_t *total);
-
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
@@ -389,7 +387,7 @@ static int select_entries(mf_ctx *ctx, const uint64_t *keys, const uint16_t *cnt
     *n_out = m;
     return MF_OK;
 }
-// the (keys[i], vals[i]) with sel[i] > thr, order kept (the join of mf_stats.hip: one sorted list, one subsequence per threshold)
+// the (keys[i], vals[i]) with sel[i] > thr, order kept (unique-kmers-multi, mf_kmersets.hip: one sorted list, one subsequence per threshold)
 int mf_select_by(mf_ctx *ctx, const uint64_t *keys, const uint16_t *sel, const uint16_t *vals, uint64_t n, int thr, mf_buf<uint64_t> &ok,
                  mf_buf<uint16_t> &oc, uint64_t *n_out) {
     return select_entries<2>(ctx, keys, sel, nullptr, n, thr, ok, oc, n_out, vals);

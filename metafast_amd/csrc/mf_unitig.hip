@@ -863,7 +863,6 @@ extern "C" int mf_seqs_device_view(const mf_seqs *s, const void **d_bases, const
 // host copy in deterministic order (canonical start k-mer, strand)
 // the sequences in their output order (ascending oriented start k-mer), made in HBM: sort of (start k-mer, index), the lengths in that
 // order, their prefix sums, a gather of the bases (a wave per sequence) -- the host sorted and gathered 3e5 sequences in 0.1 s
-int mf_sort_u64_u32(mf_ctx *ctx, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint32_t *d_vals_out);
 __global__ void k_seq_iota(uint32_t *__restrict__ v, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = (uint32_t)i;

@@ -21,8 +21,6 @@
 #include "mf_count_dev.h"
 #include "mf_wide.h"
 
-int mf_sort_u64_u32(mf_ctx *ctx, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint32_t *d_vals_out);
-
 __global__ void k_wide_mask_init(uint32_t *__restrict__ vmask, uint64_t n_words) {
     const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w < n_words) vmask[w] = 0u;

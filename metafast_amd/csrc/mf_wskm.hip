@@ -27,8 +27,6 @@
 #include "mf_common.h"
 #include "mf_wide.h"
 
-int mf_sort_u64_u32(mf_ctx *ctx, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t n, int bits, uint64_t *d_keys_out, uint32_t *d_vals_out);
-
 #define WS_T 256                                   // threads of the scan
 #define WS_TILE 4096                               // base positions (k-mer starts) of a tile
 #define WS_HALO 128                                // positions behind the tile whose bases / hashes the tile's last k-mers need (>= 63 + 15)

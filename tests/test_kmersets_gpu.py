@@ -1,5 +1,5 @@
 """unique-kmers-multi (src/tools/UniqueKmersMultipleSamplesFinder.java:84-185) and kmers-multiple-filters
-(src/tools/KmersMultipleFilters.java:77-133) on the GPU join (mf_stats.hip), through the C-ABI, against the independent restatement
+(src/tools/KmersMultipleFilters.java:77-133) on the GPU join (mf_kmersets.hip), through the C-ABI, against the independent restatement
 tests/kmersets_ref.py: record sets byte-identical, counters equal."""
 import os
 import subprocess

@@ -1,5 +1,5 @@
 """stats-kmers (src/tools/StatsKmersFinder.java:89-297) and kmers-samples-counter (src/tools/KmersSamplesCounter.java:69-140) on the GPU
-(mf_stats.hip), through the C-ABI, against the independent restatement tests/stats_ref.py: record sets byte-identical, counters equal."""
+(mf_stats.hip on the join core mf_join.hip), through the C-ABI, against the independent restatement tests/stats_ref.py: record sets byte-identical, counters equal."""
 import os
 import subprocess
 
@@ -164,7 +164,8 @@ def test_slices_give_identical_files_and_duplicates(gpu_ctx, tmp_path):
         gpu_ctx.set_option("stats_slices", 0)
 
 
-def test_kmers_samples_counter(gpu_ctx, tmp_path):
+def _counter_cohort():
+    """7 samples over a pool of 5 000 keys, a tenth of each sample's k-mers listed twice"""
     rng = np.random.default_rng(8)
     pool = rng.integers(0, 1 << 40, size=5000, dtype=np.uint64)
     samples = []
@@ -174,6 +175,11 @@ def test_kmers_samples_counter(gpu_ctx, tmp_path):
         c = rng.integers(0, 6, size=len(k)).astype(np.int16)
         dup = rng.choice(len(k), size=len(k) // 10, replace=False)
         samples.append((np.concatenate([k, k[dup]]), np.concatenate([c, rng.integers(0, 6, size=len(dup)).astype(np.int16)])))
+    return samples
+
+
+def test_kmers_samples_counter(gpu_ctx, tmp_path):
+    samples = _counter_cohort()
     files = _write_samples(tmp_path, samples, "s")
     for b in (0, 1, 3):
         wk, wn = R.kmers_samples_count(samples, b)
@@ -184,6 +190,53 @@ def test_kmers_samples_counter(gpu_ctx, tmp_path):
         assert st.read_text() == R.stat_txt(wn)
         tabs = [gpu_ctx.load_kmers([f], b, 31) for f in files]
         _same(_export(gpu_ctx.kmers_samples_count(tabs, b)), (wk, wn), "tables b=%d" % b)
+
+
+def test_kmers_samples_counter_over_slices(gpu_ctx, tmp_path):
+    """the per-slice pieces of the read-out: every number of slices gives the restatement's bytes, from files and from tables"""
+    samples = _counter_cohort()
+    files = _write_samples(tmp_path, samples, "s")
+    b = 1
+    wk, wn = R.kmers_samples_count(samples, b)
+    want = [R.records_to_bytes(wk, wn), R.stat_txt(wn).encode()]
+    tabs = [gpu_ctx.load_kmers([f], b, 31) for f in files]
+    blobs = None
+    try:
+        for S in (1, 3, 16):
+            gpu_ctx.set_option("stats_slices", S)
+            out, st = tmp_path / ("n_S%d.kmers.bin" % S), tmp_path / ("n_S%d.stat.txt" % S)
+            assert gpu_ctx.kmers_samples_count_files(files, 31, str(out), str(st), max_bad=b) == len(wk)
+            got = [out.read_bytes(), st.read_bytes()]
+            assert got == want, S
+            tk, tv = _export(gpu_ctx.kmers_samples_count(tabs, b))
+            assert [R.records_to_bytes(tk, tv), R.stat_txt(tv).encode()] == want, S
+            blobs = blobs or got
+            assert got == blobs
+    finally:
+        gpu_ctx.set_option("stats_slices", 0)
+
+
+def test_key_limit_through_the_presence_mode(gpu_ctx):
+    """a key >= 2^62 in any sample is an error of the union pass, and the error leaves nothing behind on the context"""
+    rng = np.random.default_rng(9)
+    pool = rng.integers(0, 1 << 62, size=400, dtype=np.uint64)
+    tabs = []
+    for j in range(6):
+        m = rng.random(len(pool)) < 0.6
+        tabs.append(_tab(gpu_ctx, pool[m], rng.integers(1, 30, size=int(m.sum()))))
+    recs = [_records(t) for t in tabs]
+    one = _tab(gpu_ctx, [5, 6], [3, 3])
+    big = _tab(gpu_ctx, [5, 1 << 62], [3, 3])
+
+    def still_right():
+        _check_stats(gpu_ctx, tabs[:3], tabs[3:], 0, 0.3, 0.05)
+        _same(_export(gpu_ctx.kmers_samples_count(tabs, 0)), R.kmers_samples_count(recs, 0), "n_samples")
+
+    for bad in (lambda: gpu_ctx.stats_kmers([big], [one]), lambda: gpu_ctx.stats_kmers([one], [big]),
+                lambda: gpu_ctx.kmers_samples_count([one, big], 0)):
+        with pytest.raises(Exception, match=r"2\^62"):
+            bad()
+        still_right()
 
 
 def test_cli_end_to_end(gpu_ctx, ref_files, tmp_path):

@@ -1,4 +1,4 @@
-"""Time kmers-color and component-colored (mf_stats.hip, mf_cc.hip) on a synthetic cohort, next to their yardsticks: kmers-samples-counter
+"""Time kmers-color and component-colored (mf_color.hip, mf_cc.hip) on a synthetic cohort, next to their yardsticks: kmers-samples-counter
 on the same tables (the same union with one word instead of three fields) and the component cutter on a table of as many k-mers with one
 threshold level (one adjacency, one union-find pass).
 

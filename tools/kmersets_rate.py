@@ -1,4 +1,4 @@
-"""Time unique-kmers-multi and kmers-multiple-filters (mf_stats.hip) on a synthetic cohort, next to kmers-samples-counter on the same
+"""Time unique-kmers-multi and kmers-multiple-filters (mf_kmersets.hip) on a synthetic cohort, next to kmers-samples-counter on the same
 inputs (it does the same union pass).
 
 The cohort is tools/stats_rate.py's: --n inputs (group A) + --n filters (group B) of --reads reads each, counted by the library at k = 31.

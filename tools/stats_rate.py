@@ -1,4 +1,4 @@
-"""Time the multi-sample join behind stats-kmers (mf_stats.hip) on a synthetic cohort.
+"""Time the multi-sample join behind stats-kmers (mf_stats.hip on the join core mf_join.hip) on a synthetic cohort.
 
 The cohort: --a + --b samples of --reads reads each (mf_synth_reads_device: most reads from one shared seed with the sample's own
 abundances, a share from its group's seed), counted by the library at k = 31.  Timed with device-synchronised wall time:
