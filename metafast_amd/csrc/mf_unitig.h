@@ -18,5 +18,17 @@ struct ut_arrays {
 
 // U2 .. U5 of mf_unitig.hip on a table of n good k-mers: `flags` launches the kernel(s) that fill A.info / A.ridx / A.lidx (/ A.pal) -- U1, the
 // only step that looks k-mers up --, everything after works on node ids.  d_part_off / part_bits: the table's minimizer partitions (0: none).
+// trace (may be nullptr; for the tests, mf_debug_unitigs): what the host saw on its way -- nothing is launched or copied for it.
+struct mf_ut_trace {
+    uint64_t n_starts;        // start nodes (walks of U3)
+    uint64_t walk_rounds;     // launches of k_ut_walk1
+    uint64_t doubled;         // 1: U3b ran, the segment cuts came from the entries (k_utd_*); 0: from k_ut_segments
+    uint64_t entries;         // doubled: entry nodes
+    uint64_t double_rounds;   // doubled: rounds of k_utd_double
+    uint64_t longest;         // doubled: nodes of the longest path
+    uint64_t candidates;      // paths counted by pass 0 of k_ut_ends (before the equal-case arbitration)
+    uint64_t paths;           // paths written
+    uint64_t seg_slots;       // segment slots allocated (k_ut_seg_bound)
+};
 int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint16_t *gv, uint64_t n, int k, int part_bits, const uint64_t *d_part_off,
-                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out);
+                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out, mf_ut_trace *trace = nullptr);

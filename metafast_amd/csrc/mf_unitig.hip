@@ -537,8 +537,9 @@ __global__ void k_fill_u32(uint32_t *p, uint64_t n, uint32_t v) {
 static inline unsigned grid_for(uint64_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint16_t *gv, uint64_t n, int k, int part_bits, const uint64_t *d_part_off,
-                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out) {
+                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out, mf_ut_trace *trace) {
     hipStream_t st = ctx->stream;
+    if (trace) *trace = mf_ut_trace{};
     const bool wide = ghi != nullptr;
     mf_seqs *S = new mf_seqs();
     S->ctx = ctx; S->k = k;
@@ -606,6 +607,7 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
         mf_buf<uint64_t> d_ej; mf_buf<uint32_t> d_ent;                          // U3b (long paths): the doubled jump words of the entry nodes, entry -> node
         uint64_t d_n_ent = 0;
         int doubled = 0;
+        int tr_double_rounds = 0; unsigned int tr_longest = 0; uint64_t tr_slots = 0;      // (for the trace)
         if (n_starts) {
             mf_buf<ut_item> contA, contB;
             if ((rc = contA.alloc(ctx, n_starts)) < 0) break;
@@ -665,6 +667,7 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
                         for (; done_rounds < need + 1; done_rounds++) k_utd_double<<<grid_for(n_ent), 256, 0, st>>>(d_ej.p, d_ej.p, n_ent);
                         hipMemsetAsync(&ctr.p[2], 0, 4, st);
                         doubled = 1; ctx->n_ut_doubled++; d_n_ent = n_ent;
+                        tr_double_rounds = done_rounds; tr_longest = longest + 1;
                         if (ctx->opt_verbose) fprintf(stderr, "[mf] unitigs: %u walks still under way after %d rounds: jump words doubled over %llu entry nodes of %llu in %d rounds (longest path %u nodes)\n",
                                                       n_cont, rounds, (unsigned long long)n_ent, (unsigned long long)nn, done_rounds, longest + 1);
                         break;
@@ -734,6 +737,7 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
                 rc = mf_set_error("unitigs: scan failed"); break;
             }
             mf_buf<ut_seg> seg;
+            tr_slots = n_seg;
             if ((rc = seg.alloc(ctx, n_seg)) < 0) break;
             hipMemsetAsync(seg.p, 0xFF, n_seg * sizeof(ut_seg), st);
             hipMemsetAsync(wsum.p, 0, (size_t)np * 8, st);
@@ -766,6 +770,10 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
         if (ctx->opt_verbose)
             fprintf(stderr, "[mf] unitigs: good=%llu starts=%u walk_rounds=%d+%d candidates=%u paths=%u bases=%llu\n", (unsigned long long)n,
                     n_starts, rounds, rounds2, ncand, np, (unsigned long long)total);
+        if (trace) {
+            trace->n_starts = n_starts; trace->walk_rounds = (uint64_t)rounds; trace->doubled = (uint64_t)doubled; trace->entries = d_n_ent;
+            trace->double_rounds = (uint64_t)tr_double_rounds; trace->longest = tr_longest; trace->candidates = ncand; trace->paths = np; trace->seg_slots = tr_slots;
+        }
         S->n = np; S->n_bases = total;
         S->bases_bytes = bases.bytes(); S->d_bases = bases.take();
         S->offsets_bytes = off.bytes(); S->d_offsets = off.take();
@@ -778,12 +786,42 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
     return MF_OK;
 }
 
+// U1 of a table by one of its two paths: the partition-local lookups (MODE 1 + MODE 2 of k_ut_flags_part; the table must have an index over
+// minimizer partitions, ut_flags_has_parts) or eight lookups in the HBM index per k-mer (k_ut_flags)
+static bool ut_flags_has_parts(const mf_table *g) { return g->index.skm_k && g->index.part_bits && g->d_part_off; }
+// ... the path the table and option nbr_global ask for
+// (small partitions: the set-up per partition outweighs the local lookups; nbr_global = -1 takes them all the same, 1 never)
+static bool ut_flags_local(const mf_ctx *ctx, const mf_table *g) {
+    return ut_flags_has_parts(g) && ctx->opt_nbr_global <= 0 && (ctx->opt_nbr_global < 0 || (g->n >> g->part_bits) >= 100);
+}
+static void ut_flags_launch(mf_ctx *ctx, const mf_table *g, bool local, const ut_arrays &A) {
+    hipStream_t st = ctx->stream;
+    const int k = g->k;
+    const uint64_t n = g->n;
+    if (local) {
+        const uint32_t np = 1u << g->part_bits;
+        const unsigned grid = (unsigned)std::min<uint64_t>((np + NB_WAVES - 1) / NB_WAVES, (uint64_t)ctx->n_cu * 64);
+        const unsigned grid2 = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * 16);      // partitions of 353 .. 1408 keys: a workgroup each
+        // k as a compile-time constant for the k values users run (round 5: 31 alone was specialised, and k = 21 -- BASELINE config 4 --
+        // and the CAMI example's 23, Example.md:18-21, paid 2.8 x per k-mer in the generic build); any other k: the generic one
+#define UT_FLAGS_K(KK) case KK: k_ut_flags_part<1, KK><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np); \
+                        k_ut_flags_part<2, KK><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np); break;
+        switch (k) {
+            UT_FLAGS_K(21) UT_FLAGS_K(23) UT_FLAGS_K(25) UT_FLAGS_K(27) UT_FLAGS_K(29) UT_FLAGS_K(31)
+            default:
+                k_ut_flags_part<1><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np);
+                k_ut_flags_part<2><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np);
+        }
+#undef UT_FLAGS_K
+    } else
+        k_ut_flags<<<grid_for(n), 256, 0, st>>>(mf_view(g->index), A);
+}
+
 extern "C" int mf_build_unitigs_device(mf_ctx *ctx, mf_table *t, int freq_threshold, int min_len, mf_seqs **out) {
     mf_range rng_("mf:unitigs");
     if (!ctx || !t || !out) return mf_set_error("mf_build_unitigs_device: NULL argument");
     *out = nullptr;
     MF_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     const int k = t->k;
 
     // nodes = k-mers with value > freqThreshold (task.run :46-48)
@@ -808,27 +846,141 @@ extern "C" int mf_build_unitigs_device(mf_ctx *ctx, mf_table *t, int freq_thresh
                     npart, (double)n / npart, (unsigned long long)mx, NB_CAP, 100.0 * over / n, (unsigned long long)nover, 100.0 * b[0] / n, 100.0 * b[1] / n, 100.0 * b[2] / n,
                     100.0 * b[3] / n, 100.0 * b[4] / n, 100.0 * b[5] / n);
         }
-        {
-            if (g->index.skm_k && g->index.part_bits && g->d_part_off && ctx->opt_nbr_global <= 0 && (ctx->opt_nbr_global < 0 || (n >> g->part_bits) >= 100)) {      // (small partitions: the set-up per partition outweighs the local lookups; nbr_global = -1 takes them all the same)
-                const uint32_t np = 1u << g->part_bits;
-                const unsigned grid = (unsigned)std::min<uint64_t>((np + NB_WAVES - 1) / NB_WAVES, (uint64_t)ctx->n_cu * 64);
-                const unsigned grid2 = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * 16);      // partitions of 353 .. 1408 keys: a workgroup each
-                // k as a compile-time constant for the k values users run (round 5: 31 alone was specialised, and k = 21 -- BASELINE config 4 --
-                // and the CAMI example's 23, Example.md:18-21, paid 2.8 x per k-mer in the generic build); any other k: the generic one
-#define UT_FLAGS_K(KK) case KK: k_ut_flags_part<1, KK><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np); \
-                                k_ut_flags_part<2, KK><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np); break;
-                switch (k) {
-                    UT_FLAGS_K(21) UT_FLAGS_K(23) UT_FLAGS_K(25) UT_FLAGS_K(27) UT_FLAGS_K(29) UT_FLAGS_K(31)
-                    default:
-                        k_ut_flags_part<1><<<grid, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np);
-                        k_ut_flags_part<2><<<grid2, 64 * NB_WAVES, 0, st>>>(mf_view(g->index), A, g->d_part_off, np);
-                }
-#undef UT_FLAGS_K
-            } else
-            k_ut_flags<<<grid_for(n), 256, 0, st>>>(mf_view(g->index), A);
-        }
+        ut_flags_launch(ctx, g, ut_flags_local(ctx, g), A);
         return MF_OK;
     }, out);
+}
+
+// For the tests (not in include/metafast_hip.h): U1 alone, by one chosen path, with the table's layout.  path 0: k_ut_flags; path 1: the launches
+// of k_ut_flags_part as mf_build_unitigs_device makes them -- an error where the table has no minimizer partitions or their index.
+// keys_out[n]: the keys in table order; info_out / ridx_out / lidx_out[n]: the U1 arrays (ridx / lidx mean something only where the code of
+// their side is below 4); pal_out[n]: written for an even k only (may be NULL for an odd one); *part_bits and part_off_out[2^part_bits + 1]:
+// the partitions of the table (0 and untouched: it has none).
+extern "C" int mf_debug_unitig_flags(mf_ctx *ctx, mf_table *t, int path, uint64_t *keys_out, uint8_t *info_out, uint32_t *ridx_out, uint32_t *lidx_out,
+                                     uint8_t *pal_out, int *part_bits, uint64_t *part_off_out, uint64_t part_off_cap) {
+    if (!ctx || !t || !keys_out || !info_out || !ridx_out || !lidx_out || !part_bits) return mf_set_error("mf_debug_unitig_flags: NULL argument");
+    if (t->ctx != ctx) return mf_set_error("mf_debug_unitig_flags: the table belongs to another context");
+    if (path != 0 && path != 1) return mf_set_error("mf_debug_unitig_flags: path %d", path);
+    const int k = t->k;
+    const bool even = (k & 1) == 0;
+    if (even && !pal_out) return mf_set_error("mf_debug_unitig_flags: k = %d is even, the palindrome flags need a place", k);
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = t->n;
+    if (n >= 0x7FFFFFFFull) return mf_set_error("unitigs: more than 2^31 good k-mers per table is not supported");
+    const bool parts = t->part_bits > 0 && t->d_part_off;
+    *part_bits = parts ? t->part_bits : 0;
+    if (parts && part_off_out) {
+        const uint64_t need = (1ull << t->part_bits) + 1;
+        if (part_off_cap < need) return mf_set_error("mf_debug_unitig_flags: room for %llu partition offsets, the table has %llu", (unsigned long long)part_off_cap, (unsigned long long)need);
+        MF_HIP(hipMemcpyAsync(part_off_out, t->d_part_off, need * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (n) MF_TRY(mf_table_ensure_index(t));
+    if (path == 1 && !ut_flags_has_parts(t))
+        return mf_set_error("mf_debug_unitig_flags: the table has no index over minimizer partitions (the partition-local lookup cannot run on it)");
+    if (n) {
+        mf_buf<uint8_t> info, pal; mf_buf<uint32_t> ridx, lidx;
+        MF_TRY(info.alloc(ctx, n)); MF_TRY(ridx.alloc(ctx, n)); MF_TRY(lidx.alloc(ctx, n));
+        if (even) MF_TRY(pal.alloc(ctx, n));
+        ut_arrays A;
+        A.gk = t->d_keys; A.ghi = nullptr; A.gv = t->d_counts; A.n = n; A.k = k;
+        A.info = info.p; A.ridx = ridx.p; A.lidx = lidx.p; A.pal = even ? pal.p : nullptr;
+        A.node = nullptr; A.jump = nullptr; A.starts = nullptr; A.n_starts = nullptr;
+        ut_flags_launch(ctx, t, path == 1, A);
+        MF_HIP(hipGetLastError());
+        MF_HIP(hipMemcpyAsync(info_out, info.p, n, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(ridx_out, ridx.p, n * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(lidx_out, lidx.p, n * 4, hipMemcpyDeviceToHost, st));
+        if (even) MF_HIP(hipMemcpyAsync(pal_out, pal.p, n, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(keys_out, t->d_keys, n * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipStreamSynchronize(st));                  // (the buffers are released below)
+    } else MF_HIP(hipStreamSynchronize(st));
+    return MF_OK;
+}
+
+// For the tests (not in include/metafast_hip.h): U2 .. U5 alone (mf_ut_build), on a table and U1 arrays the caller made up.  lo[n] (and hi[n],
+// given exactly when k >= 33): the k-mers in any order -- the order IS the table order, node 2 i + strand belongs to k-mer i --; counts[n]:
+// 1 .. MF_MAX_COUNT; info / ridx / lidx[n]: as k_ut_flags leaves them (ridx / lidx are looked at only where the code of their side is below 4);
+// pal[n]: given exactly when k is even; part_bits, part_off[2^part_bits + 1]: minimizer partitions (0, NULL: none -- one hop per jump word).
+// The links the arrays describe must be mutual (where f -> g is a link, the unique left neighbour of g is f), so that they form paths and
+// cycles: the kernels rely on it (two paths into one end node would share its segment slots).  trace[MF_UT_TRACE_FIELDS] (may be NULL): the
+// fields of mf_ut_trace in their order.  Everything is checked here, on the host, before anything is launched.
+#define MF_UT_TRACE_FIELDS 9
+extern "C" int mf_debug_unitigs(mf_ctx *ctx, uint64_t n, const uint64_t *lo, const uint64_t *hi, const uint16_t *counts, const uint8_t *info, const uint32_t *ridx,
+                                const uint32_t *lidx, const uint8_t *pal, int k, int min_len, int part_bits, const uint64_t *part_off, mf_seqs **out, uint64_t *trace) {
+    if (!ctx || !out) return mf_set_error("mf_debug_unitigs: NULL argument");
+    *out = nullptr;
+    if (k < 1 || k > 63) return mf_set_error("mf_debug_unitigs: k = %d (1 .. 63)", k);
+    if (n >= 0x7FFFFFFFull) return mf_set_error("mf_debug_unitigs: %llu k-mers (fewer than 2^31 - 1 are supported)", (unsigned long long)n);
+    if (n && (!lo || !counts || !info || !ridx || !lidx)) return mf_set_error("mf_debug_unitigs: NULL argument");
+    const bool wide = k >= 33, even = (k & 1) == 0;
+    if (n && wide != (hi != nullptr)) return mf_set_error("mf_debug_unitigs: high words are given exactly when k >= 33 (k = %d)", k);
+    if (n && even != (pal != nullptr)) return mf_set_error("mf_debug_unitigs: palindrome flags are given exactly when k is even (k = %d)", k);
+    if (part_bits < 0 || part_bits > 26) return mf_set_error("mf_debug_unitigs: part_bits = %d (0 .. 26)", part_bits);
+    if ((part_bits > 0) != (part_off != nullptr)) return mf_set_error("mf_debug_unitigs: partition offsets are given exactly when part_bits > 0");
+    if (part_off) {
+        const uint64_t np = 1ull << part_bits;
+        if (part_off[0] != 0) return mf_set_error("mf_debug_unitigs: partition offsets start at %llu, not at 0", (unsigned long long)part_off[0]);
+        for (uint64_t p = 0; p < np; p++)
+            if (part_off[p + 1] < part_off[p]) return mf_set_error("mf_debug_unitigs: partition offsets decrease at partition %llu", (unsigned long long)p);
+        if (part_off[np] != n) return mf_set_error("mf_debug_unitigs: partition offsets end at %llu, not at n = %llu", (unsigned long long)part_off[np], (unsigned long long)n);
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        if (counts[i] < 1 || counts[i] > MF_MAX_COUNT) return mf_set_error("mf_debug_unitigs: count %u of k-mer %llu (1 .. %d)", (unsigned)counts[i], (unsigned long long)i, MF_MAX_COUNT);
+        const bool fits = wide ? (hi[i] >> (2 * k - 64)) == 0 : (k >= 32 || (lo[i] >> (2 * k)) == 0);
+        if (!fits) return mf_set_error("mf_debug_unitigs: k-mer %llu does not fit %d bits", (unsigned long long)i, 2 * k);
+        const uint32_t rcode = info[i] & 7u, lcode = (info[i] >> 3) & 7u;
+        if (rcode > UT_CODE_MANY || lcode > UT_CODE_MANY) return mf_set_error("mf_debug_unitigs: info byte %#x of k-mer %llu (codes 0 .. 5)", (unsigned)info[i], (unsigned long long)i);
+        if (rcode < 4u && ridx[i] >= n) return mf_set_error("mf_debug_unitigs: right neighbour %u of k-mer %llu (unique: an index below %llu)", ridx[i], (unsigned long long)i, (unsigned long long)n);
+        if (lcode < 4u && lidx[i] >= n) return mf_set_error("mf_debug_unitigs: left neighbour %u of k-mer %llu (unique: an index below %llu)", lidx[i], (unsigned long long)i, (unsigned long long)n);
+        if (pal && pal[i] > 1) return mf_set_error("mf_debug_unitigs: palindrome flag %u of k-mer %llu (0 or 1)", (unsigned)pal[i], (unsigned long long)i);
+    }
+    // the links as k_ut_links reads them (ut_node, ut_right_node, ut_left_node), mutual
+    auto h_node = [&](uint32_t idx, uint32_t strand) { return idx * 2u + ((pal && pal[idx]) ? 0u : strand); };
+    auto h_runique = [&](uint32_t f) { return ((((f & 1u) ? (info[f >> 1] >> 3) : info[f >> 1])) & 7u) < 4u; };
+    auto h_lunique = [&](uint32_t f) { return ((((f & 1u) ? info[f >> 1] : (info[f >> 1] >> 3))) & 7u) < 4u; };
+    auto h_right = [&](uint32_t f) { const uint32_t i = f >> 1; const uint8_t b = info[i]; return (f & 1u) ? h_node(lidx[i], ((b >> 7) & 1u) ^ 1u) : h_node(ridx[i], (b >> 6) & 1u); };
+    auto h_left = [&](uint32_t f) { const uint32_t i = f >> 1; const uint8_t b = info[i]; return (f & 1u) ? h_node(ridx[i], ((b >> 6) & 1u) ^ 1u) : h_node(lidx[i], (b >> 7) & 1u); };
+    for (uint64_t i = 0; i < n; i++)
+        for (uint32_t o = 0; o < ((pal && pal[i]) ? 1u : 2u); o++) {
+            const uint32_t f = (uint32_t)(2 * i) + o;
+            if (!h_runique(f)) continue;
+            const uint32_t g = h_right(f);
+            if (h_lunique(g) && h_left(g) != f)
+                return mf_set_error("mf_debug_unitigs: the links are not mutual: node %u has the successor %u, whose predecessor is %u", f, g, h_left(g));
+        }
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    mf_buf<uint64_t> d_lo, d_hi, d_off; mf_buf<uint16_t> d_cnt; mf_buf<uint8_t> d_info, d_pal; mf_buf<uint32_t> d_ridx, d_lidx;
+    if (n) {
+        MF_TRY(d_lo.alloc(ctx, n)); MF_TRY(d_cnt.alloc(ctx, n)); MF_TRY(d_info.alloc(ctx, n)); MF_TRY(d_ridx.alloc(ctx, n)); MF_TRY(d_lidx.alloc(ctx, n));
+        MF_HIP(hipMemcpyAsync(d_lo.p, lo, n * 8, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(d_cnt.p, counts, n * 2, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(d_info.p, info, n, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(d_ridx.p, ridx, n * 4, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(d_lidx.p, lidx, n * 4, hipMemcpyHostToDevice, st));
+        if (wide) { MF_TRY(d_hi.alloc(ctx, n)); MF_HIP(hipMemcpyAsync(d_hi.p, hi, n * 8, hipMemcpyHostToDevice, st)); }
+        if (even) { MF_TRY(d_pal.alloc(ctx, n)); MF_HIP(hipMemcpyAsync(d_pal.p, pal, n, hipMemcpyHostToDevice, st)); }
+        if (part_off) {
+            const uint64_t cnt = (1ull << part_bits) + 1;
+            MF_TRY(d_off.alloc(ctx, cnt));
+            MF_HIP(hipMemcpyAsync(d_off.p, part_off, cnt * 8, hipMemcpyHostToDevice, st));
+        }
+        MF_HIP(hipStreamSynchronize(st));                  // (the host arrays are the caller's, pageable)
+    }
+    mf_ut_trace tr;
+    MF_TRY(mf_ut_build(ctx, d_lo.p, wide ? d_hi.p : nullptr, d_cnt.p, n, k, part_off ? part_bits : 0, part_off ? d_off.p : nullptr, min_len, [&](const ut_arrays &A) -> int {
+        MF_HIP(hipMemcpyAsync(A.info, d_info.p, n, hipMemcpyDeviceToDevice, st));
+        MF_HIP(hipMemcpyAsync(A.ridx, d_ridx.p, n * 4, hipMemcpyDeviceToDevice, st));
+        MF_HIP(hipMemcpyAsync(A.lidx, d_lidx.p, n * 4, hipMemcpyDeviceToDevice, st));
+        if (A.pal) MF_HIP(hipMemcpyAsync(A.pal, d_pal.p, n, hipMemcpyDeviceToDevice, st));
+        return MF_OK;
+    }, out, &tr));
+    if (trace) {
+        const uint64_t row[MF_UT_TRACE_FIELDS] = {tr.n_starts, tr.walk_rounds, tr.doubled, tr.entries, tr.double_rounds, tr.longest, tr.candidates, tr.paths, tr.seg_slots};
+        memcpy(trace, row, sizeof row);
+    }
+    return MF_OK;
 }
 
 extern "C" void mf_seqs_destroy(mf_seqs *s) {
