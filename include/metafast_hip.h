@@ -470,6 +470,34 @@ int mf_kmers_samples_count_tables(mf_ctx *ctx, mf_table *const *t, int n, int ma
 /* File form: -> kmers_bin (records (x, n(x))) and stat_txt (histogram of n, may be NULL); *n_kmers (may be NULL) = records written */
 int mf_kmers_samples_count(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
                            uint64_t *n_kmers);
+/* StatsKmers3GroupsFinder.runImpl (src/tools/StatsKmers3GroupsFinder.java:92-377), samples numbered A, then B, then C: as
+ * mf_stats_kmers_tables with the three-group chi-squared test on (n1A, n1B, n1C) (2 degrees of freedom; the threshold is the closed form
+ * -2 ln(p_chi2) where the reference runs a numeric solver) and, for p_mw > 0, three Mann-Whitney tests (A, B), (B, C), (A, C): a k-mer is
+ * kept when any of them gives p < p_mw.  A kept k-mer goes to A if mean(A) is greater than both other means, else to B if mean(B) is,
+ * else to C.  counters[10] (MF_STATS3_COUNTERS): k-mers, scarce, present in all, unique (present in one group only), rejected by
+ * chi-squared, rejected by Mann-Whitney, group A, group B, group C, unique left (the reference's log lines :329-339).
+ * 1 <= |A|, |B|, |C|, |A| + |B| + |C| <= 1024. */
+#define MF_STATS3_COUNTERS 10
+int mf_stats_kmers3_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *const *b, int nb, mf_table *const *c, int nc, int max_bad,
+                           double p_chi2, double p_mw, mf_table **chi, mf_table **group_a, mf_table **group_b, mf_table **group_c,
+                           uint64_t *counters);
+/* File form: as mf_stats_kmers -> <out_dir>/filtered_chisquared.kmers.bin + .stat.txt, filtered_group{A,B,C}.kmers.bin */
+int mf_stats_kmers3(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, const char *const *c_files, int nc,
+                    int max_bad, double p_chi2, double p_mw, const char *out_dir, uint64_t *counters);
+/* KmersGroupedSamplesCounter.runImpl (src/tools/KmersGroupedSamplesCounter.java:82-190): for every k-mer x of `kmers` the number of
+ * tables of each group (CD, UC, nonIBD; a group may be empty, at most 1022 tables in one) whose count of x is > max_bad.  *n = the
+ * entries of `kmers`, whatever `cap` is; with cap >= *n, keys[0 .. *n) = the k-mers in ASCENDING order (the reference's order is its hash
+ * map's) and counts[i] = cd << 32 | uc << 16 | nonibd, the packing of mf_kmers_multiple_filters_tables; with a smaller cap nothing is
+ * written (cap = 0 with NULL arrays asks for the number alone).  A key >= 2^62 in any table is an error. */
+int mf_kmers_grouped_count_tables(mf_ctx *ctx, mf_table *kmers, mf_table *const *cd, int n_cd, mf_table *const *uc, int n_uc,
+                                  mf_table *const *nonibd, int n_nonibd, int max_bad, uint64_t *keys, uint64_t *counts, uint64_t cap,
+                                  uint64_t *n);
+/* File form: kmers = IOUtils.loadKmers(kmers_files, 0) (the k-mers with some record > 0; one listed more than once comes once), every group
+ * file loaded at max_bad -> out_txt: the line "Kmer\tcd_count\tuc_count\tnonibd_count", then one line per k-mer in ascending key order,
+ * the k-mer as ShortKmer.toString prints it at this k and the three counts.  1 <= k <= 31; *n_kmers (may be NULL) = lines written. */
+int mf_kmers_grouped_count(mf_ctx *ctx, const char *const *kmers_files, int n_kmers_files, const char *const *cd_files, int n_cd,
+                           const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
+                           const char *out_txt, uint64_t *n_kmers);
 
 /* ---- set operations over cohorts on the same join (pipelines 2 and 3 of the reference's Pipelines.md; mf_kmersets.hip) -------------
  * Keys, slices and result tables as above; b = max_bad >= 0 (a negative one is an error); the counts of the tables are 1 .. MF_MAX_COUNT.

@@ -39,6 +39,10 @@ extern "C" int mf_unique_kmers_multi(mf_ctx *, const char *const *, int, const c
                                      uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_multiple_filters(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int,
                                          int, int, const char *const *, const char *const *, uint64_t *) __attribute__((weak));
+extern "C" int mf_stats_kmers3(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, int, double, double, const char *,
+                               uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_grouped_count(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int, int,
+                                      int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_color(mf_ctx *, const char *const *, const int *, int, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
     __attribute__((weak));
@@ -157,7 +161,8 @@ static const OptDef OPTS[] = {
     {"positiveReads", "pos", true, false}, {"negativeReads", "neg", true, false}, {"filter-kmers", "", true, false}, {"max-thresh", "", false, false},
     {"a-kmers", "A", true, false}, {"b-kmers", "B", true, false}, {"p-value-chi2", "pchi2", false, false}, {"p-value-mw", "pmw", false, false},
     {"min-samples", "", false, false}, {"max-samples", "", false, false}, {"cd-filter-kmers", "cd", true, false}, {"uc-filter-kmers", "uc", true, false},
-    {"nonibd-filter-kmers", "nonibd", true, false},
+    {"nonibd-filter-kmers", "nonibd", true, false}, {"c-kmers", "C", true, false},
+    {"cd-kmers", "cd", true, false}, {"uc-kmers", "uc", true, false}, {"nonibd-kmers", "nonibd", true, false},
     {"class", "", false, false}, {"val", "val", false, true}, {"n_groups", "group", false, false}, {"separate", "", false, true},
     {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false},
 };
@@ -176,11 +181,16 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
             return "reads";
         }
         if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                              tool == "unique-kmers-multi" || tool == "kmers-multiple-filters")
+                              tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "stats-kmers-3" || tool == "kmers-grouped-counter")
                                  ? "maximal-bad-frequence" : "maximal-bad-frequency";
         if (s == "l") return (tool == "seq-builder" || tool == "seq-builder-many") ? "sequence-len" : "min-seq-len";
         if (s == "o") return (tool == "view" || tool == "bin2fasta") ? "output-file" : "output-dir";
         if (s == "kf" && tool == "kmers-color") return "k-mers";            // ColorKmersMain.java:39-43 (view, bin2fasta: kmers-file)
+        if (tool == "kmers-grouped-counter") {                             // KmersGroupedSamplesCounter.java:44-60 (kmers-multiple-filters: *-filter-kmers)
+            if (s == "cd") return "cd-kmers";
+            if (s == "uc") return "uc-kmers";
+            if (s == "nonibd") return "nonibd-kmers";
+        }
         if (s == "cf") return "components-file";                           // ViewMain.java:45, BinaryToFasta.java:47
         for (auto &o : OPTS) if (o.sht[0] && s == o.sht) return o.lng;
         return "";
@@ -205,7 +215,8 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
             continue;
         }
         if (i >= argc) die("Missing argument for option: %s", tok.c_str());
-        if (def->multi) { while (i < argc && !(argv[i][0] == '-' && strlen(argv[i]) > 1 && !isdigit((unsigned char)argv[i][1]))) vals.push_back(argv[i++]); }
+        // (--kmers-file is a list in kmers-grouped-counter, KmersGroupedSamplesCounter.java:38-42, one file in view and bin2fasta)
+        if (def->multi || (tool == "kmers-grouped-counter" && name == "kmers-file")) { while (i < argc && !(argv[i][0] == '-' && strlen(argv[i]) > 1 && !isdigit((unsigned char)argv[i][1]))) vals.push_back(argv[i++]); }
         else vals.push_back(argv[i++]);
     }
     return a;
@@ -870,6 +881,8 @@ static const char *TOOLS_TEXT =
     "kmers-filter\t\tFilter k-mers from test set according to known samples\n"
     "kmers-samples-counter\tCount number of samples containing k-mers from multiple samples\n"
     "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
+    "stats-kmers-3\t\tFind k-mers that differ significantly between three groups of samples (chi-squared + Mann-Whitney)\n"
+    "kmers-grouped-counter\tCount number of samples from 3 groups containing specified k-mers\n"
     "unique-kmers-multi\tOutput k-mers present in one dataset in fixed number of samples and missing in other\n"
     "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
     "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
@@ -930,6 +943,14 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
         v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV("p-value-chi2", a.get("p-value-chi2", "0.05")),
              PV("p-value-mw", a.get("p-value-mw", "0.05")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")),
              PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
+    } else if (tool == "stats-kmers-3") {
+        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV::files("c-kmers", a.list("c-kmers")),
+             PV("p-value-chi2", a.get("p-value-chi2", "0.05")), PV("p-value-mw", a.get("p-value-mw", "0.05")),
+             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")), PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
+    } else if (tool == "kmers-grouped-counter") {
+        v = {opt_i("k"), PV::files("kmers-file", a.list("kmers-file")), PV::files("cd-kmers", a.list("cd-kmers")), PV::files("uc-kmers", a.list("uc-kmers")),
+             PV::files("nonibd-kmers", a.list("nonibd-kmers")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
+             PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
     } else if (tool == "unique-kmers-multi") {
         v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
              PV("min-samples", a.get("min-samples", "1")), PV("max-samples", a.get("max-samples", "1")),
@@ -970,7 +991,8 @@ int main(int argc, char **argv) {
     }
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
-                                  "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored"};
+                                  "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
+                                  "stats-kmers-3", "kmers-grouped-counter"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1042,6 +1064,8 @@ int main(int argc, char **argv) {
     else if (tool == "kmers-filter") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
     else if (tool == "kmers-samples-counter") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "stats-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
+    else if (tool == "stats-kmers-3") { need("a-kmers", "A"); need("b-kmers", "B"); need("c-kmers", "C"); }
+    else if (tool == "kmers-grouped-counter") { need("k", "k"); need("cd-kmers", "cd"); need("uc-kmers", "uc"); need("nonibd-kmers", "nonibd"); }
     else if (tool == "unique-kmers-multi") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
     else if (tool == "kmers-multiple-filters") {
         need("k", "k"); need("k-mers", "i"); need("cd-filter-kmers", "cd"); need("uc-filter-kmers", "uc"); need("nonibd-filter-kmers", "nonibd");
@@ -1166,6 +1190,54 @@ int main(int argc, char **argv) {
         logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
         logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
         outs = {PV::files("resulting-kmers-file", {out_dir + "/filtered_groupA.kmers.bin"})};
+    } else if (tool == "stats-kmers-3") {
+        // StatsKmers3GroupsFinder.java:92-343 (no -k, as stats-kmers).  What the library refuses is refused here first, in its words.
+        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers"), cf = a.list("c-kmers");
+        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
+        const int b = a.geti("maximal-bad-frequence", 0);
+        const string out_dir = a.get("output-dir", wd + "/kmers");
+        if (af.empty() || bf.empty() || cf.empty())
+            die("stats-kmers-3: every group needs at least one sample (|A| = %zu, |B| = %zu, |C| = %zu)", af.size(), bf.size(), cf.size());
+        if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
+        mkdirs(out_dir);
+        if (!mf_stats_kmers3) die("stats-kmers-3: this build of the library has no mf_stats_kmers3");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("INFO", "Loading k-mers occurrences...");
+        auto pa = cptrs(af), pb = cptrs(bf), pc = cptrs(cf);
+        uint64_t c[MF_STATS3_COUNTERS] = {0};
+        check(mf_stats_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), b, pchi2, pmw, out_dir.c_str(), c));
+        logmsg("INFO", "Survived after chi-squared test k-mers printed to: %s", (out_dir + "/filtered_chisquared.kmers.bin").c_str());
+        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
+        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
+        logmsg("INFO", "Group C k-mers printed to %s", (out_dir + "/filtered_groupC.kmers.bin").c_str());
+        logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
+        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
+        logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
+        logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7] + c[8]));
+        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[9]);
+        logmsg("INFO", "Total group A k-mers = %llu", (unsigned long long)c[6]);
+        logmsg("INFO", "Total group B k-mers = %llu", (unsigned long long)c[7]);
+        logmsg("INFO", "Total group C k-mers = %llu", (unsigned long long)c[8]);
+        logmsg("DEBUG", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
+        logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
+        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
+        outs = {PV::file("filtered-kmers-file", out_dir + "/filtered_chisquared.kmers.bin")};
+    } else if (tool == "kmers-grouped-counter") {
+        // KmersGroupedSamplesCounter.java:82-190: per k-mer of -kf the CD, UC and nonIBD files that hold it with a count > b
+        check_k(k);
+        const int b = a.geti("maximal-bad-frequence", 1);
+        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
+        const vector<string> kf = a.list("kmers-file"), cd = a.list("cd-kmers"), uc = a.list("uc-kmers"), ni = a.list("nonibd-kmers");
+        mkdirs(out_dir); mkdirs(st_dir);
+        if (!mf_kmers_grouped_count) die("kmers-grouped-counter: this build of the library has no mf_kmers_grouped_count");
+        mf_ctx *ctx = ctx_of(e, a);
+        auto pkf = cptrs(kf), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni);
+        const string out = out_dir + "/kmers.groups.txt";
+        uint64_t c = 0;
+        logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
+        check(mf_kmers_grouped_count(ctx, pkf.data(), (int)pkf.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(), b, k,
+                                     out.c_str(), &c));
+        logmsg("INFO", "K-mers printed to %s", out.c_str());
     } else if (tool == "unique-kmers-multi") {
         // UniqueKmersMultipleSamplesFinder.java:84-185: the k-mers that enough input files hold and no filter file does
         check_k(k);

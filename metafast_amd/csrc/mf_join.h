@@ -1,8 +1,8 @@
 // mf_join.h -- the join core of the cohort tools ("the join core"; kernels and host helpers: mf_join.hip).
 // Every tool streams its samples, once per hash slice of the key space, into an HBM open-addressed union table of 16-byte slots and
 // reads the table out again.  A tool brings its union mode and per-sample `add` words, a projection for the read-out, and its own
-// post-pass: mf_stats.hip (stats-kmers, kmers-samples-counter), mf_kmersets.hip (unique-kmers-multi, kmers-multiple-filters),
-// mf_color.hip (kmers-color).
+// post-pass: mf_stats.hip (stats-kmers, stats-kmers-3, kmers-samples-counter, kmers-grouped-counter), mf_kmersets.hip
+// (unique-kmers-multi, kmers-multiple-filters), mf_color.hip (kmers-color).
 #pragma once
 #include "mf_common.h"
 #include <functional>
@@ -17,7 +17,7 @@ static constexpr uint32_t MF_UKM_KNOCKED = 0x80000000u;            // unique-kme
 struct mf_uslot { uint64_t key; uint32_t cnt; uint32_t row; };
 
 // What a sample's entry adds to its key's slot:
-//   MF_UNION_PRESENCE  `add` to the presence word (stats-kmers, kmers-samples-counter)
+//   MF_UNION_PRESENCE  `add` to the presence word (stats-kmers, stats-kmers-3, kmers-samples-counter, kmers-grouped-counter)
 //   MF_UNION_SUM       the entry's value to the second word and 1 to the first (unique-kmers-multi: two words, so that the sum's carry
 //                      never reaches the sample count; sum <= 32767 * 65535 < 2^31)
 //   MF_UNION_FIELD     the entry's value to the 16-bit field number `add` of the slot (kmers-multiple-filters: cd, uc, nonibd; each
