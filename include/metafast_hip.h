@@ -273,6 +273,26 @@ int  mf_comps_load(mf_ctx *ctx, const char *components_bin, mf_comps **out);
 /* One call = ComponentCutterMain.runImpl :92-108 */
 int  mf_cut_components(mf_ctx *ctx, mf_table *cutter, int k, int b1, int b2,
                        const char *components_bin, const char *stat_txt, uint64_t *n_comp);
+/* comp2seq (src/tools/ComponentsToSequences.java:41-76: bin2fasta, kmer-counter-many -b 0, seq-builder-many -b 0 -l k; mf_comp2seq.hip).
+ * split != 0: the contigs of every component by itself -- the unitigs (threshold 0, minimal length k) of the component's canonical
+ * k-mers, each weighted with its multiplicity in the component's member list, a neighbour counting only when it is a member of the SAME
+ * component; a k-mer that is a member of several components takes part in each.  All components are built in one pass.  split == 0: the
+ * unitigs of the one table of all members (count = multiplicity over all components).  k <= 31; components that were loaded from a
+ * file do not know their k: mf_comps_set_k states it (an error where the components know another one). */
+int  mf_comps_set_k(mf_comps *c, int k);
+int  mf_comps_unitigs_device(mf_ctx *ctx, mf_comps *c, int split, mf_seqs **out);
+/* The component index of every sequence, in the order of mf_seqs_export -- which, for these sequences, is (component, oriented start
+ * k-mer); all 0 where split was 0; an error for sequences of another producer.  *n (may be NULL) = the number of sequences; nothing
+ * is written when capacity is below it. */
+int  mf_seqs_components(const mf_seqs *s, uint32_t *comp, uint64_t capacity, uint64_t *n);
+/* File form, the reference's layout under out_dir (i = 1, 2, ... in the file's order; without split one file set, no suffix):
+ *   kmers_fasta/component[_<i>].fasta                       the members as the file lists them (BinaryToFasta.java:120-170)
+ *   kmer-counter-many/kmers/component[_<i>].kmers.bin       records as mf_table_write_kmers writes them, ascending k-mers
+ *   kmer-counter-many/stats/component[_<i>].stat.txt
+ *   seq-builder-many/sequences/component[_<i>].seq.fasta    as mf_seqs_write_fasta, numbered from 1 in every file
+ * Every component gets its four files.  *n_files = file sets written, *n_seqs = sequences in all (either may be NULL). */
+int  mf_comp2seq(mf_ctx *ctx, const char *components_bin, int k, int split, const char *out_dir,
+                 uint64_t *n_files, uint64_t *n_seqs);
 
 /* ---- A9-A11 on several GPUs: every rank owns a shard of the cutter table ---------------------
  * The cutter table and the components step join ALL samples (ComponentCutterMain.runImpl,

@@ -46,6 +46,7 @@ extern "C" int mf_kmers_grouped_count(mf_ctx *, const char *const *, int, const 
 extern "C" int mf_kmers_color(mf_ctx *, const char *const *, const int *, int, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
     __attribute__((weak));
+extern "C" int mf_comp2seq(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -887,6 +888,7 @@ static const char *TOOLS_TEXT =
     "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
     "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
     "component-colored\tExtract graph components from tangled graph based on k-mers coloring\n"
+    "comp2seq\t\tTransforms components in binary format to FASTA sequences (contigs)\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -967,6 +969,8 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
     } else if (tool == "component-colored") {
         v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("n_groups", a.get("n_groups", "3")), flag("separate"), flag("linear"),
              PV("n_comps", a.get("n_comps", "-1")), PV("perc", a.get("perc", "0.9")), PV::file("output-dir", a.get("output-dir", wd + "/colored-components"))};
+    } else if (tool == "comp2seq") {
+        v = {PV("k", a.get("k", "31")), opt_f("components-file"), flag("split")};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -992,7 +996,7 @@ int main(int argc, char **argv) {
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
                                   "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "kmers-grouped-counter"};
+                                  "stats-kmers-3", "kmers-grouped-counter", "comp2seq"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1047,7 +1051,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     unlink((wd + "/SUCCESS").c_str()); unlink((wd + "/out.properties").c_str());
-    const int k_dflt = tool == "matrix-builder" ? 31 : -1;
+    const int k_dflt = (tool == "matrix-builder" || tool == "comp2seq") ? 31 : -1;      // (ComponentsToSequences.java:21-26)
     int k = a.geti("k", k_dflt);
     vector<PV> outs;
 
@@ -1072,6 +1076,7 @@ int main(int argc, char **argv) {
     }
     else if (tool == "kmers-color") { need("k", "k"); need("k-mers", "kf"); if (!a.has("class")) die("Mandatory argument --class not set"); }
     else if (tool == "component-colored") { need("k", "k"); need("k-mers", "i"); }
+    else if (tool == "comp2seq") need("components-file", "cf");
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1372,6 +1377,23 @@ int main(int argc, char **argv) {
         }
         logmsg("INFO", "Total %s components were found", group_digits(total).c_str());
         outs = {PV::files("components-files", written)};
+    } else if (tool == "comp2seq") {
+        // ComponentsToSequences.java:41-76: bin2fasta, kmer-counter-many -b 0, seq-builder-many -b 0 -l k as sub-steps with the work
+        // directories kmers_fasta, kmer-counter-many and seq-builder-many -- here one segmented build of all components (mf_comp2seq)
+        check_k(k);
+        const bool split = a.get("split", "false") == "true";
+        const string cf = a.get("components-file");
+        if (!mf_comp2seq) die("comp2seq: this build of the library has no mf_comp2seq");
+        mf_ctx *ctx = ctx_of(e, a);
+        uint64_t nf = 0, ns = 0;
+        check(mf_comp2seq(ctx, cf.c_str(), k, split ? 1 : 0, wd.c_str(), &nf, &ns));
+        if (split) logmsg("INFO", "%s components loaded from %s", group_digits(nf).c_str(), cf.c_str());
+        logmsg("INFO", "%s sequences found", group_digits(ns).c_str());
+        if (ns == 0) logmsg("WARN", "No sequences were found! Perhaps you should decrease --min-seq-len or --maximal-bad-frequency values");
+        logmsg("INFO", "Sequences printed to %s", (wd + "/seq-builder-many/sequences").c_str());
+        vector<string> written;
+        for (uint64_t i = 0; i < nf; i++) written.push_back(wd + "/seq-builder-many/sequences/component" + (split ? "_" + std::to_string(i + 1) : string()) + ".seq.fasta");
+        outs = {PV::files("output-files", written)};
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

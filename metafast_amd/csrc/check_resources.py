@@ -7,10 +7,12 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags")
+# ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip)
+NO_LDS = re.compile(r"k_c2s_flags")
 # the translation units that hold those kernels: the guard must SEE them there (a renamed kernel, or a remark format that changed,
 # is a failed check, not a passed one)
-EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"]}
+EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"], "mf_comp2seq": ["k_c2s_flags"]}
 
 
 def main():
@@ -47,6 +49,8 @@ def main():
                     missing.append(f"{name}: no 'ScratchSize [bytes/lane]' remark was parsed")
                 elif sc != "0":
                     bad.append((name, sc))
+            if NO_LDS.search(name) and r.get("LDS Size [bytes/block]") != "0":
+                missing.append(f"{name}: {r.get('LDS Size [bytes/block]')} bytes of LDS per block, it is to use none")
     for want in EXPECT.get(unit, []):
         if not any(want in name for name in kernels):
             missing.append(f"{unit}: no resource record of a kernel named *{want}* (renamed? remark format changed?)")

@@ -240,6 +240,9 @@ struct mf_seqs {
     int32_t *d_avg = nullptr, *d_min = nullptr, *d_max = nullptr;
     uint64_t *d_startkey = nullptr;  // oriented start k-mer per sequence (for deterministic ordering)
     size_t bases_bytes = 0, offsets_bytes = 0, w_bytes = 0, sk_bytes = 0;
+    // optional (nullptr for every producer but mf_comps_unitigs_device, mf_comp2seq.hip): the component of each sequence, ids below
+    // n_groups -- the ordered export then sorts by (component, oriented start k-mer)
+    uint32_t *d_comp = nullptr; size_t comp_bytes = 0; uint64_t n_groups = 0;
 };
 struct mf_reads {                 // the reads of a list of files, as the readers hand them on (mf_reads_load)
     mf_ctx *ctx = nullptr;

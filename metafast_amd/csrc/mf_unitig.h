@@ -19,6 +19,8 @@ struct ut_arrays {
 // U2 .. U5 of mf_unitig.hip on a table of n good k-mers: `flags` launches the kernel(s) that fill A.info / A.ridx / A.lidx (/ A.pal) -- U1, the
 // only step that looks k-mers up --, everything after works on node ids.  d_part_off / part_bits: the table's minimizer partitions (0: none).
 // trace (may be nullptr; for the tests, mf_debug_unitigs): what the host saw on its way -- nothing is launched or copied for it.
+// d_row_group (may be nullptr; mf_comp2seq.hip): a group id per table entry -- every written path gets the id of its START node's entry
+// (mf_seqs::d_comp; the caller sets mf_seqs::n_groups).
 struct mf_ut_trace {
     uint64_t n_starts;        // start nodes (walks of U3)
     uint64_t walk_rounds;     // launches of k_ut_walk1
@@ -31,4 +33,8 @@ struct mf_ut_trace {
     uint64_t seg_slots;       // segment slots allocated (k_ut_seg_bound)
 };
 int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint16_t *gv, uint64_t n, int k, int part_bits, const uint64_t *d_part_off,
-                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out, mf_ut_trace *trace = nullptr);
+                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out, mf_ut_trace *trace = nullptr,
+                const uint32_t *d_row_group = nullptr);
+// the sequences in their output order on the host (mf_seqs_export); comp (may be nullptr): their component ids, where the sequences carry them
+int mf_seqs_to_host_grouped(const mf_seqs *s, std::vector<uint8_t> &bases, std::vector<uint64_t> &off, std::vector<int32_t> &avg, std::vector<int32_t> &mn,
+                            std::vector<int32_t> &mx, std::vector<uint32_t> *comp);

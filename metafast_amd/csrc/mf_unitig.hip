@@ -528,6 +528,11 @@ __global__ void k_ut_wfinal(ut_out O, const unsigned long long *__restrict__ wsu
     const uint64_t len = O.off[pid + 1] - O.off[pid];
     O.wavg[pid] = (int32_t)(wsum[pid] / (len - (uint64_t)k + 1));          // (int)(seqWeight / (len - k + 1)) :120-121
 }
+// the group of a written path = the group of its start node's table entry (mf_ut_build, d_row_group)
+__global__ void k_ut_path_group(const uint32_t *__restrict__ pstart, uint32_t np, const uint32_t *__restrict__ row_group, uint32_t *__restrict__ out) {
+    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid < np) out[pid] = row_group[pstart[pid] >> 1];
+}
 __global__ void k_fill_u32(uint32_t *p, uint64_t n, uint32_t v) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -537,7 +542,7 @@ __global__ void k_fill_u32(uint32_t *p, uint64_t n, uint32_t v) {
 static inline unsigned grid_for(uint64_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint16_t *gv, uint64_t n, int k, int part_bits, const uint64_t *d_part_off,
-                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out, mf_ut_trace *trace) {
+                int min_len, const std::function<int(const ut_arrays &)> &flags, mf_seqs **out, mf_ut_trace *trace, const uint32_t *d_row_group) {
     hipStream_t st = ctx->stream;
     if (trace) *trace = mf_ut_trace{};
     const bool wide = ghi != nullptr;
@@ -713,6 +718,11 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
         if (hipMemcpyAsync(&np, ctr.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
             rc = mf_set_error("unitigs: ends pass failed"); break;
         }
+        mf_buf<uint32_t> pgroup;
+        if (d_row_group) {
+            if ((rc = pgroup.alloc(ctx, np)) < 0) break;
+            if (np) k_ut_path_group<<<grid_for(np), 256, 0, st>>>(pstart.p, np, d_row_group, pgroup.p);
+        }
         ridx.reset(); lidx.reset(); end_node.reset(); end_dist.reset(); eqmin.reset(); starts.reset();
         // U5: walk the emitted paths again and write them out
         mf_buf<uint64_t> off, tot; mf_buf<int32_t> wmin, wmax, wavg;
@@ -780,6 +790,7 @@ int mf_ut_build(mf_ctx *ctx, const uint64_t *gk, const uint64_t *ghi, const uint
         S->w_bytes = wavg.bytes();
         S->d_avg = wavg.take(); S->d_min = wmin.take(); S->d_max = wmax.take();
         S->sk_bytes = pkey.bytes(); S->d_startkey = pkey.take();
+        if (d_row_group) { S->comp_bytes = pgroup.bytes(); S->d_comp = pgroup.take(); }
     } while (0);
     if (rc < 0) { delete S; return rc; }
     *out = S;
@@ -991,6 +1002,7 @@ extern "C" void mf_seqs_destroy(mf_seqs *s) {
     if (s->d_min) mf_release(s->ctx, s->d_min, s->w_bytes);
     if (s->d_max) mf_release(s->ctx, s->d_max, s->w_bytes);
     if (s->d_startkey) mf_release(s->ctx, s->d_startkey, s->sk_bytes);
+    if (s->d_comp) mf_release(s->ctx, s->d_comp, s->comp_bytes);
     delete s;
 }
 extern "C" int mf_seqs_stats(const mf_seqs *s, uint64_t *n_seqs, uint64_t *total_len) {
@@ -1035,20 +1047,44 @@ __global__ __launch_bounds__(256) void k_seq_gather(const uint32_t *__restrict__
     const uint64_t src = off[j], len = off[j + 1] - src, dst = noff[i];
     for (uint64_t t = threadIdx.x & 63u; t < len; t += 64) out[dst + t] = bases[src + t];
 }
-int mf_seqs_to_host(const mf_seqs *s, std::vector<uint8_t> &bases, std::vector<uint64_t> &off, std::vector<int32_t> &avg,
-                    std::vector<int32_t> &mn, std::vector<int32_t> &mx) {
+__global__ void k_seq_gather_u32(const uint32_t *__restrict__ order, const uint32_t *__restrict__ v, uint64_t n, uint32_t *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = v[order[i]];
+}
+// order[i] = the sequence that comes i-th: ascending oriented start k-mer -- and, where the sequences carry component ids, ascending component first
+// (two stable passes); comp (then, may be nullptr): the component ids in that order
+static int seqs_order(const mf_seqs *s, mf_buf<uint32_t> &order, mf_buf<uint32_t> *comp) {
+    mf_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t n = s->n;
+    mf_buf<uint32_t> idx; mf_buf<uint64_t> skey;
+    MF_TRY(idx.alloc(ctx, n)); MF_TRY(order.alloc(ctx, n)); MF_TRY(skey.alloc(ctx, n));
+    k_seq_iota<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(idx.p, n);
+    MF_TRY(mf_sort_u64_u32(ctx, s->d_startkey, idx.p, n, 64, skey.p, order.p));
+    if (!s->d_comp) return MF_OK;
+    mf_buf<uint32_t> ck, ck2, ord2;
+    MF_TRY(ck.alloc(ctx, n)); MF_TRY(ck2.alloc(ctx, n)); MF_TRY(ord2.alloc(ctx, n));
+    k_seq_gather_u32<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(order.p, s->d_comp, n, ck.p);
+    int cb = 1; while (cb < 32 && (1ull << cb) < s->n_groups) cb++;
+    MF_TRY(mf_sort_u32_pairs(ctx, ck.p, order.p, n, cb, ck2.p, ord2.p));
+    order.swap(ord2);
+    if (comp) comp->swap(ck2);
+    return MF_OK;
+}
+int mf_seqs_to_host_grouped(const mf_seqs *s, std::vector<uint8_t> &bases, std::vector<uint64_t> &off, std::vector<int32_t> &avg, std::vector<int32_t> &mn,
+                            std::vector<int32_t> &mx, std::vector<uint32_t> *comp) {
     mf_ctx *ctx = s->ctx;
     MF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t n = s->n;
     bases.resize(s->n_bases); off.assign(n + 1, 0); avg.resize(n); mn.resize(n); mx.resize(n);
+    if (comp) comp->assign(s->d_comp ? n : 0, 0u);
     if (!n) return MF_OK;
     if (n >= (1ull << 32)) return mf_set_error("sequences: more than 2^32 is not supported");
-    mf_buf<uint32_t> idx, order, len; mf_buf<uint64_t> skey, noff, tot; mf_buf<int32_t> oa, omn, omx; mf_buf<uint8_t> ob;
-    MF_TRY(idx.alloc(ctx, n)); MF_TRY(order.alloc(ctx, n)); MF_TRY(len.alloc(ctx, n)); MF_TRY(skey.alloc(ctx, n)); MF_TRY(noff.alloc(ctx, n + 1)); MF_TRY(tot.alloc(ctx, 1));
+    mf_buf<uint32_t> order, len, oc; mf_buf<uint64_t> noff, tot; mf_buf<int32_t> oa, omn, omx; mf_buf<uint8_t> ob;
+    MF_TRY(len.alloc(ctx, n)); MF_TRY(noff.alloc(ctx, n + 1)); MF_TRY(tot.alloc(ctx, 1));
     MF_TRY(oa.alloc(ctx, n)); MF_TRY(omn.alloc(ctx, n)); MF_TRY(omx.alloc(ctx, n)); MF_TRY(ob.alloc(ctx, s->n_bases + 1));
-    k_seq_iota<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(idx.p, n);
-    MF_TRY(mf_sort_u64_u32(ctx, s->d_startkey, idx.p, n, 64, skey.p, order.p));
+    MF_TRY(seqs_order(s, order, comp ? &oc : nullptr));
     k_seq_ordered_meta<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(order.p, s->d_offsets, s->d_avg, s->d_min, s->d_max, n, len.p, oa.p, omn.p, omx.p);
     MF_TRY(mf_scan<1>(ctx, len.p, noff.p, n, tot.p));
     k_seq_gather<<<(unsigned)((n * 64 + 255) / 256), 256, 0, st>>>(order.p, s->d_offsets, noff.p, s->d_bases, n, ob.p);
@@ -1057,7 +1093,26 @@ int mf_seqs_to_host(const mf_seqs *s, std::vector<uint8_t> &bases, std::vector<u
     MF_HIP(hipMemcpyAsync(avg.data(), oa.p, n * 4, hipMemcpyDeviceToHost, st));
     MF_HIP(hipMemcpyAsync(mn.data(), omn.p, n * 4, hipMemcpyDeviceToHost, st));
     MF_HIP(hipMemcpyAsync(mx.data(), omx.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (comp && s->d_comp) MF_HIP(hipMemcpyAsync(comp->data(), oc.p, n * 4, hipMemcpyDeviceToHost, st));
     MF_HIP(hipStreamSynchronize(st));
+    return MF_OK;
+}
+int mf_seqs_to_host(const mf_seqs *s, std::vector<uint8_t> &bases, std::vector<uint64_t> &off, std::vector<int32_t> &avg,
+                    std::vector<int32_t> &mn, std::vector<int32_t> &mx) {
+    return mf_seqs_to_host_grouped(s, bases, off, avg, mn, mx, nullptr);
+}
+// the component of every sequence in export order (mf_comps_unitigs_device)
+extern "C" int mf_seqs_components(const mf_seqs *s, uint32_t *comp, uint64_t capacity, uint64_t *n) {
+    if (!s) return mf_set_error("seqs is NULL");
+    if (!s->d_comp) return mf_set_error("mf_seqs_components: these sequences carry no component ids (they do not come from mf_comps_unitigs_device)");
+    if (n) *n = s->n;
+    if (!comp || capacity < s->n || !s->n) return MF_OK;
+    mf_ctx *ctx = s->ctx;
+    MF_HIP(hipSetDevice(ctx->device));
+    mf_buf<uint32_t> order, oc;
+    MF_TRY(seqs_order(s, order, &oc));
+    MF_HIP(hipMemcpyAsync(comp, oc.p, s->n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
     return MF_OK;
 }
 extern "C" int mf_seqs_export(const mf_seqs *s, uint8_t *bases, uint64_t *offsets, int32_t *avg, int32_t *mn, int32_t *mx) {

@@ -120,6 +120,10 @@ _SIGS = {
     "mf_comps_write": (i32, [vp, cp, cp]),
     "mf_comps_load": (i32, [vp, cp, pvp]),
     "mf_cut_components": (i32, [vp, vp, i32, i32, i32, cp, cp, pu64]),
+    "mf_comps_set_k": (i32, [vp, i32]),
+    "mf_comps_unitigs_device": (i32, [vp, vp, i32, pvp]),
+    "mf_seqs_components": (i32, [vp, vp, u64, pu64]),
+    "mf_comp2seq": (i32, [vp, cp, i32, i32, cp, pu64, pu64]),
     "mf_features_device": (i32, [vp, vp, vp, i32, vp, vp]),
     "mf_features_reads_device": (i32, [vp, vp, vp, vp, u64, u64, i32, i32, vp, vp]),
     "mf_features_reads": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, cp, cp]),
@@ -423,6 +427,24 @@ class Context:
         c = C.c_void_p()
         _check(lib().mf_comps_load(self.h, os.fsencode(path), C.byref(c)))
         return Comps(self, c)
+
+    # ---- comp2seq ----
+    def comps_unitigs(self, comps, split=True, k=None):
+        """The contigs of the components (ComponentsToSequences.java:41-76), all components in one build.  split: every component by
+        itself; else the one table of all members.  k: for components that were loaded from a file (they do not know theirs).
+        -> (Seqs, uint32 array: the component index of every sequence in export order -- all 0 without split)"""
+        if k is not None:
+            _check(lib().mf_comps_set_k(comps.h, k))
+        s = C.c_void_p()
+        _check(lib().mf_comps_unitigs_device(self.h, comps.h, 1 if split else 0, C.byref(s)))
+        seqs = Seqs(self, s)
+        return seqs, seqs.components()
+
+    def comp2seq(self, components_bin, k, out_dir, split=False):
+        """File form: kmers_fasta/, kmer-counter-many/{kmers,stats}/, seq-builder-many/sequences/ under out_dir -> (file sets, sequences)"""
+        nf, ns = C.c_uint64(), C.c_uint64()
+        _check(lib().mf_comp2seq(self.h, os.fsencode(components_bin), k, 1 if split else 0, os.fsencode(out_dir), C.byref(nf), C.byref(ns)))
+        return nf.value, ns.value
 
     # ---- A12 ----
     def features(self, comps, sample_table, threshold=0, selected=None):
@@ -1055,6 +1077,14 @@ class Seqs:
 
     def write_fasta(self, path):
         _check(lib().mf_seqs_write_fasta(self.h, os.fsencode(path)))
+
+    def components(self):
+        """the component index of every sequence in export order (sequences of Context.comps_unitigs only)"""
+        n = self.stats()[0]
+        comp = np.zeros(n, dtype=np.uint32)
+        m = C.c_uint64()
+        _check(lib().mf_seqs_components(self.h, comp.ctypes.data if n else None, n, C.byref(m)))
+        return comp
 
 
 class Comps:
