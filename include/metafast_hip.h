@@ -519,6 +519,35 @@ int mf_kmers_grouped_count(mf_ctx *ctx, const char *const *kmers_files, int n_km
                            const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
                            const char *out_txt, uint64_t *n_kmers);
 
+/* KmersPerSampleCounter.runImpl (src/tools/KmersPerSampleCounter.java:56-157; mf_kps.hip): the k-mer x sample abundance table of a cohort.
+ * n(x) = the number of samples j >= 1 whose count of x is > max_bad -- sample 0 is NOT counted (count_first = 0, the reference: its first
+ * file's map is the accumulator and is zeroed before it is iterated, :82-96; count_first != 0 counts it like the others); a k-mer that
+ * only sample 0 holds has n = 0 and is still a candidate.  Selected: n(x) >= thresh = n * percent / 100 in Java int arithmetic
+ * (truncation toward zero; percent may be negative or above 100), so thresh <= 0 selects the whole union.  The result holds the M
+ * selected k-mers in ASCENDING order (the reference's order is its hash map's), their n(x), and the n x M row-major matrix of the
+ * samples' counts (0 = absent or count <= max_bad).  Errors: n < 1 or n > 32767, a key >= 2^62, 2^32 - 1 or more selected k-mers, more
+ * than 2^32 - 1 union k-mers in one hash slice, and a matrix of n x M x 2 bytes that does not fit the free device memory (select fewer
+ * k-mers with a higher percent, or use the file form). */
+typedef struct mf_kps mf_kps;
+int  mf_kmers_per_sample_tables(mf_ctx *ctx, mf_table *const *tables, int n, int max_bad, int percent, int count_first, mf_kps **out);
+void mf_kps_destroy(mf_kps *r);
+int  mf_kps_stats(const mf_kps *r, uint64_t *n_kmers, int *n_samples);                 /* either may be NULL */
+/* device pointers, valid until the destroy: uint64 keys[M], uint16 n(x)[M], uint16 matrix[n][M]; any may be NULL */
+int  mf_kps_device_view(const mf_kps *r, const void **d_keys, const void **d_nsamples, const void **d_matrix);
+/* host copies: keys[M], nsamples[M], matrix[n * M]; any may be NULL */
+int  mf_kps_export(const mf_kps *r, uint64_t *keys, uint16_t *nsamples, uint16_t *matrix);
+/* The text of the reference's file, formatted on the device: the first line without its newline ("\t" + ShortKmer.toString at this k per
+ * selected k-mer, M * (k + 1) bytes) and one sample's line without name and newline ("\t" + decimal count per selected k-mer, at most
+ * 6 M bytes).  *n = the bytes of the text, whatever cap is; nothing is written when cap is below it. */
+int  mf_kps_header_text(const mf_kps *r, int k, uint8_t *text, uint64_t cap, uint64_t *n);
+int  mf_kps_row_text(const mf_kps *r, int sample, uint8_t *text, uint64_t cap, uint64_t *n);
+/* File form, max_bad = 0 (every load is IOUtils.loadKmers(file, 0): records with a value > 0, duplicate records of a k-mer summed with
+ * saturation) -> out_txt (selected_kmers_<percent>.txt): the line of k-mers, then one line per file in argument order -- the file's name
+ * with every ".kmers.bin" removed, then "\t" + count per selected k-mer.  Streams: a sample is loaded, gathered, formatted and written
+ * before the next, the matrix is never resident and every file is read twice.  1 <= k <= 31; *n_kmers (may be NULL) = M. */
+int  mf_kmers_per_sample(mf_ctx *ctx, const char *const *files, int n, int k, int percent, int count_first, const char *out_txt,
+                         uint64_t *n_kmers);
+
 /* ---- set operations over cohorts on the same join (pipelines 2 and 3 of the reference's Pipelines.md; mf_kmersets.hip) -------------
  * Keys, slices and result tables as above; b = max_bad >= 0 (a negative one is an error); the counts of the tables are 1 .. MF_MAX_COUNT.
  *

@@ -43,6 +43,7 @@ extern "C" int mf_stats_kmers3(mf_ctx *, const char *const *, int, const char *c
                                uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_grouped_count(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int, int,
                                       int, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_per_sample(mf_ctx *, const char *const *, int, int, int, int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_color(mf_ctx *, const char *const *, const int *, int, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
     __attribute__((weak));
@@ -165,7 +166,7 @@ static const OptDef OPTS[] = {
     {"nonibd-filter-kmers", "nonibd", true, false}, {"c-kmers", "C", true, false},
     {"cd-kmers", "cd", true, false}, {"uc-kmers", "uc", true, false}, {"nonibd-kmers", "nonibd", true, false},
     {"class", "", false, false}, {"val", "val", false, true}, {"n_groups", "group", false, false}, {"separate", "", false, true},
-    {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false},
+    {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false}, {"percent-present", "perc", false, false},
 };
 // `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
@@ -177,7 +178,7 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
         if (s == "i") {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
             if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored") return "k-mers";
+                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample") return "k-mers";
             if (tool == "component-cutter") return "sequences";
             return "reads";
         }
@@ -193,6 +194,7 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
             if (s == "nonibd") return "nonibd-kmers";
         }
         if (s == "cf") return "components-file";                           // ViewMain.java:45, BinaryToFasta.java:47
+        if (s == "perc") return tool == "kmers-per-sample" ? "percent-present" : "";   // KmersPerSampleCounter.java:43-48 (component-colored: --perc only)
         for (auto &o : OPTS) if (o.sht[0] && s == o.sht) return o.lng;
         return "";
     };
@@ -884,6 +886,7 @@ static const char *TOOLS_TEXT =
     "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
     "stats-kmers-3\t\tFind k-mers that differ significantly between three groups of samples (chi-squared + Mann-Whitney)\n"
     "kmers-grouped-counter\tCount number of samples from 3 groups containing specified k-mers\n"
+    "kmers-per-sample\tCounts the abundance of frequent k-mers from dataset in each sample\n"
     "unique-kmers-multi\tOutput k-mers present in one dataset in fixed number of samples and missing in other\n"
     "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
     "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
@@ -953,6 +956,9 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
         v = {opt_i("k"), PV::files("kmers-file", a.list("kmers-file")), PV::files("cd-kmers", a.list("cd-kmers")), PV::files("uc-kmers", a.list("uc-kmers")),
              PV::files("nonibd-kmers", a.list("nonibd-kmers")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
              PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
+    } else if (tool == "kmers-per-sample") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("percent-present", a.get("percent-present", "20")),
+             PV::file("output-dir", a.get("output-dir", wd + "/kmers_per_samples"))};
     } else if (tool == "unique-kmers-multi") {
         v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
              PV("min-samples", a.get("min-samples", "1")), PV("max-samples", a.get("max-samples", "1")),
@@ -996,7 +1002,7 @@ int main(int argc, char **argv) {
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
                                   "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "kmers-grouped-counter", "comp2seq"};
+                                  "stats-kmers-3", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1070,6 +1076,7 @@ int main(int argc, char **argv) {
     else if (tool == "stats-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
     else if (tool == "stats-kmers-3") { need("a-kmers", "A"); need("b-kmers", "B"); need("c-kmers", "C"); }
     else if (tool == "kmers-grouped-counter") { need("k", "k"); need("cd-kmers", "cd"); need("uc-kmers", "uc"); need("nonibd-kmers", "nonibd"); }
+    else if (tool == "kmers-per-sample") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "unique-kmers-multi") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
     else if (tool == "kmers-multiple-filters") {
         need("k", "k"); need("k-mers", "i"); need("cd-filter-kmers", "cd"); need("uc-filter-kmers", "uc"); need("nonibd-filter-kmers", "nonibd");
@@ -1242,6 +1249,24 @@ int main(int argc, char **argv) {
         logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
         check(mf_kmers_grouped_count(ctx, pkf.data(), (int)pkf.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(), b, k,
                                      out.c_str(), &c));
+        logmsg("INFO", "K-mers printed to %s", out.c_str());
+    } else if (tool == "kmers-per-sample") {
+        // KmersPerSampleCounter.java:56-157: the abundance in every file of the k-mers that enough files hold (no -b: every load is at 0).
+        // The first file is not counted, as in the reference (:82-96): count_first = 0.
+        check_k(k);
+        const int perc = a.geti("percent-present", 20);
+        const string out_dir = a.get("output-dir", wd + "/kmers_per_samples");
+        const vector<string> files = a.list("k-mers");
+        mkdirs(out_dir);
+        if (!mf_kmers_per_sample) die("kmers-per-sample: this build of the library has no mf_kmers_per_sample");
+        mf_ctx *ctx = ctx_of(e, a);
+        auto fp = cptrs(files);
+        const string out = out_dir + "/selected_kmers_" + std::to_string(perc) + ".txt";
+        uint64_t c = 0;
+        logmsg("INFO", "Loading all k-mers...");
+        logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
+        check(mf_kmers_per_sample(ctx, fp.data(), (int)fp.size(), k, perc, 0, out.c_str(), &c));
+        logmsg("DEBUG", "Selected k-mers = %s", group_digits(c).c_str());
         logmsg("INFO", "K-mers printed to %s", out.c_str());
     } else if (tool == "unique-kmers-multi") {
         // UniqueKmersMultipleSamplesFinder.java:84-185: the k-mers that enough input files hold and no filter file does

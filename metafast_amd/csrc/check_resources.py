@@ -7,12 +7,14 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags")
-# ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip)
-NO_LDS = re.compile(r"k_c2s_flags")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_")
+# ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
+# column or value: mf_kps.hip)
+NO_LDS = re.compile(r"k_c2s_flags|k_kps_")
 # the translation units that hold those kernels: the guard must SEE them there (a renamed kernel, or a remark format that changed,
 # is a failed check, not a passed one)
-EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"], "mf_comp2seq": ["k_c2s_flags"]}
+EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"], "mf_comp2seq": ["k_c2s_flags"],
+          "mf_kps": ["k_kps_index", "k_kps_gather", "k_kps_header", "k_kps_widths", "k_kps_format"]}
 
 
 def main():

@@ -99,6 +99,7 @@ struct mf_ctx {
     int64_t opt_cc_sparse = 1;     // component cutter: threshold levels that few vertices reach run on a list of them (0: every level visits all vertices)
     int64_t opt_dcc_sparse = 0;    // sharded cutter, levels after the first: 1 = always the sparse set-up of the arrays over all vertex ids (tests)
     int64_t opt_stats_slices = 0;  // multi-sample join (mf_join.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
+    int64_t opt_kps_matrix_bytes = 0;  // kmers-per-sample, tables form: the samples x k-mers count matrix may take this many bytes (0 = what is free in HBM; tests: a small number)
     // ... the count for k = 32..63
     int64_t opt_wide_skm = 1;      // mf_count_wide_device: super-k-mer records + LDS tables (mf_wskm.hip) instead of sorting every occurrence (0: the sort path, mf_wide.hip)
     int64_t opt_wide_skm_min = 1 << 20;     // ... from this many k-mer occurrences on (tests: 1)

@@ -174,7 +174,7 @@ static const struct { const char *name; int64_t mf_ctx::*field; int64_t lo = OPT
     {"stream_count_piece_bytes", &mf_ctx::opt_stream_count_piece}, {"stream_count_test_pct", &mf_ctx::opt_stream_count_test_pct},
     {"nbr_global", &mf_ctx::opt_nbr_global}, {"ut_double_after", &mf_ctx::opt_ut_double_after, 1, 64}, {"ut_plain_rounds", &mf_ctx::opt_ut_plain_rounds},
     {"cc_compress", &mf_ctx::opt_cc_compress}, {"cc_sparse", &mf_ctx::opt_cc_sparse}, {"dcc_sparse", &mf_ctx::opt_dcc_sparse},
-    {"stats_slices", &mf_ctx::opt_stats_slices, 0, 4096},
+    {"stats_slices", &mf_ctx::opt_stats_slices, 0, 4096}, {"kps_matrix_bytes", &mf_ctx::opt_kps_matrix_bytes, 0},
     {"wide_skm", &mf_ctx::opt_wide_skm}, {"wide_skm_min", &mf_ctx::opt_wide_skm_min}, {"wide_skm_lazy_order", &mf_ctx::opt_wide_skm_lazy_order},
     {"wide_skm_fine", &mf_ctx::opt_wide_skm_fine}, {"wide_skm_pack", &mf_ctx::opt_wide_skm_pack}, {"wide_skm_merge", &mf_ctx::opt_wide_skm_merge},
     {"wide_skm_lead", &mf_ctx::opt_wide_skm_lead}, {"wide_skm_unit", &mf_ctx::opt_wide_skm_unit},

@@ -2,7 +2,7 @@
 // Every tool streams its samples, once per hash slice of the key space, into an HBM open-addressed union table of 16-byte slots and
 // reads the table out again.  A tool brings its union mode and per-sample `add` words, a projection for the read-out, and its own
 // post-pass: mf_stats.hip (stats-kmers, stats-kmers-3, kmers-samples-counter, kmers-grouped-counter), mf_kmersets.hip
-// (unique-kmers-multi, kmers-multiple-filters), mf_color.hip (kmers-color).
+// (unique-kmers-multi, kmers-multiple-filters), mf_color.hip (kmers-color), mf_kps.hip (kmers-per-sample).
 #pragma once
 #include "mf_common.h"
 #include <functional>
@@ -61,6 +61,14 @@ struct mf_read_nsamples {          // kmers-samples-counter: every entry -> numb
     static constexpr bool all = true;
     static constexpr const char *tool = "kmers-samples-counter", *timer = "k_stats_nsamples";
     __device__ __forceinline__ bool keep(ulonglong2) const { return true; }
+    __device__ __forceinline__ value val(ulonglong2 raw) const { return (uint16_t)raw.y; }
+};
+struct mf_read_kps {               // kmers-per-sample: (int)count >= thresh -> the count (thresh may be <= 0: every entry, the ones with count 0 included)
+    using value = uint16_t;
+    static constexpr bool all = false;
+    static constexpr const char *tool = "kmers-per-sample", *timer = "k_kps_select";
+    int thresh;
+    __device__ __forceinline__ bool keep(ulonglong2 raw) const { return (int)(uint32_t)raw.y >= thresh; }
     __device__ __forceinline__ value val(ulonglong2 raw) const { return (uint16_t)raw.y; }
 };
 struct mf_read_color {             // kmers-color: every entry -> packed value

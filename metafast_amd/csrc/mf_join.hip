@@ -186,6 +186,7 @@ int mf_join_read(mf_ctx *ctx, const mf_uslot *slots, uint64_t cap, uint64_t nu, 
     return MF_OK;
 }
 template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_nsamples &, mf_join_parts<uint64_t, uint16_t> &);
+template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_kps &, mf_join_parts<uint64_t, uint16_t> &);
 template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_color &, mf_join_parts<uint64_t, uint64_t> &);
 template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_ukm &, mf_join_parts<uint64_t, uint32_t> &);
 

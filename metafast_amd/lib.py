@@ -155,6 +155,14 @@ _SIGS = {
     "mf_stats_kmers3": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, C.c_double, C.c_double, cp, vp]),
     "mf_kmers_grouped_count_tables": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, u64, pu64]),
     "mf_kmers_grouped_count": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, cp, pu64]),
+    "mf_kmers_per_sample_tables": (i32, [vp, vp, i32, i32, i32, i32, pvp]),
+    "mf_kps_destroy": (None, [vp]),
+    "mf_kps_stats": (i32, [vp, pu64, C.POINTER(C.c_int)]),
+    "mf_kps_device_view": (i32, [vp, pvp, pvp, pvp]),
+    "mf_kps_export": (i32, [vp, vp, vp, vp]),
+    "mf_kps_header_text": (i32, [vp, i32, vp, u64, pu64]),
+    "mf_kps_row_text": (i32, [vp, i32, vp, u64, pu64]),
+    "mf_kmers_per_sample": (i32, [vp, C.POINTER(cp), i32, i32, i32, i32, cp, pu64]),
     "mf_unique_kmers_multi_tables": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, C.POINTER(C.c_int), pu64, vp]),
     "mf_unique_kmers_multi": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, i32, i32, cp, C.POINTER(C.c_int), pu64, vp]),
     "mf_kmers_multiple_filters_tables": (i32, [vp, vp, vp, vp, vp, i32, pvp, vp, vp, u64, pu64, vp]),
@@ -544,6 +552,21 @@ class Context:
                                             len(uc_files), _cfiles(nonibd_files), len(nonibd_files), max_bad, k, os.fsencode(out_txt), C.byref(n)))
         return n.value
 
+    def kmers_per_sample(self, tables, percent=20, max_bad=0, count_first=False):
+        """KmersPerSampleCounter (src/tools/KmersPerSampleCounter.java:56-157) on resident tables -> KmersPerSample: the k-mers that at
+        least len(tables) * percent / 100 (Java int arithmetic) of the samples hold with a count > max_bad, in ascending order, and every
+        sample's count of each.  count_first = False is the reference: the first sample is not counted."""
+        h = (C.c_void_p * max(len(tables), 1))(*[t.h for t in tables])
+        r = C.c_void_p()
+        _check(lib().mf_kmers_per_sample_tables(self.h, h, len(tables), max_bad, percent, 1 if count_first else 0, C.byref(r)))
+        return KmersPerSample(self, r)
+
+    def kmers_per_sample_files(self, files, k, out_txt, percent=20, count_first=False):
+        """the same from .kmers.bin files, streamed -> out_txt (selected_kmers_<percent>.txt); returns the number of selected k-mers"""
+        n = C.c_uint64()
+        _check(lib().mf_kmers_per_sample(self.h, _cfiles(files), len(files), k, percent, 1 if count_first else 0, os.fsencode(out_txt), C.byref(n)))
+        return n.value
+
     @staticmethod
     def _ukm_slots(n_inputs, min_samples, max_samples):
         return max(1, min(max_samples, max(min_samples, n_inputs + 1)) - min_samples + 1)
@@ -898,6 +921,58 @@ class WideComps:
         off = np.zeros(n + 1, dtype=np.uint64); hi = np.zeros(nk, dtype=np.uint64); lo = np.zeros(nk, dtype=np.uint64)
         _check(lib().mf_wcomps_export(self.h, sizes.ctypes.data, weights.ctypes.data, thr.ctypes.data, off.ctypes.data, hi.ctypes.data, lo.ctypes.data))
         return dict(sizes=sizes, weights=weights, thr=thr, offsets=off, hi=hi, lo=lo)
+
+
+class KmersPerSample:
+    """the result of Context.kmers_per_sample: M selected k-mers x N samples, resident in HBM"""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None and self.ctx.h:
+            _lib.mf_kps_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def shape(self):
+        """(samples, selected k-mers)"""
+        m, n = C.c_uint64(), C.c_int()
+        _check(lib().mf_kps_stats(self.h, C.byref(m), C.byref(n)))
+        return n.value, m.value
+
+    def device_view(self):
+        """device pointers (keys uint64[M], n(x) uint16[M], matrix uint16[N][M])"""
+        k, s, m = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().mf_kps_device_view(self.h, C.byref(k), C.byref(s), C.byref(m)))
+        return k.value, s.value, m.value
+
+    def export(self):
+        """-> (keys uint64[M] ascending, n(x) uint16[M], matrix uint16[N][M])"""
+        n, m = self.shape()
+        keys, ns, mat = np.zeros(m, np.uint64), np.zeros(m, np.uint16), np.zeros((n, m), np.uint16)
+        _check(lib().mf_kps_export(self.h, keys.ctypes.data, ns.ctypes.data, mat.ctypes.data))
+        return keys, ns, mat
+
+    def _text(self, fn, arg, cap):
+        buf = np.zeros(max(cap, 1), np.uint8)
+        n = C.c_uint64()
+        _check(fn(self.h, arg, buf.ctypes.data, cap, C.byref(n)))
+        assert n.value <= cap
+        return buf[:n.value].tobytes()
+
+    def header_text(self, k):
+        """the file's first line without its newline, formatted on the device"""
+        return self._text(lib().mf_kps_header_text, k, self.shape()[1] * (k + 1))
+
+    def row_text(self, sample):
+        """sample's line without the name and the newline, formatted on the device"""
+        return self._text(lib().mf_kps_row_text, sample, self.shape()[1] * 6)
 
 
 class Table:
