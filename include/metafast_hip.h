@@ -293,6 +293,28 @@ int  mf_seqs_components(const mf_seqs *s, uint32_t *comp, uint64_t capacity, uin
  * Every component gets its four files.  *n_files = file sets written, *n_seqs = sequences in all (either may be NULL). */
 int  mf_comp2seq(mf_ctx *ctx, const char *components_bin, int k, int split, const char *out_dir,
                  uint64_t *n_files, uint64_t *n_seqs);
+/* comp2graph (src/tools/ComponentsToGraph.java:70-130, src/algo/Comp2Graph.java, src/io/GFAWriter.java; mf_comp2graph.hip): the compacted
+ * de Bruijn graph of every component as GFA text, all components in one pass.  Per component all S lines, then all L lines; components
+ * in their order, an empty one contributes nothing.  A segment is a maximal path whose inner links are the only way out of one k-mer and
+ * the only way into the next, inside the component; it is printed on the strand that is not above its reverse complement in string
+ * order (LN = its bases, KC = the values of its k-mers + (k - 1) x the value of the printed strand's last k-mer).  L lines as
+ * GFAWriter.printEdge: every adjacency from both sides.  Where the reference's names follow the iteration order of a hash map, these are
+ * fixed: segment <n>_i<c>, c = the component's position, n = 1, 2, ... inside the component -- paths (walked from the end whose
+ * canonical k-mer is smaller) ascending by (canonical start k-mer, strand of the start k-mer as walked: canonical first),
+ * then isolated cycles, each opened at its smallest canonical k-mer (numeric order of the 2-bit code A0 G1 C2 T3) on that k-mer's
+ * canonical strand, with a link from its end to its start; L lines ascending by (from, from sign, to, to sign), '+' before '-'.
+ * Values: no samples -- every k-mer 1; coverage == 0 -- the number of samples that hold the k-mer; coverage != 0 -- its summed count over
+ * the samples, bounded at 32767 (IOUtils.loadKmers, threshold 0).  k <= 31 (mf_comps_set_k for components loaded from a file). */
+typedef struct mf_gfa mf_gfa;
+int  mf_comps_graph_device(mf_ctx *ctx, mf_comps *c, mf_table *const *samples, int n_samples, int coverage, mf_gfa **out);
+void mf_gfa_destroy(mf_gfa *g);
+/* any may be NULL: segments (a palindromic k-mer's two S lines count once), L lines, opened cycles, bytes of text */
+int  mf_gfa_stats(const mf_gfa *g, uint64_t *n_segments, uint64_t *n_links, uint64_t *n_cycles, uint64_t *n_bytes);
+/* *n (may be NULL) = the bytes of the text, whatever cap is; nothing is written when cap is below it */
+int  mf_gfa_text(const mf_gfa *g, uint8_t *text, uint64_t cap, uint64_t *n);
+/* File form: components_bin + optional .kmers.bin files (one resident at a time) -> out_gfa.  The counts may be NULL. */
+int  mf_comp2graph(mf_ctx *ctx, const char *components_bin, int k, const char *const *kmers_files, int n_files, int coverage,
+                   const char *out_gfa, uint64_t *n_components, uint64_t *n_segments, uint64_t *n_links);
 
 /* ---- A9-A11 on several GPUs: every rank owns a shard of the cutter table ---------------------
  * The cutter table and the components step join ALL samples (ComponentCutterMain.runImpl,

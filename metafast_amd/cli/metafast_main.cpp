@@ -48,6 +48,7 @@ extern "C" int mf_kmers_color(mf_ctx *, const char *const *, const int *, int, i
 extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
     __attribute__((weak));
 extern "C" int mf_comp2seq(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_comp2graph(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -167,6 +168,7 @@ static const OptDef OPTS[] = {
     {"cd-kmers", "cd", true, false}, {"uc-kmers", "uc", true, false}, {"nonibd-kmers", "nonibd", true, false},
     {"class", "", false, false}, {"val", "val", false, true}, {"n_groups", "group", false, false}, {"separate", "", false, true},
     {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false}, {"percent-present", "perc", false, false},
+    {"coverage", "cov", false, true}, {"graph-file", "", false, false},
 };
 // `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
@@ -178,7 +180,7 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
         if (s == "i") {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
             if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample") return "k-mers";
+                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample" || tool == "comp2graph") return "k-mers";
             if (tool == "component-cutter") return "sequences";
             return "reads";
         }
@@ -892,6 +894,7 @@ static const char *TOOLS_TEXT =
     "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
     "component-colored\tExtract graph components from tangled graph based on k-mers coloring\n"
     "comp2seq\t\tTransforms components in binary format to FASTA sequences (contigs)\n"
+    "comp2graph\t\tTransforms components in binary format to de Bruijn graph in GFA format\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -977,6 +980,9 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
              PV("n_comps", a.get("n_comps", "-1")), PV("perc", a.get("perc", "0.9")), PV::file("output-dir", a.get("output-dir", wd + "/colored-components"))};
     } else if (tool == "comp2seq") {
         v = {PV("k", a.get("k", "31")), opt_f("components-file"), flag("split")};
+    } else if (tool == "comp2graph") {
+        v = {opt_i("k"), opt_f("components-file"), a.has("k-mers") ? PV::files("k-mers", a.list("k-mers")) : PV::null("k-mers"), flag("coverage"),
+             PV::file("graph-file", a.get("graph-file", wd + "/components-graph.gfa"))};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -1002,7 +1008,7 @@ int main(int argc, char **argv) {
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
                                   "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
+                                  "stats-kmers-3", "comp2graph", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1084,6 +1090,7 @@ int main(int argc, char **argv) {
     else if (tool == "kmers-color") { need("k", "k"); need("k-mers", "kf"); if (!a.has("class")) die("Mandatory argument --class not set"); }
     else if (tool == "component-colored") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "comp2seq") need("components-file", "cf");
+    else if (tool == "comp2graph") { need("k", "k"); need("components-file", "cf"); }
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1419,6 +1426,21 @@ int main(int argc, char **argv) {
         vector<string> written;
         for (uint64_t i = 0; i < nf; i++) written.push_back(wd + "/seq-builder-many/sequences/component" + (split ? "_" + std::to_string(i + 1) : string()) + ".seq.fasta");
         outs = {PV::files("output-files", written)};
+    } else if (tool == "comp2graph") {
+        // ComponentsToGraph.java:70-130: one Comp2Graph per component on a thread pool, a HashMap of strings and a quadratic merge loop
+        // each -- here the graphs of all components in one pass, the text formatted on the device (mf_comp2graph)
+        check_k(k);
+        const string cf = a.get("components-file"), gf = a.get("graph-file", wd + "/components-graph.gfa");
+        const vector<string> files = a.list("k-mers");
+        const bool cov = a.get("coverage", "false") == "true";                // (without -i: accepted and ignored, as in the reference)
+        if (!mf_comp2graph) die("comp2graph: this build of the library has no mf_comp2graph");
+        mf_ctx *ctx = ctx_of(e, a);
+        auto fp = cptrs(files);
+        uint64_t nc = 0, ns = 0, nl = 0;
+        check(mf_comp2graph(ctx, cf.c_str(), k, files.empty() ? nullptr : fp.data(), (int)files.size(), cov ? 1 : 0, gf.c_str(), &nc, &ns, &nl));
+        logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
+        logmsg("INFO", "Graph components saved to GFA format!");
+        outs = {PV::file("graph-file", gf)};
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

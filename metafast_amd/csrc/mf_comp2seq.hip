@@ -14,19 +14,11 @@
 //                 ordered export groups them by it
 //
 // Without --split the route is one ordinary table of all members (mf_table_from_device_pairs) and mf_build_unitigs_device.
-#include "mf_common.h"
-#include "mf_join.h"
-#include "mf_unitig.h"
+#include "mf_c2s.h"
 #include "mf_parse.h"
 #include <errno.h>
 
 int mf_table_from_device_pairs(mf_ctx *ctx, const uint64_t *d_keys, const uint16_t *d_vals, uint64_t n, int k, mf_table **out);
-
-#define C2S_NONE 0xFFFFFFFFu
-#define C2S_CODE_NONE 4u          // the codes of mf_unitig.hip's info byte
-#define C2S_CODE_MANY 5u
-
-static inline unsigned c2s_grid(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 // members -> canonical k-mers; a member that does not fit 2k bits raises bit 0 of *flags
 __global__ __launch_bounds__(256) void k_c2s_canon(const uint64_t *__restrict__ kmers, uint64_t n, int k, uint64_t *__restrict__ out, uint16_t *__restrict__ ones,
@@ -61,7 +53,6 @@ __global__ __launch_bounds__(256) void k_c2s_counts(const uint32_t *__restrict__
 }
 
 // ---- the pair index: slot = {k-mer, row | component << 32} (mf_uslot: cnt = row, row = component); empty = MF_EMPTY in the key word
-__device__ __forceinline__ uint64_t c2s_hash(uint64_t key, uint32_t comp) { return mf_hash64(key ^ ((uint64_t)comp * 0x9E3779B97F4A7C15ULL)); }
 // the rows' pairs are all different: a row takes the first empty slot of its probe sequence, nobody has to be recognised
 __global__ __launch_bounds__(256) void k_c2s_index_insert(mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ rkey, const uint32_t *__restrict__ rcomp,
                                                           uint64_t n_rows, unsigned int *__restrict__ flags) {
@@ -79,17 +70,6 @@ __global__ __launch_bounds__(256) void k_c2s_index_insert(mf_uslot *__restrict__
     }
     atomicOr(flags, 2u);                                     // (full: never with the capacity the host picks)
 }
-__device__ __forceinline__ bool c2s_find(const mf_uslot *__restrict__ slots, uint64_t mask, uint64_t key, uint32_t comp, uint32_t *row) {
-    uint64_t p = c2s_hash(key, comp) & mask;
-    for (uint64_t probe = 0; probe <= mask; probe++) {
-        const ulonglong2 raw = *reinterpret_cast<const ulonglong2 *>(&slots[p]);
-        if (raw.x == key && (uint32_t)(raw.y >> 32) == comp) { *row = (uint32_t)raw.y; return true; }
-        if (raw.x == MF_EMPTY) return false;
-        p = (p + 1) & mask;
-    }
-    return false;
-}
-
 // U1 restricted to a component: what k_ut_flags (mf_unitig.hip) does per table entry, per ROW -- getRightNucleotide / getLeftNucleotide
 // (HashMapOperations.java:13-47) in the map of the row's own component
 __global__ __launch_bounds__(256) void k_c2s_flags(const mf_uslot *__restrict__ slots, uint64_t mask, const uint32_t *__restrict__ rcomp, ut_arrays A) {
@@ -131,9 +111,7 @@ __global__ __launch_bounds__(256) void k_c2s_flags(const mf_uslot *__restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------
-struct c2s_rows { mf_buf<uint64_t> key; mf_buf<uint32_t> comp; mf_buf<uint16_t> cnt; uint64_t n = 0; };
-
-static int c2s_check_k(int k) {
+int c2s_check_k(int k) {
     if (k <= 0) return mf_set_error("The size of k-mer must be at least 1.");                 // KmersCounterMain.java:66-73
     if (k > 31) return mf_set_error("The size of k-mer must be no more than 31.");
     return MF_OK;
@@ -147,7 +125,7 @@ static int c2s_member_flags(mf_ctx *ctx, const unsigned int *d_flags, int k) {
     return MF_OK;
 }
 // the rows of all components, built from the member lists (d_kmers / d_comp), never from the components' own k-mer index
-static int c2s_build_rows(mf_ctx *ctx, const mf_comps *c, int k, c2s_rows &R) {
+int c2s_build_rows(mf_ctx *ctx, const mf_comps *c, int k, c2s_rows &R) {
     hipStream_t st = ctx->stream;
     const uint64_t n = c->n_kmers;
     R.n = 0;
@@ -186,12 +164,13 @@ static int c2s_build_rows(mf_ctx *ctx, const mf_comps *c, int k, c2s_rows &R) {
     R.n = nr;
     return MF_OK;
 }
-// the segmented build over the rows: pair index, restricted U1, U2 .. U5
-static int c2s_unitigs_of_rows(mf_ctx *ctx, const c2s_rows &R, uint64_t n_comps, int k, mf_seqs **out) {
+// the pair index of the rows; *cap_out = its slots (a power of two)
+int c2s_pair_index(mf_ctx *ctx, const c2s_rows &R, int k, mf_buf<mf_uslot> &slots, uint64_t *cap_out) {
     hipStream_t st = ctx->stream;
     const uint64_t nr = R.n;
-    mf_buf<mf_uslot> slots; mf_buf<unsigned int> flags;
+    mf_buf<unsigned int> flags;
     uint64_t cap = 1024; while (cap < 2 * nr) cap <<= 1;     // load <= 0.5, as the HBM index of a table (mf_index_build)
+    *cap_out = cap;
     if (nr) {
         MF_TRY(slots.alloc(ctx, cap)); MF_TRY(flags.alloc(ctx, 1));
         MF_HIP(hipMemsetAsync(slots.p, 0xFF, cap * sizeof(mf_uslot), st));       // every key word = MF_EMPTY
@@ -202,11 +181,22 @@ static int c2s_unitigs_of_rows(mf_ctx *ctx, const c2s_rows &R, uint64_t n_comps,
         }
         MF_TRY(c2s_member_flags(ctx, flags.p, k));
     }
+    return MF_OK;
+}
+int c2s_flags_launch(mf_ctx *ctx, const mf_uslot *slots, uint64_t cap, const c2s_rows &R, const ut_arrays &A) {
+    mf_ktimer tm(ctx, "k_c2s_flags");
+    k_c2s_flags<<<c2s_grid(R.n), 256, 0, ctx->stream>>>(slots, cap - 1, R.comp.p, A);
+    return MF_OK;
+}
+// the segmented build over the rows: pair index, restricted U1, U2 .. U5
+static int c2s_unitigs_of_rows(mf_ctx *ctx, const c2s_rows &R, uint64_t n_comps, int k, mf_seqs **out) {
+    const uint64_t nr = R.n;
+    mf_buf<mf_uslot> slots;
+    uint64_t cap = 0;
+    MF_TRY(c2s_pair_index(ctx, R, k, slots, &cap));
     mf_seqs *S = nullptr;
     MF_TRY(mf_ut_build(ctx, R.key.p, nullptr, R.cnt.p, nr, k, 0, nullptr, k, [&](const ut_arrays &A) -> int {
-        mf_ktimer tm(ctx, "k_c2s_flags");
-        k_c2s_flags<<<c2s_grid(nr), 256, 0, st>>>(slots.p, cap - 1, R.comp.p, A);
-        return MF_OK;
+        return c2s_flags_launch(ctx, slots.p, cap, R, A);
     }, &S, nullptr, R.comp.p));
     if (!S->d_comp) {                                        // (no rows: no sequences, but sequences of components all the same)
         void *p = nullptr;

@@ -124,6 +124,11 @@ _SIGS = {
     "mf_comps_unitigs_device": (i32, [vp, vp, i32, pvp]),
     "mf_seqs_components": (i32, [vp, vp, u64, pu64]),
     "mf_comp2seq": (i32, [vp, cp, i32, i32, cp, pu64, pu64]),
+    "mf_comps_graph_device": (i32, [vp, vp, vp, i32, i32, pvp]),
+    "mf_gfa_destroy": (None, [vp]),
+    "mf_gfa_stats": (i32, [vp, pu64, pu64, pu64, pu64]),
+    "mf_gfa_text": (i32, [vp, vp, u64, pu64]),
+    "mf_comp2graph": (i32, [vp, cp, i32, C.POINTER(cp), i32, i32, cp, pu64, pu64, pu64]),
     "mf_features_device": (i32, [vp, vp, vp, i32, vp, vp]),
     "mf_features_reads_device": (i32, [vp, vp, vp, vp, u64, u64, i32, i32, vp, vp]),
     "mf_features_reads": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, cp, cp]),
@@ -453,6 +458,34 @@ class Context:
         nf, ns = C.c_uint64(), C.c_uint64()
         _check(lib().mf_comp2seq(self.h, os.fsencode(components_bin), k, 1 if split else 0, os.fsencode(out_dir), C.byref(nf), C.byref(ns)))
         return nf.value, ns.value
+
+    # ---- comp2graph ----
+    def comps_graph(self, comps, samples=None, coverage=False, k=None):
+        """The compacted de Bruijn graph of every component as GFA (ComponentsToGraph.java:70-130), all components in one pass ->
+        (text, dict of segments / links / cycles).  samples: Tables that colour the segments (None: every k-mer is worth 1); coverage:
+        their summed counts instead of the number of samples that hold a k-mer.  k: for components loaded from a file."""
+        if k is not None:
+            _check(lib().mf_comps_set_k(comps.h, k))
+        samples = list(samples or [])
+        h = (C.c_void_p * max(len(samples), 1))(*[t.h for t in samples])
+        g = C.c_void_p()
+        _check(lib().mf_comps_graph_device(self.h, comps.h, h, len(samples), 1 if coverage else 0, C.byref(g)))
+        try:
+            ns, nl, ncy, nb = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            _check(lib().mf_gfa_stats(g, C.byref(ns), C.byref(nl), C.byref(ncy), C.byref(nb)))
+            buf = np.zeros(max(nb.value, 1), np.uint8)
+            _check(lib().mf_gfa_text(g, buf.ctypes.data, nb.value, None))
+        finally:
+            lib().mf_gfa_destroy(g)
+        return buf[:nb.value].tobytes().decode("ascii"), {"segments": ns.value, "links": nl.value, "cycles": ncy.value}
+
+    def comp2graph(self, components_bin, k, out_gfa, kmers_files=(), coverage=False):
+        """File form -> out_gfa; returns (components, segments, links)"""
+        files = list(kmers_files)
+        nc, ns, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().mf_comp2graph(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files), 1 if coverage else 0,
+                                   os.fsencode(out_gfa), C.byref(nc), C.byref(ns), C.byref(nl)))
+        return nc.value, ns.value, nl.value
 
     # ---- A12 ----
     def features(self, comps, sample_table, threshold=0, selected=None):
