@@ -316,6 +316,29 @@ int  mf_gfa_text(const mf_gfa *g, uint8_t *text, uint64_t cap, uint64_t *n);
 int  mf_comp2graph(mf_ctx *ctx, const char *components_bin, int k, const char *const *kmers_files, int n_files, int coverage,
                    const char *out_gfa, uint64_t *n_components, uint64_t *n_segments, uint64_t *n_links);
 
+/* seq2comp (src/tools/SequencesToComponents.java:61-103, src/algo/ComponentFromSequence.java:24-30; mf_seq2comp.hip): sequences a user
+ * already has -- a gene catalogue, marker contigs, filtered .seq.fasta files of comp2seq -- as components, so that features-calculator
+ * counts one feature per sequence.  Every sequence gives ONE component, in the order of the sequences: its members are the distinct
+ * canonical k-mers of the sequence, size = their number, weight = the k-mer occurrences max(0, L - k + 1).  A sequence shorter than k
+ * gives a component of size 0 and weight 0 (its position is its feature index; its breadth is 0.0 / 0.0 = NaN, its vector entry 0).
+ * Components may share k-mers (a common stretch, a sequence given twice): the features calls credit such a k-mer to every component
+ * that lists it, as the reference does.  Deviations, as sets and in size and weight the components are the reference's: inside one
+ * file the reference appends the components in the order its thread pool finishes, here they come in file order, then record order;
+ * the reference lists a component's k-mers in first-occurrence order, here they ascend, as in every components.bin of this library.
+ * Device form: the (bases, offsets) layout of mf_count_device / mf_reads_device_view; the result is an ordinary mf_comps -- k set, thr 0,
+ * no index yet -- for mf_comps_export, mf_comps_write, mf_features_device*, mf_comps_unitigs_device, mf_comps_graph_device.
+ * 1 <= k <= 31, n_seqs < 2^32 - 1, a sequence of fewer than 2^32 - 1 k-mers, fewer than 2^32 - 1 members in all: anything beyond is an
+ * error, never a truncated result.  Sequences of up to mf_ctx_stat("s2c_lds_max") k-mers build their sets in LDS, longer ones are
+ * sorted; option "s2c_lds" = 0 sorts all of them (same result), "s2c_batch_pairs" bounds the k-mer occurrences sorted together. */
+int  mf_comps_from_sequences_device(mf_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases, int k,
+                                    mf_comps **out);
+/* File form: the files one at a time, in the order given, through the readers of mf_reads_load (records with N or a phred-0 base are
+ * not there) -> components_bin (ConnectedComponent format) and stat_txt (may be NULL): "# component.no\tcomponent.size\tcomponent.weight"
+ * and one line per component, numbered from 1 -- three columns, not the cutter's four.  *n_components (may be NULL) = components in
+ * all, per_file[nfiles] (may be NULL) = components of each file. */
+int  mf_seq2comp(mf_ctx *ctx, const char *const *files, int nfiles, int k, const char *components_bin, const char *stat_txt,
+                 uint64_t *n_components, uint64_t *per_file);
+
 /* ---- A9-A11 on several GPUs: every rank owns a shard of the cutter table ---------------------
  * The cutter table and the components step join ALL samples (ComponentCutterMain.runImpl,
  * src/tools/ComponentCutterMain.java:78-114; ComponentsBuilder.run, src/algo/ComponentsBuilder.java:58-153).

@@ -49,6 +49,7 @@ extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, in
     __attribute__((weak));
 extern "C" int mf_comp2seq(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_comp2graph(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_seq2comp(mf_ctx *, const char *const *, int, int, const char *, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -181,7 +182,7 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
             if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
                 tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample" || tool == "comp2graph") return "k-mers";
-            if (tool == "component-cutter") return "sequences";
+            if (tool == "component-cutter" || tool == "seq2comp") return "sequences";
             return "reads";
         }
         if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
@@ -895,6 +896,7 @@ static const char *TOOLS_TEXT =
     "component-colored\tExtract graph components from tangled graph based on k-mers coloring\n"
     "comp2seq\t\tTransforms components in binary format to FASTA sequences (contigs)\n"
     "comp2graph\t\tTransforms components in binary format to de Bruijn graph in GFA format\n"
+    "seq2comp\t\tTransforms sequences to components\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -983,6 +985,8 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
     } else if (tool == "comp2graph") {
         v = {opt_i("k"), opt_f("components-file"), a.has("k-mers") ? PV::files("k-mers", a.list("k-mers")) : PV::null("k-mers"), flag("coverage"),
              PV::file("graph-file", a.get("graph-file", wd + "/components-graph.gfa"))};
+    } else if (tool == "seq2comp") {
+        v = {opt_i("k"), PV::files("sequences", a.list("sequences")), PV::file("components-file", a.get("components-file", wd + "/components.bin"))};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -1008,7 +1012,7 @@ int main(int argc, char **argv) {
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
                                   "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "comp2graph", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
+                                  "stats-kmers-3", "seq2comp", "comp2graph", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1091,6 +1095,7 @@ int main(int argc, char **argv) {
     else if (tool == "component-colored") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "comp2seq") need("components-file", "cf");
     else if (tool == "comp2graph") { need("k", "k"); need("components-file", "cf"); }
+    else if (tool == "seq2comp") { need("k", "k"); need("sequences", "i"); }
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1441,6 +1446,32 @@ int main(int argc, char **argv) {
         logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
         logmsg("INFO", "Graph components saved to GFA format!");
         outs = {PV::file("graph-file", gf)};
+    } else if (tool == "seq2comp") {
+        // SequencesToComponents.java:61-103: a component per sequence that survives the readers, its members the distinct canonical k-mers
+        // (a LongArraySet with a linear scan per add there: quadratic in the sequence's length) -- here a segmented set-build on the
+        // device (mf_seq2comp).  Components in file order, then record order (the reference: as its thread pool finishes); a sequence
+        // shorter than k keeps its place as an empty component
+        check_k(k);
+        const vector<string> files = a.list("sequences");
+        const string cf = a.get("components-file", wd + "/components.bin"), sf = wd + "/components-stat.txt";
+        for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
+        if (!mf_seq2comp) die("seq2comp: this build of the library has no mf_seq2comp");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("DEBUG", "Loading sequences from files...");
+        auto fp = cptrs(files);
+        vector<uint64_t> per(files.size() + 1, 0);
+        uint64_t nc = 0;
+        { const size_t q = cf.find_last_of('/'); if (q != string::npos && q > 0) mkdirs(cf.substr(0, q)); }
+        check(mf_seq2comp(ctx, files.empty() ? nullptr : fp.data(), (int)files.size(), k, cf.c_str(), sf.c_str(), &nc, per.data()));
+        for (size_t i = 0; i < files.size(); i++) {          // (the reference logs each pair as it goes; the numbers are the same)
+            logmsg("INFO", "Loading file %s...", basename_of(files[i]).c_str());
+            logmsg("INFO", "%llu components added", (unsigned long long)per[i]);
+        }
+        logmsg("INFO", "Total %s components were found", group_digits(nc).c_str());
+        logmsg("INFO", "Components saved to %s", cf.c_str());
+        describe(sf, "File with components' statistics (in text format)");
+        describe(cf, "File with components made from the input sequences, one per sequence (in binary format)");
+        outs = {PV::file("components-file", cf), PV::file("components-stat", sf)};
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

@@ -7,7 +7,7 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
 # column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip)
 NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_")
@@ -16,7 +16,10 @@ NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_")
 EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"], "mf_comp2seq": ["k_c2s_flags"],
           "mf_kps": ["k_kps_index", "k_kps_gather", "k_kps_header", "k_kps_widths", "k_kps_format"],
           "mf_comp2graph": ["k_c2g_links", "k_c2g_double", "k_c2g_ends", "k_c2g_assign", "k_c2g_segments", "k_c2g_links_of", "k_c2g_write_s",
-                            "k_c2g_write_bases", "k_c2g_write_l", "k_c2g_values"]}
+                            "k_c2g_write_bases", "k_c2g_write_l", "k_c2g_values"],
+          # (k_s2c_lds: waves that share a workgroup's LDS table between wave-level barriers, two workgroups per CU)
+          "mf_seq2comp": ["k_s2c_sizes", "k_s2c_lds", "k_s2c_pairs", "k_s2c_heads", "k_s2c_seg_heads", "k_s2c_seg_sizes", "k_s2c_compact", "k_s2c_place",
+                          "k_s2c_shift"]}
 
 
 def main():

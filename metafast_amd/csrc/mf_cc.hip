@@ -456,6 +456,28 @@ __global__ void k_features_occ(const unsigned long long *__restrict__ occ, const
     }
 }
 
+// Components that share k-mers (seq2comp: two sequences with a common stretch, a sequence given twice) list a k-mer more than once.
+// The index over the members then holds the k-mer in several slots and a lookup finds the first of them only, while the reference
+// credits a k-mer to every component that lists it (FeaturesCalculatorMain.java:97-103 one map entry, :192-203 read once per listing).
+// *shared = 1 when some member is not the entry its own k-mer is found at.
+__global__ void k_comps_shared(mf_index_view ix, const uint64_t *__restrict__ ckeys, uint64_t nk, unsigned int *__restrict__ shared) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nk) return;
+    uint32_t idx, v;
+    if (mf_index_find(ix, ckeys[j], &idx, &v) && idx != (uint32_t)j) atomicOr(shared, 1u);
+}
+// k_features_occ for such components: the reads' occurrences of a k-mer were all counted at the entry a lookup finds, every listing reads them there
+__global__ void k_features_occ_shared(mf_index_view ix, const uint64_t *__restrict__ ckeys, const unsigned long long *__restrict__ occ,
+                                      const uint32_t *__restrict__ comp_of, uint64_t nk, int threshold, const uint8_t *__restrict__ sel,
+                                      unsigned long long *__restrict__ vec, unsigned int *__restrict__ found) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nk || (sel && !sel[j])) return;
+    uint32_t idx, v;
+    if (!mf_index_find(ix, ckeys[j], &idx, &v)) return;
+    const unsigned long long o = occ[idx];
+    if ((long long)o > (long long)threshold) { atomicAdd(&vec[comp_of[j]], o); atomicAdd(&found[comp_of[j]], 1u); }
+}
+
 // --selected (FeaturesCalculatorMain.java:55-57, 115-117, 193): sel[j] = 1 iff component k-mer j has a value > 0 in the table of
 // selected k-mers (selected.getWithZero(kmer) > 0); selcnt[c] = such k-mers of component c (kmersCount, the breadth's denominator)
 __global__ void k_features_select(mf_index_view ix, const uint64_t *__restrict__ ckeys, const uint32_t *__restrict__ comp_of, uint64_t nk,
@@ -839,6 +861,18 @@ int mf_comps_from_host(mf_ctx *ctx, int k, const std::vector<uint64_t> &sizes, c
     return MF_OK;
 }
 
+// learns once whether the member list holds a k-mer twice (the index over the members must stand)
+static int comps_learn_shared(mf_ctx *ctx, mf_comps *c) {
+    if (c->shared >= 0) return MF_OK;
+    mf_buf<unsigned int> flag; MF_TRY(flag.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(flag.p, 0, 4, ctx->stream));
+    k_comps_shared<<<cgrid(c->n_kmers), 256, 0, ctx->stream>>>(mf_view(c->index), c->d_kmers, c->n_kmers, flag.p);
+    unsigned int h = 0;
+    MF_HIP(hipMemcpyAsync(&h, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    c->shared = h ? 1 : 0;
+    return MF_OK;
+}
 // the selection of --selected on the component k-mers: mask per k-mer + count per component (host); selected == NULL: no mask
 static int features_selection(mf_ctx *ctx, mf_comps *c, mf_table *selected, mf_buf<uint8_t> &mask, std::vector<unsigned int> &selcnt) {
     if (!selected) return MF_OK;
@@ -893,10 +927,17 @@ extern "C" int mf_features_device_selected(mf_ctx *ctx, mf_comps *c, const mf_ta
             k_features_rev<<<cgrid(c->n_kmers), 256, 0, st>>>(mf_view(sample->index), c->d_kmers, c->d_comp, c->n_kmers, threshold, mask.p, dvec.p, dfound.p);
         } else {          // ... or the components
             if (!c->index.slots) MF_TRY(mf_index_build(ctx, c->d_kmers, nullptr, c->n_kmers, &c->index, &c->index_bytes));
-            unsigned grid = (unsigned)std::min<uint64_t>((sample->n + 255) / 256, 65536);
-            mf_ktimer tm(ctx, "k_features");
-            k_features<<<grid, 256, 0, st>>>(mf_view(c->index), c->d_comp, sample->d_keys,
-                                             sample->d_counts, sample->n, threshold, mask.p, dvec.p, dfound.p);
+            MF_TRY(comps_learn_shared(ctx, c));
+            if (c->shared) {          // (a lookup in their index finds ONE of a shared k-mer's components: every listing asks the sample instead)
+                MF_TRY(mf_table_ensure_index(const_cast<mf_table *>(sample)));
+                mf_ktimer tm(ctx, "k_features");
+                k_features_rev<<<cgrid(c->n_kmers), 256, 0, st>>>(mf_view(sample->index), c->d_kmers, c->d_comp, c->n_kmers, threshold, mask.p, dvec.p, dfound.p);
+            } else {
+                unsigned grid = (unsigned)std::min<uint64_t>((sample->n + 255) / 256, 65536);
+                mf_ktimer tm(ctx, "k_features");
+                k_features<<<grid, 256, 0, st>>>(mf_view(c->index), c->d_comp, sample->d_keys,
+                                                 sample->d_counts, sample->n, threshold, mask.p, dvec.p, dfound.p);
+            }
         }
     }
     std::vector<unsigned int> hf(nc);
@@ -930,8 +971,10 @@ extern "C" int mf_features_reads_device_selected(mf_ctx *ctx, mf_comps *c, const
     if (c->n_kmers) {
         if (!c->index.slots) MF_TRY(mf_index_build(ctx, c->d_kmers, nullptr, c->n_kmers, &c->index, &c->index_bytes));   // hm.put(kmer, 0) :99-103
         MF_TRY(mf_presence_core(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_reads, n_bases, k, c->index, occ.p));
+        MF_TRY(comps_learn_shared(ctx, c));
         mf_ktimer tm(ctx, "k_features");
-        k_features_occ<<<cgrid(c->n_kmers), 256, 0, st>>>(occ.p, c->d_comp, c->n_kmers, threshold, mask.p, dvec.p, dfound.p);
+        if (c->shared) k_features_occ_shared<<<cgrid(c->n_kmers), 256, 0, st>>>(mf_view(c->index), c->d_kmers, occ.p, c->d_comp, c->n_kmers, threshold, mask.p, dvec.p, dfound.p);
+        else k_features_occ<<<cgrid(c->n_kmers), 256, 0, st>>>(occ.p, c->d_comp, c->n_kmers, threshold, mask.p, dvec.p, dfound.p);
     }
     std::vector<unsigned int> hf(nc);
     MF_HIP(hipMemcpyAsync(vec, dvec.p, nc * 8, hipMemcpyDeviceToHost, st));

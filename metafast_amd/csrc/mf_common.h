@@ -100,6 +100,8 @@ struct mf_ctx {
     int64_t opt_dcc_sparse = 0;    // sharded cutter, levels after the first: 1 = always the sparse set-up of the arrays over all vertex ids (tests)
     int64_t opt_stats_slices = 0;  // multi-sample join (mf_join.hip): hash slices of the key space, one union pass each (0 = as many as free HBM asks for)
     int64_t opt_kps_matrix_bytes = 0;  // kmers-per-sample, tables form: the samples x k-mers count matrix may take this many bytes (0 = what is free in HBM; tests: a small number)
+    int64_t opt_s2c_lds = 1;       // seq2comp (mf_seq2comp.hip): sequences of up to 4096 k-mers build their sets in LDS (0: every sequence through the sort path)
+    int64_t opt_s2c_batch_pairs = 1 << 28;   // ... the sort path takes whole sequences of at most this many k-mer occurrences together (a longer sequence goes alone; tests: a small number)
     // ... the count for k = 32..63
     int64_t opt_wide_skm = 1;      // mf_count_wide_device: super-k-mer records + LDS tables (mf_wskm.hip) instead of sorting every occurrence (0: the sort path, mf_wide.hip)
     int64_t opt_wide_skm_min = 1 << 20;     // ... from this many k-mer occurrences on (tests: 1)
@@ -132,7 +134,7 @@ struct mf_ctx {
     size_t arena_bytes = 0;
     // counters a host can read (mf_ctx_stat): counting runs that started their slices over because a buffer found no place (mf_skm.hip);
     // read files the device parser took / handed to the host readers (mf_dparse.hip)
-    uint64_t n_slice_restarts = 0, n_dparse_files = 0, n_dparse_stepped_back = 0, n_wide_big = 0, n_wide_hashed = 0, n_ut_doubled = 0, n_pilots = 0, n_gz_device = 0;
+    uint64_t n_slice_restarts = 0, n_dparse_files = 0, n_dparse_stepped_back = 0, n_wide_big = 0, n_wide_hashed = 0, n_ut_doubled = 0, n_pilots = 0, n_gz_device = 0, n_s2c_batches = 0;
     // timers
     std::vector<mf_timer_rec> pending;
     std::vector<hipEvent_t> event_pool;
@@ -265,6 +267,7 @@ struct mf_comps {
     uint64_t *d_kmers = nullptr; uint32_t *d_comp = nullptr;
     size_t kmers_bytes = 0, comp_bytes = 0;
     mf_index index; size_t index_bytes = 0;
+    int shared = -1;              // does the member list hold a k-mer twice (components that share k-mers: seq2comp)?  -1: not looked at yet (the features calls find out, mf_cc.hip)
 };
 
 // ascending k-mers with 64-bit values (BigLong2LongHashMap): the packed class counts of kmers-color, the input of component-colored

@@ -175,6 +175,7 @@ static const struct { const char *name; int64_t mf_ctx::*field; int64_t lo = OPT
     {"nbr_global", &mf_ctx::opt_nbr_global}, {"ut_double_after", &mf_ctx::opt_ut_double_after, 1, 64}, {"ut_plain_rounds", &mf_ctx::opt_ut_plain_rounds},
     {"cc_compress", &mf_ctx::opt_cc_compress}, {"cc_sparse", &mf_ctx::opt_cc_sparse}, {"dcc_sparse", &mf_ctx::opt_dcc_sparse},
     {"stats_slices", &mf_ctx::opt_stats_slices, 0, 4096}, {"kps_matrix_bytes", &mf_ctx::opt_kps_matrix_bytes, 0},
+    {"s2c_lds", &mf_ctx::opt_s2c_lds, 0, 1}, {"s2c_batch_pairs", &mf_ctx::opt_s2c_batch_pairs, 1},
     {"wide_skm", &mf_ctx::opt_wide_skm}, {"wide_skm_min", &mf_ctx::opt_wide_skm_min}, {"wide_skm_lazy_order", &mf_ctx::opt_wide_skm_lazy_order},
     {"wide_skm_fine", &mf_ctx::opt_wide_skm_fine}, {"wide_skm_pack", &mf_ctx::opt_wide_skm_pack}, {"wide_skm_merge", &mf_ctx::opt_wide_skm_merge},
     {"wide_skm_lead", &mf_ctx::opt_wide_skm_lead}, {"wide_skm_unit", &mf_ctx::opt_wide_skm_unit},
@@ -222,6 +223,8 @@ extern "C" int64_t mf_ctx_stat(mf_ctx *ctx, const char *name) {
     if (s == "streamed_counts_stepped_back") return (int64_t)ctx->n_stream_stepped_back;
     if (s == "device_parsed_files") return (int64_t)ctx->n_dparse_files;
     if (s == "device_parser_stepped_back") return (int64_t)ctx->n_dparse_stepped_back;
+    if (s == "s2c_lds_max") return 4096;                  // (S2C_T of mf_seq2comp.hip: the longest sequence, in k-mers, of the LDS class)
+    if (s == "s2c_sort_batches") return (int64_t)ctx->n_s2c_batches;
     if (s == "hipmalloc_calls") return (int64_t)ctx->n_hipmalloc;
     if (s == "hipmalloc_bytes") return (int64_t)ctx->b_hipmalloc;
     if (s == "hipmalloc_us") return (int64_t)(ctx->t_hipmalloc * 1e6);

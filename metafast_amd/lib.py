@@ -129,6 +129,8 @@ _SIGS = {
     "mf_gfa_stats": (i32, [vp, pu64, pu64, pu64, pu64]),
     "mf_gfa_text": (i32, [vp, vp, u64, pu64]),
     "mf_comp2graph": (i32, [vp, cp, i32, C.POINTER(cp), i32, i32, cp, pu64, pu64, pu64]),
+    "mf_comps_from_sequences_device": (i32, [vp, vp, vp, u64, u64, i32, pvp]),
+    "mf_seq2comp": (i32, [vp, C.POINTER(cp), i32, i32, cp, cp, pu64, vp]),
     "mf_features_device": (i32, [vp, vp, vp, i32, vp, vp]),
     "mf_features_reads_device": (i32, [vp, vp, vp, vp, u64, u64, i32, i32, vp, vp]),
     "mf_features_reads": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, cp, cp]),
@@ -486,6 +488,23 @@ class Context:
         _check(lib().mf_comp2graph(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files), 1 if coverage else 0,
                                    os.fsencode(out_gfa), C.byref(nc), C.byref(ns), C.byref(nl)))
         return nc.value, ns.value, nl.value
+
+    # ---- seq2comp ----
+    def comps_from_sequences(self, d_bases, d_offsets, n_seqs, n_bases, k):
+        """One component per sequence (SequencesToComponents.java:61-103): its distinct canonical k-mers, size = their number, weight =
+        the k-mer occurrences; a sequence shorter than k gives an empty component.  Input as for count_device."""
+        c = C.c_void_p()
+        _check(lib().mf_comps_from_sequences_device(self.h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_seqs, n_bases, k, C.byref(c)))
+        return Comps(self, c)
+
+    def seq2comp(self, files, k, components_bin, stat_txt=None):
+        """File form -> components_bin and the three-column stat_txt; returns (components, components per file)"""
+        files = list(files)
+        n = C.c_uint64()
+        per = np.zeros(max(len(files), 1), dtype=np.uint64)
+        _check(lib().mf_seq2comp(self.h, _cfiles(files) if files else None, len(files), k, os.fsencode(components_bin), _opt(stat_txt), C.byref(n),
+                                 per.ctypes.data))
+        return n.value, [int(x) for x in per[:len(files)]]
 
     # ---- A12 ----
     def features(self, comps, sample_table, threshold=0, selected=None):
