@@ -339,6 +339,50 @@ int  mf_comps_from_sequences_device(mf_ctx *ctx, const void *d_bases, const void
 int  mf_seq2comp(mf_ctx *ctx, const char *const *files, int nfiles, int k, const char *components_bin, const char *stat_txt,
                  uint64_t *n_components, uint64_t *per_file);
 
+/* component-paths (src/tools/ComponentPathsMain.java:82-206; mf_comppaths.hip): which stretches of the given sequences lie inside a
+ * component.  Every selected component is looked at by itself: a path is a maximal run of consecutive positions of ONE sequence whose
+ * canonical k-mers are all members of the component -- the sequence's own text [first, first + positions + k - 1), forward as given,
+ * upper case.  Runs never join across two sequences; a sequence shorter than k has no positions; components that share k-mers
+ * (seq2comp) each get the shared stretch, and each run goes on by itself where the other ends.  A path is kept when its length is at
+ * least min_len; per component the first max_paths kept paths in encounter order (call of mf_paths_add, sequence, position) stay,
+ * the rest are dropped; the kept ones are printed longest first, ties in encounter order, as Sequence.printSequences prints them:
+ * ">i length=L av_weight=W min_weight=0 max_weight=0", i from 1, the bases in lines of 70; W = Math.round(weight / (double) size) =
+ * floor(x + 0.5) of the component (an error where it does not fit a signed 32-bit integer; the reference's cast wraps around).  Every
+ * position costs one lookup in an index over the members of the selected components, whatever their number (the reference: one hash
+ * set per component and sequence).
+ * Device form: mf_paths_create (the components must know their k: mf_comps_set_k; selection: component numbers from 1, NULL = all of
+ * them; a number twice counts once, a number below 1 or above the count is an error; slot = place in the de-duplicated selection, in
+ * the order given), mf_paths_add once per batch of sequences (the (bases, offsets) layout of mf_count_device; the batch may be
+ * released afterwards: the kept paths' bases are copied into a store on the device), mf_paths_finish, then the counts and the text.
+ * A thread of the marking kernel takes mf_ctx_stat("cp_run") consecutive positions of one sequence, a workgroup "cp_block".
+ * Limits, each an error and never a truncated result: 1 <= k <= 31; fewer than 2^32 - 1 components, members, sequences per batch, runs
+ * per batch, kept paths and max_paths; a sequence of fewer than 2^31 k-mers; fewer than 2^26 selected components that list one k-mer;
+ * the store and the text must find room in HBM. */
+typedef struct mf_paths mf_paths;
+int  mf_paths_create(mf_ctx *ctx, mf_comps *c, const uint32_t *selection, uint64_t n_selection, int min_len, uint64_t max_paths,
+                     mf_paths **out);
+int  mf_paths_add(mf_paths *p, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases);
+int  mf_paths_finish(mf_paths *p);
+void mf_paths_destroy(mf_paths *p);
+/* any may be NULL: slots, kept paths and bytes of text over all slots (these two after mf_paths_finish), the most selected components
+ * that list one k-mer (1: the selected components share no k-mer) */
+int  mf_paths_stats(const mf_paths *p, uint64_t *n_slots, uint64_t *n_paths, uint64_t *n_bytes, uint64_t *max_listings);
+/* per slot, arrays of n_slots entries, any may be NULL: the component's number, its kept paths, the bytes of its text, and whether
+ * its count reached max_paths (the reference warns then: "keeping only first ... of them"); all but the first after mf_paths_finish */
+int  mf_paths_slots(const mf_paths *p, uint32_t *component_no, uint64_t *n_paths, uint64_t *n_bytes, uint8_t *reached_cap);
+/* the text of one slot, or of all slots one after the other (slot = -1): *n (may be NULL) = its bytes, whatever cap is; nothing is
+ * written when cap is below it */
+int  mf_paths_text(const mf_paths *p, int64_t slot, uint8_t *text, uint64_t cap, uint64_t *n);
+/* out_dir/component-<no>.seq.fasta for every slot, an empty file where a component has no path; out_dir is made if it is not there.
+ * *n_paths (may be NULL) = paths written */
+int  mf_paths_write(const mf_paths *p, const char *out_dir, uint64_t *n_paths);
+/* File form: components_bin + the sequence files, one resident at a time, in the order given, through the readers of mf_reads_load
+ * (records with N or a phred-0 base are not there) -> out_dir.  selection as for mf_paths_create; the driver passes max_paths = 10^6
+ * (MAX_PATHS_COUNT).  *n_components (may be NULL) = components in the file, *n_paths (may be NULL) = paths written. */
+int  mf_component_paths(mf_ctx *ctx, const char *components_bin, int k, const char *const *files, int nfiles, const uint32_t *selection,
+                        uint64_t n_selection, int min_len, uint64_t max_paths, const char *out_dir, uint64_t *n_components,
+                        uint64_t *n_paths);
+
 /* ---- A9-A11 on several GPUs: every rank owns a shard of the cutter table ---------------------
  * The cutter table and the components step join ALL samples (ComponentCutterMain.runImpl,
  * src/tools/ComponentCutterMain.java:78-114; ComponentsBuilder.run, src/algo/ComponentsBuilder.java:58-153).

@@ -50,6 +50,22 @@ extern "C" int mf_colored_components(mf_ctx *, const char *const *, int, int, in
 extern "C" int mf_comp2seq(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_comp2graph(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_seq2comp(mf_ctx *, const char *const *, int, int, const char *, const char *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_paths_create(mf_ctx *, mf_comps *, const uint32_t *, uint64_t, int, uint64_t, mf_paths **) __attribute__((weak));
+extern "C" int mf_paths_add(mf_paths *, const void *, const void *, uint64_t, uint64_t) __attribute__((weak));
+extern "C" int mf_paths_finish(mf_paths *) __attribute__((weak));
+extern "C" void mf_paths_destroy(mf_paths *) __attribute__((weak));
+extern "C" int mf_paths_slots(const mf_paths *, uint32_t *, uint64_t *, uint64_t *, uint8_t *) __attribute__((weak));
+extern "C" int mf_paths_write(const mf_paths *, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_paths_stats(const mf_paths *, uint64_t *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
+// (component-paths drives the library step by step, to log as the reference does: these older entry points are weak for it too)
+extern "C" int mf_comps_load(mf_ctx *, const char *, mf_comps **) __attribute__((weak));
+extern "C" int mf_comps_set_k(mf_comps *, int) __attribute__((weak));
+extern "C" int mf_comps_stats(const mf_comps *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" void mf_comps_destroy(mf_comps *) __attribute__((weak));
+extern "C" int mf_reads_load(mf_ctx *, const char *const *, int, mf_reads **) __attribute__((weak));
+extern "C" int mf_reads_stats(const mf_reads *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_reads_device_view(const mf_reads *, const void **, const void **) __attribute__((weak));
+extern "C" void mf_reads_destroy(mf_reads *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -170,6 +186,7 @@ static const OptDef OPTS[] = {
     {"class", "", false, false}, {"val", "val", false, true}, {"n_groups", "group", false, false}, {"separate", "", false, true},
     {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false}, {"percent-present", "perc", false, false},
     {"coverage", "cov", false, true}, {"graph-file", "", false, false},
+    {"seq", "", true, false}, {"components", "", true, false}, {"all-components", "a", false, true}, {"min-length", "", false, false},
 };
 // `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
@@ -188,6 +205,10 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
         if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
                               tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "stats-kmers-3" || tool == "kmers-grouped-counter")
                                  ? "maximal-bad-frequence" : "maximal-bad-frequency";
+        if (tool == "component-paths") {                                   // ComponentPathsMain.java:52-71 (features-calculator: -cm is the components' file)
+            if (s == "cm") return "components";
+            if (s == "l") return "min-length";
+        }
         if (s == "l") return (tool == "seq-builder" || tool == "seq-builder-many") ? "sequence-len" : "min-seq-len";
         if (s == "o") return (tool == "view" || tool == "bin2fasta") ? "output-file" : "output-dir";
         if (s == "kf" && tool == "kmers-color") return "k-mers";            // ColorKmersMain.java:39-43 (view, bin2fasta: kmers-file)
@@ -897,6 +918,7 @@ static const char *TOOLS_TEXT =
     "comp2seq\t\tTransforms components in binary format to FASTA sequences (contigs)\n"
     "comp2graph\t\tTransforms components in binary format to de Bruijn graph in GFA format\n"
     "seq2comp\t\tTransforms sequences to components\n"
+    "component-paths\t\tExtracts paths in the components\n"
     "view\t\t\tView different binary objects (k-mers files, components)\n"
     "bin2fasta\t\tConverts different binary objects to FASTA format\n"
     "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
@@ -987,6 +1009,9 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
              PV::file("graph-file", a.get("graph-file", wd + "/components-graph.gfa"))};
     } else if (tool == "seq2comp") {
         v = {opt_i("k"), PV::files("sequences", a.list("sequences")), PV::file("components-file", a.get("components-file", wd + "/components.bin"))};
+    } else if (tool == "component-paths") {
+        v = {opt_i("k"), opt_f("components-file"), PV::files("seq", a.list("seq")), PV("components", a.list("components")), flag("all-components"),
+             PV("min-length", a.get("min-length", "50")), PV::file("output-dir", a.get("output-dir", wd + "/paths"))};
     } else if (tool == "view" || tool == "bin2fasta") {
         v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
     }
@@ -1012,7 +1037,7 @@ int main(int argc, char **argv) {
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
                                   "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "seq2comp", "comp2graph", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
+                                  "stats-kmers-3", "seq2comp", "component-paths", "comp2graph", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1096,6 +1121,7 @@ int main(int argc, char **argv) {
     else if (tool == "comp2seq") need("components-file", "cf");
     else if (tool == "comp2graph") { need("k", "k"); need("components-file", "cf"); }
     else if (tool == "seq2comp") { need("k", "k"); need("sequences", "i"); }
+    else if (tool == "component-paths") { need("k", "k"); need("components-file", "cf"); if (!a.has("seq")) die("Mandatory argument --seq not set"); }
     props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
 
     if (tool == "kmer-counter") {
@@ -1472,6 +1498,70 @@ int main(int argc, char **argv) {
         describe(sf, "File with components' statistics (in text format)");
         describe(cf, "File with components made from the input sequences, one per sequence (in binary format)");
         outs = {PV::file("components-file", cf), PV::file("components-stat", sf)};
+    } else if (tool == "component-paths") {
+        // ComponentPathsMain.java:82-190: for every sequence one hash set per selected component is probed, O(components x bases) -- here
+        // one lookup per k-mer position in an index over the members of all selected components, the runs found, paired, capped, sorted
+        // and printed on the device (mf_comppaths.hip).  Without a selection the reference logs its message and ends cleanly; here the
+        // run fails with it.  A number out of range is an exception there and an error here.
+        check_k(k);
+        const string cf = a.get("components-file"), od = a.get("output-dir", wd + "/paths");
+        const vector<string> files = a.list("seq");
+        const bool all = a.get("all-components", "false") == "true";
+        const int min_len = a.geti("min-length", 50);
+        vector<uint32_t> sel;
+        for (auto &v : a.list("components")) {
+            char *end = nullptr; const long long no = strtoll(v.c_str(), &end, 10);
+            if (v.empty() || *end) die("Can't parse integer value '%s' of option --components", v.c_str());
+            if (no < 1 || no > 0xFFFFFFFFll) die("There is no component %s (components are numbered from 1)", v.c_str());
+            sel.push_back((uint32_t)no);
+        }
+        if (!all && sel.empty()) die("No components to process!!! Do you forget to set --all-components or --components n1,n2,...?");
+        if (!exists(cf)) die("Can't load components: file not found (%s)", cf.c_str());
+        for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
+        if (!mf_paths_create || !mf_paths_add || !mf_paths_finish || !mf_paths_destroy || !mf_paths_slots || !mf_paths_write || !mf_paths_stats || !mf_comps_load ||
+            !mf_comps_set_k || !mf_comps_stats || !mf_comps_destroy || !mf_reads_load || !mf_reads_stats || !mf_reads_device_view || !mf_reads_destroy)
+            die("component-paths: this build of the library has no mf_paths_create");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("DEBUG", "Loading components...");
+        mf_comps *c = nullptr;
+        check(mf_comps_load(ctx, cf.c_str(), &c));
+        check(mf_comps_set_k(c, k));
+        uint64_t nc = 0;
+        check(mf_comps_stats(c, &nc, nullptr));
+        logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
+        if (all && nc == 0) die("No components to process!!!");
+        logmsg("DEBUG", "Preparing...");
+        mf_paths *paths = nullptr;
+        const uint64_t max_paths = 1000000;                                   // MAX_PATHS_COUNT (:30)
+        check(mf_paths_create(ctx, c, all ? nullptr : sel.data(), all ? 0 : sel.size(), min_len, max_paths, &paths));
+        logmsg("DEBUG", "Loading sequences and extracting paths...");
+        for (auto &f : files) {                                               // one file resident at a time
+            logmsg("INFO", "Loading file %s...", basename_of(f).c_str());
+            const char *fp = f.c_str();
+            mf_reads *r = nullptr;
+            check(mf_reads_load(ctx, &fp, 1, &r));
+            const void *db = nullptr, *doff = nullptr; uint64_t nr = 0, nb = 0;
+            check(mf_reads_stats(r, &nr, &nb));
+            check(mf_reads_device_view(r, &db, &doff));
+            check(mf_paths_add(paths, db, doff, nr, nb));
+            mf_reads_destroy(r);
+        }
+        check(mf_paths_finish(paths));
+        uint64_t nslots = 0;
+        check(mf_paths_stats(paths, &nslots, nullptr, nullptr, nullptr));
+        vector<uint32_t> no(nslots + 1, 0); vector<uint8_t> reached(nslots + 1, 0);
+        check(mf_paths_slots(paths, no.data(), nullptr, nullptr, reached.data()));
+        for (uint64_t i = 0; i < nslots; i++)
+            if (reached[i]) logmsg("WARN", "Too many paths in component %u, keeping only first %llu of them!", no[i], (unsigned long long)max_paths);
+        logmsg("INFO", "Sorting...");
+        logmsg("INFO", "Saving to files...");
+        { const size_t q = od.find_last_of('/'); if (q != string::npos && q > 0) mkdirs(od.substr(0, q)); }
+        uint64_t np = 0;
+        check(mf_paths_write(paths, od.c_str(), &np));
+        mf_paths_destroy(paths);
+        mf_comps_destroy(c);
+        logmsg("INFO", "Paths for %llu component(s) were saved in directory %s", (unsigned long long)nslots, od.c_str());
+        outs = {};
     } else if (tool == "view") {
         run_view(a, k);
     } else if (tool == "bin2fasta") {

@@ -16,6 +16,7 @@
 // Components come in sequence order; inside a component the resident order is unspecified (export and write sort it, as for the
 // cutter's components).
 #include "mf_common.h"
+#include "mf_roll.h"
 #include <algorithm>
 #include <memory>
 
@@ -24,29 +25,7 @@
 #define S2C_WAVE_T (S2C_T / 4)        // one wave + a quarter of the table up to here
 #define S2C_RUN 32                    // long class: positions per thread
 
-// A0 G1 C2 T3 from the ASCII letter, either case (the decoding of mf_dec4, one byte)
-__device__ __forceinline__ uint32_t s2c_code(uint8_t b) {
-    const uint32_t t = ((uint32_t)b >> 1) & 3u;
-    return (((t ^ (t >> 1)) & 1u) << 1) | (t >> 1);
-}
-// the canonical k-mers at positions [0, count) of p (count + k - 1 bases are read: k - 1 of lead-in, then one per k-mer)
-template <typename F>
-__device__ __forceinline__ void s2c_roll(const uint8_t *__restrict__ p, uint32_t count, int k, F &&f) {
-    const int top = 2 * k - 2;
-    const uint64_t mask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    uint64_t fw = 0, rc = 0;
-    for (int j = 0; j < k - 1; j++) {
-        const uint64_t c = s2c_code(p[j]);
-        fw = (fw << 2) | c;
-        rc = (rc >> 2) | ((3ull - c) << top);
-    }
-    for (uint32_t i = 0; i < count; i++) {
-        const uint64_t c = s2c_code(p[(uint32_t)(k - 1) + i]);
-        fw = ((fw << 2) | c) & mask;
-        rc = (rc >> 2) | ((3ull - c) << top);
-        f(i, fw < rc ? fw : rc);
-    }
-}
+// (s2c_code, s2c_roll: mf_roll.h)
 
 // occ[i] = max(0, len_i - k + 1); a sequence of 2^32 - 1 or more occurrences (or offsets that go backwards) raises *bad
 __global__ void k_s2c_sizes(const uint64_t *__restrict__ off, uint64_t n, int k, uint32_t *__restrict__ occ, unsigned int *__restrict__ bad) {

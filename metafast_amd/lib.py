@@ -131,6 +131,15 @@ _SIGS = {
     "mf_comp2graph": (i32, [vp, cp, i32, C.POINTER(cp), i32, i32, cp, pu64, pu64, pu64]),
     "mf_comps_from_sequences_device": (i32, [vp, vp, vp, u64, u64, i32, pvp]),
     "mf_seq2comp": (i32, [vp, C.POINTER(cp), i32, i32, cp, cp, pu64, vp]),
+    "mf_paths_create": (i32, [vp, vp, vp, u64, i32, u64, pvp]),
+    "mf_paths_add": (i32, [vp, vp, vp, u64, u64]),
+    "mf_paths_finish": (i32, [vp]),
+    "mf_paths_destroy": (None, [vp]),
+    "mf_paths_stats": (i32, [vp, pu64, pu64, pu64, pu64]),
+    "mf_paths_slots": (i32, [vp, vp, vp, vp, vp]),
+    "mf_paths_text": (i32, [vp, i64, vp, u64, pu64]),
+    "mf_paths_write": (i32, [vp, cp, pu64]),
+    "mf_component_paths": (i32, [vp, cp, i32, C.POINTER(cp), i32, vp, u64, i32, u64, cp, pu64, pu64]),
     "mf_features_device": (i32, [vp, vp, vp, i32, vp, vp]),
     "mf_features_reads_device": (i32, [vp, vp, vp, vp, u64, u64, i32, i32, vp, vp]),
     "mf_features_reads": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, cp, cp]),
@@ -187,6 +196,7 @@ _SIGS = {
     "mf_colored_components": (i32, [vp, C.POINTER(cp), i32, i32, i64, i32, i32, C.c_double, cp, cp, vp]),
 }
 
+MAX_PATHS_COUNT = 10 ** 6       # ComponentPathsMain.java:30
 STATS_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "unique_left")
 STATS3_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "group_c", "unique_left")
 
@@ -505,6 +515,29 @@ class Context:
         _check(lib().mf_seq2comp(self.h, _cfiles(files) if files else None, len(files), k, os.fsencode(components_bin), _opt(stat_txt), C.byref(n),
                                  per.ctypes.data))
         return n.value, [int(x) for x in per[:len(files)]]
+
+    # ---- component-paths ----
+    def paths(self, comps, selection=None, min_len=50, max_paths=MAX_PATHS_COUNT, k=None):
+        """The stretches of sequences that lie inside components (ComponentPathsMain.java:82-206) -> Paths: add() a batch of sequences
+        (once per file), finish(), then counts and text.  selection: component numbers from 1 (None: all).  k: for components that
+        were loaded from a file."""
+        if k is not None:
+            _check(lib().mf_comps_set_k(comps.h, k))
+        sel = None if selection is None else np.ascontiguousarray(selection, dtype=np.uint32)
+        p = C.c_void_p()
+        _check(lib().mf_paths_create(self.h, comps.h, sel.ctypes.data if sel is not None else None, len(sel) if sel is not None else 0, min_len,
+                                     max_paths, C.byref(p)))
+        return Paths(self, p)
+
+    def component_paths(self, components_bin, k, files, out_dir, selection=None, min_len=50, max_paths=MAX_PATHS_COUNT):
+        """File form -> out_dir/component-<no>.seq.fasta; returns (components in the file, paths written)"""
+        files = list(files)
+        sel = None if selection is None else np.ascontiguousarray(selection, dtype=np.uint32)
+        nc, npth = C.c_uint64(), C.c_uint64()
+        _check(lib().mf_component_paths(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files),
+                                        sel.ctypes.data if sel is not None else None, len(sel) if sel is not None else 0, min_len, max_paths,
+                                        os.fsencode(out_dir), C.byref(nc), C.byref(npth)))
+        return nc.value, npth.value
 
     # ---- A12 ----
     def features(self, comps, sample_table, threshold=0, selected=None):
@@ -1251,6 +1284,67 @@ class Comps:
 
     def write(self, components_bin, stat_txt=None):
         _check(lib().mf_comps_write(self.h, os.fsencode(components_bin), _opt(stat_txt)))
+
+
+class Paths:
+    """The paths of the selected components (mf_paths_* in include/metafast_hip.h)"""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None and getattr(self.ctx, "h", None):
+            _lib.mf_paths_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, d_bases, d_offsets, n_seqs, n_bases):
+        _check(lib().mf_paths_add(self.h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_seqs, n_bases))
+
+    def finish(self):
+        _check(lib().mf_paths_finish(self.h))
+
+    def max_listings(self):
+        """the most selected components that list one k-mer (1: they share none)"""
+        m = C.c_uint64()
+        _check(lib().mf_paths_stats(self.h, None, None, None, C.byref(m)))
+        return m.value
+
+    def slots(self):
+        """after finish() -> (component numbers, paths, bytes of text, count reached max_paths), one entry per slot"""
+        n = C.c_uint64()
+        _check(lib().mf_paths_stats(self.h, C.byref(n), None, None, None))
+        n = n.value
+        no, cnt, nb, cap = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint8)
+        _check(lib().mf_paths_slots(self.h, no.ctypes.data, cnt.ctypes.data, nb.ctypes.data, cap.ctypes.data))
+        return no[:n], cnt[:n], nb[:n], cap[:n].astype(bool)
+
+    def text(self, slot=-1):
+        """after finish(): the text of one slot, or of all of them one after the other (slot = -1), as bytes"""
+        n = C.c_uint64()
+        _check(lib().mf_paths_text(self.h, slot, None, 0, C.byref(n)))
+        buf = np.zeros(max(n.value, 1), np.uint8)
+        _check(lib().mf_paths_text(self.h, slot, buf.ctypes.data, n.value, None))
+        return buf[:n.value].tobytes()
+
+    def files(self):
+        """after finish() -> {file name: bytes}, as mf_paths_write names them"""
+        no, _, nb, _ = self.slots()
+        whole, at, out = self.text(), 0, {}
+        for i in range(len(no)):
+            out[f"component-{int(no[i])}.seq.fasta"] = whole[at:at + int(nb[i])]
+            at += int(nb[i])
+        return out
+
+    def write(self, out_dir):
+        n = C.c_uint64()
+        _check(lib().mf_paths_write(self.h, os.fsencode(out_dir), C.byref(n)))
+        return n.value
 
 
 class DistCutter:
