@@ -593,6 +593,34 @@ int mf_stats_kmers3_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *co
 /* File form: as mf_stats_kmers -> <out_dir>/filtered_chisquared.kmers.bin + .stat.txt, filtered_group{A,B,C}.kmers.bin */
 int mf_stats_kmers3(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, const char *const *c_files, int nc,
                     int max_bad, double p_chi2, double p_mw, const char *out_dir, uint64_t *counters);
+/* SpecificKmersFinder.runImpl (src/tools/SpecificKmersFinder.java:65-245), samples numbered A first, then B; every sample is read at
+ * threshold 0 and the decision is made on its RAW counts c_j(x) (absent = 0).  Per k-mer x of the union, in the reference's order:
+ * unique (held by one group only) is counted; x is scarce when the count of the FIRST sample that holds it is <= ceil(N * 0.05) -- a
+ * count against a bound made from the number of samples, reproduced as it is --; else the two-group chi-squared test on (n1A, n1B) at
+ * p_chi2 (1 degree of freedom), which an x that EVERY sample holds passes whatever its statistic; then (p_mw > 0) Mann-Whitney on the raw
+ * counts, x is dropped when p > p_mw (kept at p == p_mw); the kept go to A with (short)(int)mean(A) when mean(A) > mean(B), else to B
+ * with (short)(int)mean(B).  No chi-squared list is written.  counters[MF_SPECIFIC_COUNTERS], indexed by the enum below (the log lines
+ * :202-216).  1 <= |A|, 1 <= |B|, |A| + |B| <= 1024; a key >= 2^62 is an error. */
+#define MF_SPECIFIC_COUNTERS 8
+enum { MF_SPECIFIC_TOTAL = 0, MF_SPECIFIC_UNIQUE = 1, MF_SPECIFIC_SCARCE = 2, MF_SPECIFIC_SKIP_CHI2 = 3, MF_SPECIFIC_SKIP_MW = 4,
+       MF_SPECIFIC_UNIQUE_LEFT = 5, MF_SPECIFIC_GROUP_A = 6, MF_SPECIFIC_GROUP_B = 7 };
+int mf_specific_kmers_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *const *b, int nb, double p_chi2, double p_mw,
+                             mf_table **group_a, mf_table **group_b, uint64_t *counters);
+/* File form: each file loaded like IOUtils.loadKmers([file], 0) -> <out_dir>/filtered_groupA.kmers.bin, filtered_groupB.kmers.bin in
+ * ascending key order (the reference's order is its hash map's); counters may be NULL. */
+int mf_specific_kmers(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, double p_chi2, double p_mw,
+                      const char *out_dir, uint64_t *counters);
+/* SpecificKmers3GroupsFinder.runImpl (src/tools/SpecificKmers3GroupsFinder.java:70-280): mf_stats_kmers3_tables at threshold 0 with these
+ * differences -- the chi-squared threshold is the quantile of 1 degree of freedom, not 2; no chi-squared list; F_j = the sum of sample
+ * j's (bounded) counts and M = (sum of all F_j) / N in integer arithmetic; v_j = (c_j * M) / F_j for a sample that holds x and 0 for one
+ * that does not (no NaN from an empty sample); unique left = kept and held by one group only.  counters[MF_SPECIFIC3_COUNTERS] in the
+ * order of MF_STATS3_COUNTERS. */
+#define MF_SPECIFIC3_COUNTERS 10
+int mf_specific_kmers3_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *const *b, int nb, mf_table *const *c, int nc, double p_chi2,
+                              double p_mw, mf_table **group_a, mf_table **group_b, mf_table **group_c, uint64_t *counters);
+/* File form -> <out_dir>/filtered_group{A,B,C}.kmers.bin */
+int mf_specific_kmers3(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, const char *const *c_files, int nc,
+                       double p_chi2, double p_mw, const char *out_dir, uint64_t *counters);
 /* KmersGroupedSamplesCounter.runImpl (src/tools/KmersGroupedSamplesCounter.java:82-190): for every k-mer x of `kmers` the number of
  * tables of each group (CD, UC, nonIBD; a group may be empty, at most 1022 tables in one) whose count of x is > max_bad.  *n = the
  * entries of `kmers`, whatever `cap` is; with cap >= *n, keys[0 .. *n) = the k-mers in ASCENDING order (the reference's order is its hash
@@ -655,6 +683,16 @@ int mf_unique_kmers_multi_tables(mf_ctx *ctx, mf_table *const *inputs, int n_inp
  * those > b) -> <out_dir>/filtered_<i>.kmers.bin for the i above */
 int mf_unique_kmers_multi(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters, int max_bad,
                           int k, int min_samples, int max_samples, const char *out_dir, int *n_out, uint64_t *n_union, uint64_t *counts);
+/* UniqueKmersFinder.runImpl (src/tools/UniqueKmersFinder.java:73-144): the inputs are POOLED into one map -- pooled(x) = the sum of the
+ * inputs' counts of x that are > b, bounded at 32767 (IOUtils.loadKmers over all files: the threshold is per record, the add saturates);
+ * an x that a filter table holds with count > b is zeroed.  *out = the records (x, pooled(x)) that are left, *n_pooled = the size of the
+ * pooled map, zeroed k-mers included (hm.size()).  b >= 0; at most 32767 inputs; a key >= 2^62 in any table is an error. */
+int mf_unique_kmers_tables(mf_ctx *ctx, mf_table *const *inputs, int n_inputs, mf_table *const *filters, int n_filters, int max_bad,
+                           mf_table **out, uint64_t *n_pooled);
+/* File form -> kmers_bin and stat_txt (may be NULL: IOUtils.printKmers of the pooled map at b -- the histogram counts the zeroed k-mers
+ * under 0); *n_good (may be NULL) = records written, *n_pooled may be NULL.  1 <= k <= 31. */
+int mf_unique_kmers(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters, int max_bad, int k,
+                    const char *kmers_bin, const char *stat_txt, uint64_t *n_pooled, uint64_t *n_good);
 /* IOUtils.MultipleFiltersAndPrintKmers (src/io/IOUtils.java:125-213) for one input table: every entry (x, v) with v > b gets the triple
  * (cd(x), uc(x), nonibd(x)) of the three filter tables' counts (entries with count > 0; absent = 0); *kept = the entries with a non-zero
  * triple.  The distinct triples, packed cd << 32 | uc << 16 | nonibd, come in ascending order (Triple.compareTo) with the number of

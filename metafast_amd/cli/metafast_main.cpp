@@ -41,6 +41,11 @@ extern "C" int mf_kmers_multiple_filters(mf_ctx *, const char *const *, int, con
                                          int, int, const char *const *, const char *const *, uint64_t *) __attribute__((weak));
 extern "C" int mf_stats_kmers3(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, int, double, double, const char *,
                                uint64_t *) __attribute__((weak));
+extern "C" int mf_specific_kmers(mf_ctx *, const char *const *, int, const char *const *, int, double, double, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_specific_kmers3(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, double, double, const char *,
+                                  uint64_t *) __attribute__((weak));
+extern "C" int mf_unique_kmers(mf_ctx *, const char *const *, int, const char *const *, int, int, int, const char *, const char *, uint64_t *, uint64_t *)
+    __attribute__((weak));
 extern "C" int mf_kmers_grouped_count(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int, int,
                                       int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_per_sample(mf_ctx *, const char *const *, int, int, int, int, const char *, uint64_t *) __attribute__((weak));
@@ -198,12 +203,13 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
         if (s == "i") {
             if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
             if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample" || tool == "comp2graph") return "k-mers";
+                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample" || tool == "comp2graph" ||
+                tool == "unique-kmers") return "k-mers";
             if (tool == "component-cutter" || tool == "seq2comp") return "sequences";
             return "reads";
         }
         if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                              tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "stats-kmers-3" || tool == "kmers-grouped-counter")
+                              tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "stats-kmers-3" || tool == "kmers-grouped-counter" || tool == "unique-kmers")
                                  ? "maximal-bad-frequence" : "maximal-bad-frequency";
         if (tool == "component-paths") {                                   // ComponentPathsMain.java:52-71 (features-calculator: -cm is the components' file)
             if (s == "cm") return "components";
@@ -909,8 +915,11 @@ static const char *TOOLS_TEXT =
     "kmers-samples-counter\tCount number of samples containing k-mers from multiple samples\n"
     "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
     "stats-kmers-3\t\tFind k-mers that differ significantly between three groups of samples (chi-squared + Mann-Whitney)\n"
+    "specific-kmers\t\tOutput k-mers specific to groups of samples based on chi-squared & Mann-Whitney tests\n"
+    "specific-kmers-3\tOutput k-mers specific to each of three groups of samples based on chi-squared & Mann-Whitney tests\n"
     "kmers-grouped-counter\tCount number of samples from 3 groups containing specified k-mers\n"
     "kmers-per-sample\tCounts the abundance of frequent k-mers from dataset in each sample\n"
+    "unique-kmers\t\tOutput k-mers present in one dataset and missing in other\n"
     "unique-kmers-multi\tOutput k-mers present in one dataset in fixed number of samples and missing in other\n"
     "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
     "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
@@ -979,6 +988,17 @@ static vector<PV> tool_inputs(const string &tool, const Args &a, const string &w
         v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV::files("c-kmers", a.list("c-kmers")),
              PV("p-value-chi2", a.get("p-value-chi2", "0.05")), PV("p-value-mw", a.get("p-value-mw", "0.05")),
              PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")), PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
+    } else if (tool == "specific-kmers") {                                 // (SpecificKmersFinder.java:30-57: no maximal-bad-frequence)
+        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV("p-value-chi2", a.get("p-value-chi2", "0.05")),
+             PV("p-value-mw", a.get("p-value-mw", "0.05")), PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
+    } else if (tool == "specific-kmers-3") {
+        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV::files("c-kmers", a.list("c-kmers")),
+             PV("p-value-chi2", a.get("p-value-chi2", "0.05")), PV("p-value-mw", a.get("p-value-mw", "0.05")),
+             PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
+    } else if (tool == "unique-kmers") {
+        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
+             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
+             PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
     } else if (tool == "kmers-grouped-counter") {
         v = {opt_i("k"), PV::files("kmers-file", a.list("kmers-file")), PV::files("cd-kmers", a.list("cd-kmers")), PV::files("uc-kmers", a.list("uc-kmers")),
              PV::files("nonibd-kmers", a.list("nonibd-kmers")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
@@ -1037,7 +1057,8 @@ int main(int argc, char **argv) {
     static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
                                   "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
                                   "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "seq2comp", "component-paths", "comp2graph", "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
+                                  "stats-kmers-3", "specific-kmers", "specific-kmers-3", "unique-kmers", "seq2comp", "component-paths", "comp2graph",
+                                  "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
     if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
@@ -1110,6 +1131,9 @@ int main(int argc, char **argv) {
     else if (tool == "kmers-samples-counter") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "stats-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
     else if (tool == "stats-kmers-3") { need("a-kmers", "A"); need("b-kmers", "B"); need("c-kmers", "C"); }
+    else if (tool == "specific-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
+    else if (tool == "specific-kmers-3") { need("a-kmers", "A"); need("b-kmers", "B"); need("c-kmers", "C"); }
+    else if (tool == "unique-kmers") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
     else if (tool == "kmers-grouped-counter") { need("k", "k"); need("cd-kmers", "cd"); need("uc-kmers", "uc"); need("nonibd-kmers", "nonibd"); }
     else if (tool == "kmers-per-sample") { need("k", "k"); need("k-mers", "i"); }
     else if (tool == "unique-kmers-multi") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
@@ -1272,6 +1296,87 @@ int main(int argc, char **argv) {
         logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
         logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
         outs = {PV::file("filtered-kmers-file", out_dir + "/filtered_chisquared.kmers.bin")};
+    } else if (tool == "specific-kmers") {
+        // SpecificKmersFinder.java:65-216 (no -k and no -b: every file is read at threshold 0).  What the library refuses is refused here
+        // first, in its words.
+        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers");
+        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
+        const string out_dir = a.get("output-dir", wd + "/kmers");
+        if (af.empty() || bf.empty()) die("specific-kmers: both groups need at least one sample (|A| = %zu, |B| = %zu)", af.size(), bf.size());
+        if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
+        mkdirs(out_dir);
+        if (!mf_specific_kmers) die("specific-kmers: this build of the library has no mf_specific_kmers");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("INFO", "Splitting k-mers...");
+        auto pa = cptrs(af), pb = cptrs(bf);
+        uint64_t c[MF_SPECIFIC_COUNTERS] = {0};
+        check(mf_specific_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pchi2, pmw, out_dir.c_str(), c));
+        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
+        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
+        logmsg("INFO", "Total specific k-mers in Group A = %llu", (unsigned long long)c[MF_SPECIFIC_GROUP_A]);
+        logmsg("INFO", "Total specific k-mers in Group B = %llu", (unsigned long long)c[MF_SPECIFIC_GROUP_B]);
+        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[MF_SPECIFIC_UNIQUE]);
+        logmsg("DEBUG", "Total scarce k-mers = = %llu", (unsigned long long)c[MF_SPECIFIC_SCARCE]);
+        logmsg("DEBUG", "Total skipped by chi-squared test = %llu", (unsigned long long)c[MF_SPECIFIC_SKIP_CHI2]);
+        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[MF_SPECIFIC_SKIP_MW]);
+        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[MF_SPECIFIC_UNIQUE_LEFT]);
+        logmsg("DEBUG", "Total kmers left = %llu", (unsigned long long)(c[MF_SPECIFIC_GROUP_A] + c[MF_SPECIFIC_GROUP_B]));
+        logmsg("DEBUG", "Processed %llu k-mers", (unsigned long long)c[MF_SPECIFIC_TOTAL]);
+    } else if (tool == "specific-kmers-3") {
+        // SpecificKmers3GroupsFinder.java:70-280
+        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers"), cf = a.list("c-kmers");
+        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
+        const string out_dir = a.get("output-dir", wd + "/kmers");
+        if (af.empty() || bf.empty() || cf.empty())
+            die("specific-kmers-3: every group needs at least one sample (|A| = %zu, |B| = %zu, |C| = %zu)", af.size(), bf.size(), cf.size());
+        if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
+        mkdirs(out_dir);
+        if (!mf_specific_kmers3) die("specific-kmers-3: this build of the library has no mf_specific_kmers3");
+        mf_ctx *ctx = ctx_of(e, a);
+        logmsg("INFO", "Splitting k-mers...");
+        auto pa = cptrs(af), pb = cptrs(bf), pc = cptrs(cf);
+        uint64_t c[MF_SPECIFIC3_COUNTERS] = {0};
+        check(mf_specific_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), pchi2, pmw, out_dir.c_str(), c));
+        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
+        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
+        logmsg("INFO", "Group C k-mers printed to %s", (out_dir + "/filtered_groupC.kmers.bin").c_str());
+        logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
+        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
+        logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
+        logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7] + c[8]));
+        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[9]);
+        logmsg("DEBUG", "Total group A k-mers = %llu", (unsigned long long)c[6]);
+        logmsg("DEBUG", "Total group B k-mers = %llu", (unsigned long long)c[7]);
+        logmsg("DEBUG", "Total group C k-mers = %llu", (unsigned long long)c[8]);
+        logmsg("INFO", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
+        logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
+        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
+    } else if (tool == "unique-kmers") {
+        // UniqueKmersFinder.java:73-144: the pooled k-mers of the input files that no filter file holds
+        check_k(k);
+        const int b = a.geti("maximal-bad-frequence", 1);
+        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
+        const vector<string> files = a.list("k-mers"), filt = a.list("filter-kmers");
+        if (!mf_unique_kmers) die("unique-kmers: this build of the library has no mf_unique_kmers");
+        mf_ctx *ctx = ctx_of(e, a);
+        mkdirs(out_dir); mkdirs(st_dir);
+        auto fp = cptrs(files), ff = cptrs(filt);
+        const string out = out_dir + "/filtered.kmers.bin", st = st_dir + "/filtered.stat.txt";
+        uint64_t n = 0, c = 0;
+        logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
+        check(mf_unique_kmers(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, out.c_str(), st.c_str(), &n, &c));
+        char pct[64];
+        if (n) snprintf(pct, sizeof pct, "%.1f", c * 100.0 / n); else snprintf(pct, sizeof pct, "NaN");
+        logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n).c_str(),
+               group_digits(c).c_str(), pct);
+        if (n == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
+        else if (c == 0 || c < (uint64_t)(int64_t)(n * 0.03))
+            logmsg("WARN", "Too few good k-mers were found! Perhaps you should decrease k-mer size or --maximal-bad-frequency value");
+        const uint64_t all_kmers = (1ull << (2 * k)) / 2;                   // (4^k)/2
+        if (n == all_kmers) logmsg("WARN", "All possible k-mers were found in reads! Perhaps you should increase k-mer size");
+        else if (n >= (uint64_t)(int64_t)(all_kmers * 0.99)) logmsg("WARN", "Almost all possible k-mers were found in reads! Perhaps you should increase k-mer size");
+        logmsg("INFO", "Good k-mers printed to %s", out.c_str());
+        outs = {PV::file("resulting-kmers-file", out)};
     } else if (tool == "kmers-grouped-counter") {
         // KmersGroupedSamplesCounter.java:82-190: per k-mer of -kf the CD, UC and nonIBD files that hold it with a count > b
         check_k(k);

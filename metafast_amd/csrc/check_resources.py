@@ -7,7 +7,7 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_cp_")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_cp_|k_specific|k_uk_")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
 # column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip; one thread per run of positions, per
 # run, per record, or one wave per record: mf_comppaths.hip)
@@ -23,7 +23,10 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
                           "k_s2c_shift"],
           "mf_comppaths": ["k_cp_select", "k_cp_members", "k_cp_heads", "k_cp_distinct", "k_cp_maxlist", "k_cp_split", "k_cp_join", "k_cp_sizes", "k_cp_mark",
                            "k_cp_pair", "k_cp_keep", "k_cp_bump", "k_cp_records", "k_cp_copy", "k_cp_keys", "k_cp_widths", "k_cp_slot_bytes",
-                           "k_cp_write_head", "k_cp_write_bases"]}
+                           "k_cp_write_head", "k_cp_write_bases"],
+          # (the row kernels of specific-kmers and specific-kmers-3 keep a row in LDS: a spill would cost them their occupancy)
+          "mf_specific": ["k_specific_select", "k_specific_gather", "k_specific_rows_thread", "k_specific_rows_wave"],
+          "mf_stats": ["k_specific3_rows_thread", "k_specific3_rows_wave"], "mf_kmersets": ["k_uk_knock"]}
 
 
 def main():

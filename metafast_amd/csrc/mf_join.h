@@ -1,8 +1,9 @@
 // mf_join.h -- the join core of the cohort tools ("the join core"; kernels and host helpers: mf_join.hip).
 // Every tool streams its samples, once per hash slice of the key space, into an HBM open-addressed union table of 16-byte slots and
 // reads the table out again.  A tool brings its union mode and per-sample `add` words, a projection for the read-out, and its own
-// post-pass: mf_stats.hip (stats-kmers, stats-kmers-3, kmers-samples-counter, kmers-grouped-counter), mf_kmersets.hip
-// (unique-kmers-multi, kmers-multiple-filters), mf_color.hip (kmers-color), mf_kps.hip (kmers-per-sample).
+// post-pass: mf_stats.hip (stats-kmers, stats-kmers-3, specific-kmers-3, kmers-samples-counter, kmers-grouped-counter), mf_specific.hip
+// (specific-kmers), mf_kmersets.hip (unique-kmers, unique-kmers-multi, kmers-multiple-filters), mf_color.hip (kmers-color), mf_kps.hip
+// (kmers-per-sample).
 #pragma once
 #include "mf_common.h"
 #include <functional>
@@ -88,6 +89,16 @@ struct mf_read_ukm {               // unique-kmers-multi: not knocked out and (s
         return !(sw & MF_UKM_KNOCKED) && (int)(int16_t)(uint16_t)sw > thr;
     }
     __device__ __forceinline__ value val(ulonglong2 raw) const { return (uint32_t)((raw.y >> 32) & 0xFFFFu) | ((uint32_t)raw.y << 16); }
+};
+struct mf_read_uk {                // unique-kmers: every entry -> its pooled value, the sum bounded at 32767 (addAndBound), 0 where knocked out
+    using value = uint16_t;
+    static constexpr bool all = true;
+    static constexpr const char *tool = "unique-kmers", *timer = "k_uk_read";
+    __device__ __forceinline__ bool keep(ulonglong2) const { return true; }
+    __device__ __forceinline__ value val(ulonglong2 raw) const {
+        const uint32_t sw = (uint32_t)(raw.y >> 32);
+        return (sw & MF_UKM_KNOCKED) ? (uint16_t)0 : (uint16_t)(sw < 32767u ? sw : 32767u);
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------

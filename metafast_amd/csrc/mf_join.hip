@@ -189,6 +189,7 @@ template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const 
 template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_kps &, mf_join_parts<uint64_t, uint16_t> &);
 template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_color &, mf_join_parts<uint64_t, uint64_t> &);
 template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_ukm &, mf_join_parts<uint64_t, uint32_t> &);
+template int mf_join_read(mf_ctx *, const mf_uslot *, uint64_t, uint64_t, const mf_read_uk &, mf_join_parts<uint64_t, uint16_t> &);
 
 int pairs_to_table(mf_ctx *ctx, mf_buf<uint64_t> &keys, mf_buf<uint16_t> &vals, uint64_t n, mf_table **out) {
     const int k = 31;

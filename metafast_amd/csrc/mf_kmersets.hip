@@ -4,6 +4,8 @@
 //   unique-kmers-multi      union (MF_UNION_SUM) of the inputs; the filter samples' keys knock slots out (bit 31 of the sum word);
 //                           one read-out of (key, (short)sum, samples) with (short)sum > b; one sort by key; filtered_<i> = the
 //                           subsequence with samples >= i, by an order-keeping compaction.
+//   unique-kmers            (UniqueKmersFinder.java:73-144) the same union with the sum BOUNDED at 32767 where it is
+//                           read: the inputs pooled into one map; one read-out of every slot, knocked-out ones with value 0.
 //   kmers-multiple-filters  probe table {key, cd, uc, nonibd} (MF_UNION_FIELD) of the three filter tables; per input sample one
 //                           probe per entry: the kept records and every entry's triple packed into 48 bits; the histogram is the
 //                           sort of the packed triples and a run-length pass.
@@ -22,6 +24,24 @@ __global__ __launch_bounds__(256) void k_ukm_knock(mf_uslot *__restrict__ slots,
         ulonglong2 raw;
         const uint64_t p = mf_join_find(slots, mask, k.h, key, &raw);
         if (p != MF_JOIN_NOT_FOUND && (int)(int16_t)(uint16_t)(raw.y >> 32) > thr) atomicOr(&slots[p].row, MF_UKM_KNOCKED);
+    }
+}
+
+// unique-kmers (UniqueKmersFinder.java:91-105): k_ukm_knock's probe with the pooled map's BOUNDED sum in the test where that one wraps --
+// the pool is one map filled by addAndBound, so 3 x 20000 is 32767 here and -5536 there
+__global__ __launch_bounds__(256) void k_uk_knock(mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys,
+                                                  const uint16_t *__restrict__ cnts, uint64_t n, int thr, uint32_t S, uint32_t s,
+                                                  unsigned int *__restrict__ flags) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if ((int)cnts[i] <= thr) continue;
+        const uint64_t key = keys[i];
+        const mf_join_key k = mf_join_mine<true>(key, S, s, flags);
+        if (!k.mine) continue;
+        ulonglong2 raw;
+        const uint64_t p = mf_join_find(slots, mask, k.h, key, &raw);
+        if (p == MF_JOIN_NOT_FOUND) continue;
+        const uint32_t sum = (uint32_t)(raw.y >> 32) & ~MF_UKM_KNOCKED;
+        if ((int)(sum < 32767u ? sum : 32767u) > thr) atomicOr(&slots[p].row, MF_UKM_KNOCKED);
     }
 }
 
@@ -171,6 +191,78 @@ extern "C" int mf_unique_kmers_multi(mf_ctx *ctx, const char *const *in_files, i
     }
     if (rc == MF_OK) { for (size_t i = 0; i < cs.size(); i++) counts[i] = cs[i]; *n_out = (int)cs.size(); }
     destroy_all(outs);
+    return rc;
+}
+
+// ---- unique-kmers (UniqueKmersFinder.java:73-144) ----
+// The inputs are POOLED: IOUtils.loadKmers(files, b) keeps the RECORDS with a value > b (the threshold is per record, not on the sum:
+// a k-mer with count 1 in two files is not there at b = 1) and adds them into one map with addAndBound (the sum stops at 32767).  Every
+// filter file, loaded alone at b, zeroes the pooled k-mers it holds.  -> hm: the whole pooled map, the zeroed k-mers with value 0 (what
+// printKmers walks: its histogram counts them, its records leave them out)
+static int uk_join(mf_ctx *ctx, const mf_join_get &get_in, int n_in, const mf_join_get &get_f, int n_f, uint64_t total, int b, mf_table **hm) {
+    uint32_t S = 1; uint64_t cap = 0;
+    MF_TRY(plan_slices(ctx, total, &S, &cap));
+    mf_join_parts<uint64_t, uint16_t> parts;
+    mf_buf<unsigned int> flags; MF_TRY(flags.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(flags.p, 0, 4, ctx->stream));
+    const std::vector<uint32_t> add((size_t)n_in, 0u);
+    for (uint32_t s = 0; s < S; s++) {
+        mf_buf<mf_uslot> slots; uint64_t nu = 0;
+        MF_TRY(mf_join_union(ctx, get_in, n_in, b, MF_UNION_SUM, add.data(), S, s, cap, slots, &nu));
+        for (int j = 0; j < n_f; j++)
+            MF_TRY(mf_join_pass(ctx, get_f, j, "unique-kmers: filter pass", [&](const mf_table *t) {
+                mf_ktimer tm(ctx, "k_uk_knock");
+                k_uk_knock<<<grid_for(ctx, t->n), 256, 0, ctx->stream>>>(slots.p, cap - 1, t->d_keys, t->d_counts, t->n, b, S, s, flags.p);
+            }));
+        MF_TRY(mf_join_read(ctx, slots.p, cap, nu, mf_read_uk{}, parts));
+    }
+    MF_TRY(mf_join_flags(ctx, flags.p, "unique-kmers"));
+    mf_buf<uint64_t> keys; mf_buf<uint16_t> vals; uint64_t n = 0;
+    MF_TRY(parts.concat(ctx, keys, vals, &n));
+    return pairs_to_table(ctx, keys, vals, n, hm);
+}
+static int uk_check(int n_in, int max_bad) {
+    if (max_bad < 0) return mf_set_error("unique-kmers: maximal-bad-frequence = %d is negative", max_bad);
+    if (n_in > 32767) return mf_set_error("unique-kmers: %d input files, at most 32767 (the pooled sum is kept in 31 bits)", n_in);
+    return MF_OK;
+}
+
+extern "C" int mf_unique_kmers_tables(mf_ctx *ctx, mf_table *const *inputs, int n_inputs, mf_table *const *filters, int n_filters, int max_bad,
+                                      mf_table **out, uint64_t *n_pooled) {
+    mf_range rng_("mf:unique_kmers");
+    if (!ctx || !out || !n_pooled || (n_inputs && !inputs) || (n_filters && !filters) || n_inputs < 0 || n_filters < 0)
+        return mf_set_error("mf_unique_kmers_tables: NULL argument");
+    *out = nullptr;
+    MF_TRY(uk_check(n_inputs, max_bad));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    MF_TRY(tables_total(ctx, inputs, n_inputs, "mf_unique_kmers_tables (inputs)", &total));
+    MF_TRY(tables_total(ctx, filters, n_filters, "mf_unique_kmers_tables (filters)", nullptr));
+    mf_table *hm = nullptr;
+    MF_TRY(uk_join(ctx, mf_join_tables(inputs), n_inputs, mf_join_tables(filters), n_filters, total, max_bad, &hm));
+    *n_pooled = hm->n;
+    const int rc = mf_table_filter(hm, max_bad, out);
+    mf_table_destroy(hm);
+    return rc;
+}
+
+extern "C" int mf_unique_kmers(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters, int max_bad, int k,
+                               const char *kmers_bin, const char *stat_txt, uint64_t *n_pooled, uint64_t *n_good) {
+    mf_range rng_("mf:unique_kmers(files)");
+    if (!ctx || !kmers_bin || (n_inputs && !in_files) || (n_filters && !filter_files) || n_inputs < 0 || n_filters < 0)
+        return mf_set_error("mf_unique_kmers: NULL argument");
+    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    MF_TRY(uk_check(n_inputs, max_bad));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0, tf = 0;
+    MF_TRY(file_records(in_files, n_inputs, &total));
+    MF_TRY(file_records(filter_files, n_filters, &tf));
+    mf_table *hm = nullptr;
+    MF_TRY(uk_join(ctx, mf_join_files(in_files, max_bad, k), n_inputs, mf_join_files(filter_files, max_bad, k), n_filters, total, max_bad, &hm));
+    uint64_t w = 0;
+    const int rc = mf_table_write_kmers(hm, max_bad, kmers_bin, stat_txt, &w);
+    if (rc == MF_OK) { if (n_pooled) *n_pooled = hm->n; if (n_good) *n_good = w; }
+    mf_table_destroy(hm);
     return rc;
 }
 

@@ -1,0 +1,29 @@
+// mf_stats.h -- what the group-comparison tools share beside the join core: the limits of a row, the wave counter, Java's cast, and the
+// host's decision tables (defined in mf_stats.hip; used there and by mf_specific.hip).
+#pragma once
+#include "mf_join.h"
+
+#define MF_STATS_MAX_N 1024          // samples of one stats-kmers run (the row kernels keep a row's values in LDS)
+#define MF_STATS_THREAD_N 32         // up to this many samples: one thread per row (values in LDS, 64 KiB per 256 rows), else a wave per row
+
+// wave sum of a per-lane counter into a 64-bit global counter
+__device__ __forceinline__ void mf_stats_add(unsigned long long *ctr, uint32_t x) {
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
+    if (mf_lane() == 0 && x) atomicAdd(ctr, (unsigned long long)x);
+}
+// Java's (short)(int)x: NaN -> 0, saturation to int, low 16 bits (JLS 5.1.3)
+__device__ __forceinline__ uint16_t mf_java_short(double x) {
+    int32_t i;
+    if (x != x) i = 0;
+    else if (x >= 2147483647.0) i = 2147483647;
+    else if (x <= -2147483648.0) i = (-2147483647 - 1);
+    else i = (int32_t)x;                                  // (in range: truncation toward zero)
+    return (uint16_t)(uint32_t)i;
+}
+
+// the two-group chi-squared decision (StatsKmersFinder.chisq = SpecificKmersFinder.chisq) and the quantile with 1 degree of freedom
+bool chisq_keep(float c0, float c1, float p0, float p1, double value);
+double chi2_1_quantile(double p_chi2);
+// the smallest 2 * Umin in [0, nA nB] whose p is not < pmw (or_equal: whose p is > pmw); nA nB + 1: every row passes
+uint32_t mw_threshold(int na, int nb, double pmw, bool or_equal = false);
+int mf_stats_check_p(double pchi2);

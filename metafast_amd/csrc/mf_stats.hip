@@ -1,6 +1,7 @@
 // mf_stats.hip -- stats-kmers (src/tools/StatsKmersFinder.java:89-297), stats-kmers-3 (src/tools/StatsKmers3GroupsFinder.java:92-377),
 // kmers-samples-counter (src/tools/KmersSamplesCounter.java:69-140) and kmers-grouped-counter
-// (src/tools/KmersGroupedSamplesCounter.java:82-190) on the join core (mf_join.h).
+// (src/tools/KmersGroupedSamplesCounter.java:82-190) on the join core (mf_join.h); specific-kmers-3
+// (src/tools/SpecificKmers3GroupsFinder.java:70-313) is a mode of the three-group join.
 //
 // Passes:
 //   union   every sample's keys with count > b go into an HBM open-addressed table of 16-byte slots {key, presence, row}; the
@@ -19,22 +20,14 @@
 // No floating point of the decisions but v_j and the means runs on the device, and those are IEEE double operations in the
 // reference's order (no contraction in this file).
 #pragma clang fp contract(off)
-#include "mf_join.h"
+#include "mf_stats.h"
 #include <algorithm>
 #include <cmath>
 
-#define MF_STATS_MAX_N 1024          // samples of one stats-kmers run (the row kernels keep a row's values in LDS)
-#define MF_STATS_THREAD_N 32         // up to this many samples: one thread per row (values in LDS, 64 KiB per 256 rows), else a wave per row
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------------------------------
-// wave sum of a per-lane counter into a 64-bit global counter
-__device__ __forceinline__ void mf_stats_add(unsigned long long *ctr, uint32_t x) {
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
-    if (mf_lane() == 0 && x) atomicAdd(ctr, (unsigned long long)x);
-}
-
 // stats-kmers pass 1 over the union (StatsKmersFinder.java:129-162): counters [0] n, [1] scarce, [2] in all, [3] unique, [4] chi-squared
 // rejected; survivors get row numbers and their keys go to rkeys.  (uniform trip count: every lane reaches mf_wave_reserve)
 __global__ __launch_bounds__(256) void k_stats_select(mf_uslot *__restrict__ slots, uint64_t cap, const uint8_t *__restrict__ chi_keep, int na, int nb,
@@ -126,15 +119,6 @@ struct mf_stats_row_args {
     unsigned int *cur;                                    // [0] A, [1] B
     unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] unique left
 };
-// Java's (short)(int)x: NaN -> 0, saturation to int, low 16 bits (JLS 5.1.3)
-__device__ __forceinline__ uint16_t mf_java_short(double x) {
-    int32_t i;
-    if (x != x) i = 0;
-    else if (x >= 2147483647.0) i = 2147483647;
-    else if (x <= -2147483648.0) i = (-2147483647 - 1);
-    else i = (int32_t)x;                                  // (in range: truncation toward zero)
-    return (uint16_t)(uint32_t)i;
-}
 // decision + output of one row: group 0 (A) / 1 (B) / -1 (rejected by the Mann-Whitney test) and the value
 __device__ __forceinline__ int mf_stats_group(bool pass, double meanA, double meanB, uint16_t *val) {
     if (!pass) return -1;
@@ -370,6 +354,96 @@ __global__ __launch_bounds__(256) void k_stats3_rows_wave(mf_stats3_row_args a) 
     mf_stats3_flush(a.ctr, c_mw, c_a, c_b, c_c, c_ul);
 }
 
+// ---- specific-kmers-3 (SpecificKmers3GroupsFinder.java:166-254): the rows of k_stats3_rows_*, decided its way ----
+// A sample that does not hold the k-mer contributes 0, not 0 * M / F_j (:173-199): an empty sample (F_j = 0) gives no NaN, so no pair has
+// a NaN rule to apply.  Unique left is the presence test of :207 on the gathered row (a count of 0 = absent: every load is at threshold
+// 0), not a test of the means -- M may be 0 (truncated), and then every mean is.
+__device__ __forceinline__ double mf_specific3_value(uint16_t c, double M, double F) { return c ? ((double)c * M) / F : 0.0; }
+__device__ __forceinline__ bool mf_specific3_unique(uint32_t n1a, uint32_t n1b, uint32_t n1c) { return n1a + n1c == 0 || n1b + n1a == 0 || n1b + n1c == 0; }
+
+// one thread per row, the layout of k_stats_rows_thread
+__global__ __launch_bounds__(256) void k_specific3_rows_thread(mf_stats3_row_args a) {
+    extern __shared__ double vs[];
+    const int nab = a.na + a.nb, N = nab + a.nc;
+    uint32_t c_mw = 0, c_a = 0, c_b = 0, c_c = 0, c_ul = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * blockDim.x; r0 < a.m; r0 += stride) {   // uniform trip count (mf_wave_reserve)
+        const uint64_t r = r0 + threadIdx.x;
+        int grp = -1; uint16_t val = 0;
+        if (r < a.m) {
+            double *v = vs + threadIdx.x;
+            const uint16_t *row = a.mat + r * (uint64_t)N;
+            uint32_t n1a = 0, n1b = 0, n1c = 0;
+            for (int j = 0; j < N; j++) {
+                const uint16_t c = row[j];
+                v[(size_t)j * 256] = mf_specific3_value(c, a.M, a.F[j]);
+                if (c) { if (j < a.na) n1a++; else if (j < nab) n1b++; else n1c++; }
+            }
+            const bool pass = !a.mw || mf_stats3_pair<256, 1>(v, 0, a.na, a.na, a.nb, false, a.Tab, 0) ||
+                              mf_stats3_pair<256, 1>(v, a.na, a.nb, nab, a.nc, false, a.Tbc, 0) ||
+                              mf_stats3_pair<256, 1>(v, 0, a.na, nab, a.nc, false, a.Tac, 0);
+            double sa = 0.0, sb = 0.0, sc = 0.0;
+            for (int j = 0; j < a.na; j++) sa += v[(size_t)j * 256];
+            for (int j = a.na; j < nab; j++) sb += v[(size_t)j * 256];
+            for (int j = nab; j < N; j++) sc += v[(size_t)j * 256];
+            grp = mf_stats3_group(pass, sa / (double)a.na, sb / (double)a.nb, sc / (double)a.nc, &val);
+            c_mw += grp < 0; c_a += grp == 0; c_b += grp == 1; c_c += grp == 2;
+            c_ul += grp >= 0 && mf_specific3_unique(n1a, n1b, n1c);
+        }
+        const uint32_t ia = mf_wave_reserve(&a.cur[0], grp == 0 ? 1u : 0u);
+        const uint32_t ib = mf_wave_reserve(&a.cur[1], grp == 1 ? 1u : 0u);
+        const uint32_t ic = mf_wave_reserve(&a.cur[2], grp == 2 ? 1u : 0u);
+        if (grp == 0) { a.ka[ia] = a.rkeys[r]; a.va[ia] = val; }
+        else if (grp == 1) { a.kb[ib] = a.rkeys[r]; a.vb[ib] = val; }
+        else if (grp == 2) { a.kc[ic] = a.rkeys[r]; a.vc[ic] = val; }
+    }
+    mf_stats3_flush(a.ctr, c_mw, c_a, c_b, c_c, c_ul);
+}
+
+// one wave per row, the layout of k_stats3_rows_wave (32 KiB of LDS a block); the holders of a row are counted by the lanes and summed
+__global__ __launch_bounds__(256) void k_specific3_rows_wave(mf_stats3_row_args a) {
+    __shared__ double vs[4][MF_STATS_MAX_N];
+    const int nab = a.na + a.nb, N = nab + a.nc, w = threadIdx.x >> 6, lane = mf_lane();
+    double *v = vs[w];
+    uint32_t c_mw = 0, c_a = 0, c_b = 0, c_c = 0, c_ul = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * 4; r0 < a.m; r0 += (uint64_t)gridDim.x * 4) {   // block-uniform trip count
+        const uint64_t r = r0 + (uint64_t)w;
+        const bool live = r < a.m;
+        uint32_t n1 = 0;                                  // holders this lane saw: A | B << 10 | C << 20 (at most 1024 in all)
+        if (live) {
+            const uint16_t *row = a.mat + r * (uint64_t)N;
+            for (int j = lane; j < N; j += 64) {
+                const uint16_t c = row[j];
+                v[j] = mf_specific3_value(c, a.M, a.F[j]);
+                if (c) n1 += j < a.na ? 1u : j < nab ? 1u << 10 : 1u << 20;
+            }
+        }
+        __syncthreads();
+        for (int d = 32; d >= 1; d >>= 1) n1 += __shfl_xor(n1, d, 64);
+        bool pass = true;
+        if (live && a.mw)
+            pass = mf_stats3_pair<1, 64>(v, 0, a.na, a.na, a.nb, false, a.Tab, lane) ||
+                   mf_stats3_pair<1, 64>(v, a.na, a.nb, nab, a.nc, false, a.Tbc, lane) ||
+                   mf_stats3_pair<1, 64>(v, 0, a.na, nab, a.nc, false, a.Tac, lane);
+        if (live && lane == 0) {
+            double sa = 0.0, sb = 0.0, sc = 0.0;
+            for (int j = 0; j < a.na; j++) sa += v[j];
+            for (int j = a.na; j < nab; j++) sb += v[j];
+            for (int j = nab; j < N; j++) sc += v[j];
+            uint16_t val = 0;
+            const uint64_t key = a.rkeys[r];
+            const int grp = mf_stats3_group(pass, sa / (double)a.na, sb / (double)a.nb, sc / (double)a.nc, &val);
+            c_mw += grp < 0; c_a += grp == 0; c_b += grp == 1; c_c += grp == 2;
+            c_ul += grp >= 0 && mf_specific3_unique(n1 & 0x3FFu, (n1 >> 10) & 0x3FFu, n1 >> 20);
+            if (grp == 0) { const uint32_t i = atomicAdd(&a.cur[0], 1u); a.ka[i] = key; a.va[i] = val; }
+            else if (grp == 1) { const uint32_t i = atomicAdd(&a.cur[1], 1u); a.kb[i] = key; a.vb[i] = val; }
+            else if (grp == 2) { const uint32_t i = atomicAdd(&a.cur[2], 1u); a.kc[i] = key; a.vc[i] = val; }
+        }
+        __syncthreads();
+    }
+    mf_stats3_flush(a.ctr, c_mw, c_a, c_b, c_c, c_ul);
+}
+
 // kmers-grouped-counter: the presence word of every key of the -kf table that slice s holds (a key in no group keeps its 0)
 __global__ __launch_bounds__(256) void k_grouped_probe(const mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys, uint64_t n,
                                                        uint32_t S, uint32_t s, uint32_t *__restrict__ words, unsigned int *__restrict__ flags) {
@@ -385,7 +459,7 @@ __global__ __launch_bounds__(256) void k_grouped_probe(const mf_uslot *__restric
 // ---------------------------------------------------------------------------------------------------------------------------
 // host: the decisions' tables (StatsKmersFinder.chisq :300-316; commons-math3 3.6.1 MannWhitneyUTest.calculateAsymptoticPValue)
 // ---------------------------------------------------------------------------------------------------------------------------
-static bool chisq_keep(float c0, float c1, float p0, float p1, double value) {
+bool chisq_keep(float c0, float c1, float p0, float p1, double value) {
     float tmp = c0;
     c0 = 100 * c0 / (c0 + c1);
     c1 = 100 * c1 / (tmp + c1);
@@ -403,7 +477,7 @@ static bool chisq_keep(float c0, float c1, float p0, float p1, double value) {
     return value < kk;                                    // (NaN: rejected)
 }
 // ChiSquaredDistribution(1).inverseCumulativeProbability(1 - p): P(X > q) = erfc(sqrt(q / 2)) = 1 - (1 - p), by bisection
-static double chi2_1_quantile(double p_chi2) {
+double chi2_1_quantile(double p_chi2) {
     const double P = 1.0 - p_chi2, tail = 1.0 - P;
     if (P >= 1.0) return INFINITY;
     if (P <= 0.0) return 0.0;
@@ -457,10 +531,13 @@ static double mw_pvalue(double umin, int n1, int n2) {
     return 2 * cdf;
 }
 // p grows with Umin: the smallest 2 * Umin in [0, nA nB] whose p is not < pmw (nA nB + 1: every row passes)
-static uint32_t mw_threshold(int na, int nb, double pmw) {
+// (or_equal: the smallest whose p is > pmw -- specific-kmers keeps a row unless p > pmw, SpecificKmersFinder.java:166-170)
+uint32_t mw_threshold(int na, int nb, double pmw, bool or_equal) {
     const uint32_t top = (uint32_t)na * (uint32_t)nb;
-    for (uint32_t u2 = 0; u2 <= top; u2++)
-        if (!(mw_pvalue(u2 / 2.0, na, nb) < pmw)) return u2;
+    for (uint32_t u2 = 0; u2 <= top; u2++) {
+        const double p = mw_pvalue(u2 / 2.0, na, nb);
+        if (or_equal ? p > pmw : !(p < pmw)) return u2;
+    }
     return top + 1;
 }
 
@@ -471,13 +548,15 @@ static uint32_t mw_threshold(int na, int nb, double pmw) {
 using stats_get_counts = std::function<int(int j, mf_join_sample &, uint64_t *F)>;
 
 // the join of G = 2 (stats-kmers) or 3 (stats-kmers-3) groups of ng[0 .. G) samples, numbered group by group; grp_out[0 .. G) get the
-// groups' tables, counters MF_STATS_COUNTERS (G = 2) or MF_STATS3_COUNTERS values
+// groups' tables, counters MF_STATS_COUNTERS (G = 2) or MF_STATS3_COUNTERS values.  specific (G = 3 only): the decision of specific-kmers-3
+// (SpecificKmers3GroupsFinder.java:70-280) -- the quantile of 1 degree of freedom, M truncated to a long, an absent sample's value 0
+// whatever its F_j, unique-left by presence (k_specific3_rows_*); chi_out may then be NULL: the tool writes no chi-squared list
 static int stats_join(mf_ctx *ctx, const mf_join_get &get, const stats_get_counts &get_counts, const int *ng, int G, uint64_t total, int b, double pchi2,
-                      double pmw, mf_table **chi_out, mf_table **grp_out, uint64_t *counters) {
+                      double pmw, mf_table **chi_out, mf_table **grp_out, uint64_t *counters, bool specific = false) {
     const int na = ng[0], nb = ng[1], nc = G == 3 ? ng[2] : 0, N = na + nb + nc;
     const int n_ctr = G == 3 ? MF_STATS3_COUNTERS : MF_STATS_COUNTERS;
     // the decisions' tables (three groups: one byte per (n1A, n1B, n1C), at most 342^3 = 4 * 10^7 of them)
-    const double q = G == 3 ? chi2_2_quantile(pchi2) : chi2_1_quantile(pchi2);
+    const double q = G == 3 && !specific ? chi2_2_quantile(pchi2) : chi2_1_quantile(pchi2);
     std::vector<uint8_t> chi((size_t)(na + 1) * (nb + 1) * (nc + 1), 0);
     for (int n1a = 0; n1a <= na; n1a++)
         for (int n1b = 0; n1b <= nb; n1b++) {
@@ -541,7 +620,7 @@ static int stats_join(mf_ctx *ctx, const mf_join_get &get, const stats_get_count
         // rows
         uint64_t Fsum = 0;
         for (uint64_t x : F) Fsum += x;
-        const double M = (double)Fsum / N;
+        const double M = specific ? (double)(Fsum / (uint64_t)N) : (double)Fsum / N;   // (specific: meanSumKmers is a long, :147-151)
         std::vector<double> Fd((size_t)N);
         for (int j = 0; j < N; j++) Fd[(size_t)j] = (double)F[(size_t)j];
         mf_buf<double> dF; MF_TRY(dF.alloc(ctx, N));
@@ -565,7 +644,13 @@ static int stats_join(mf_ctx *ctx, const mf_join_get &get, const stats_get_count
                 }
             } else {
                 mf_stats3_row_args ra{mat.p, rkeys, m, na, nb, nc, dF.p, M, mw, T, Tbc, Tac, kg[0], kg[1], kg[2], vg[0], vg[1], vg[2], cur, ctr.p};
-                if (N <= MF_STATS_THREAD_N) {
+                if (specific && N <= MF_STATS_THREAD_N) {
+                    mf_ktimer tm(ctx, "k_specific3_rows_thread");
+                    k_specific3_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
+                } else if (specific) {
+                    mf_ktimer tm(ctx, "k_specific3_rows_wave");
+                    k_specific3_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
+                } else if (N <= MF_STATS_THREAD_N) {
                     mf_ktimer tm(ctx, "k_stats3_rows_thread");
                     k_stats3_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
                 } else {
@@ -593,7 +678,7 @@ static int stats_join(mf_ctx *ctx, const mf_join_get &get, const stats_get_count
         }
         return pairs_to_table(ctx, keys, vals, n, out);
     };
-    MF_TRY(finish(p_chi, chi_out));
+    if (chi_out) MF_TRY(finish(p_chi, chi_out));
     for (int g = 0; g < G; g++) MF_TRY(finish(p_g[g], &grp_out[g]));
     return MF_OK;
 }
@@ -626,7 +711,7 @@ static int check_groups3(int na, int nb, int nc) {
         return mf_set_error("stats-kmers-3: %lld samples, this build supports at most %d (|A| + |B| + |C|)", (long long)na + nb + nc, MF_STATS_MAX_N);
     return MF_OK;
 }
-static int check_p(double pchi2) {
+int mf_stats_check_p(double pchi2) {
     if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) return mf_set_error("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
     return MF_OK;
 }
@@ -640,7 +725,7 @@ extern "C" int mf_stats_kmers_tables(mf_ctx *ctx, mf_table *const *a, int na, mf
     if (!ctx || !chi || !group_a || !group_b || !counters || (na && !a) || (nb && !b)) return mf_set_error("mf_stats_kmers_tables: NULL argument");
     *chi = *group_a = *group_b = nullptr;
     MF_TRY(check_groups(na, nb));
-    MF_TRY(check_p(p_chi2));
+    MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t total = 0;
     std::vector<mf_table *> all(a, a + na);
@@ -666,7 +751,7 @@ extern "C" int mf_stats_kmers(mf_ctx *ctx, const char *const *a_files, int na, c
     mf_range rng_("mf:stats_kmers(files)");
     if (!ctx || !out_dir || (na && !a_files) || (nb && !b_files)) return mf_set_error("mf_stats_kmers: NULL argument");
     MF_TRY(check_groups(na, nb));
-    MF_TRY(check_p(p_chi2));
+    MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t ta = 0, tb = 0;
     MF_TRY(file_records(a_files, na, &ta));
@@ -700,7 +785,7 @@ extern "C" int mf_stats_kmers3_tables(mf_ctx *ctx, mf_table *const *a, int na, m
         return mf_set_error("mf_stats_kmers3_tables: NULL argument");
     *chi = *group_a = *group_b = *group_c = nullptr;
     MF_TRY(check_groups3(na, nb, nc));
-    MF_TRY(check_p(p_chi2));
+    MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t total = 0;
     std::vector<mf_table *> all(a, a + na);
@@ -728,7 +813,7 @@ extern "C" int mf_stats_kmers3(mf_ctx *ctx, const char *const *a_files, int na, 
     mf_range rng_("mf:stats_kmers3(files)");
     if (!ctx || !out_dir || (na && !a_files) || (nb && !b_files) || (nc && !c_files)) return mf_set_error("mf_stats_kmers3: NULL argument");
     MF_TRY(check_groups3(na, nb, nc));
-    MF_TRY(check_p(p_chi2));
+    MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t ta = 0, tb = 0, tc = 0;
     MF_TRY(file_records(a_files, na, &ta));
@@ -749,6 +834,77 @@ extern "C" int mf_stats_kmers3(mf_ctx *ctx, const char *const *a_files, int na, 
     for (int g = 0; g < 3; g++)
         if (rc == MF_OK) rc = mf_table_write_kmers(grp[g], -1, (d + names[g]).c_str(), nullptr, &w);
     mf_table_destroy(chi);
+    for (int g = 0; g < 3; g++) mf_table_destroy(grp[g]);
+    if (rc == MF_OK && counters) memcpy(counters, c, sizeof c);
+    return rc;
+}
+
+// ---- specific-kmers-3: the three-group join in its `specific` mode; every load is at threshold 0, F_j = the sum of the loaded map's values
+// (:103-114: the saturated sums, not the records' sum of loadKmersFreq)
+static int specific3_run(mf_ctx *ctx, const mf_join_get &get, int na, int nb, int nc, uint64_t total, double p_chi2, double p_mw, mf_table **grp,
+                         uint64_t *counters) {
+    const int N = na + nb + nc;
+    std::vector<uint64_t> F((size_t)N, 0);
+    std::vector<bool> have((size_t)N, false);
+    const stats_get_counts get_counts = [&](int j, mf_join_sample &sm, uint64_t *Fj) -> int {
+        MF_TRY(get(j, sm));
+        if (!have[(size_t)j]) { MF_TRY(mf_sum_counts(ctx, sm.t->d_counts, sm.t->n, &F[(size_t)j])); have[(size_t)j] = true; }
+        *Fj = F[(size_t)j];
+        return MF_OK;
+    };
+    const int ng[3] = {na, nb, nc};
+    return stats_join(ctx, get, get_counts, ng, 3, total, 0, p_chi2, p_mw, nullptr, grp, counters, true);
+}
+static int check_specific3(int na, int nb, int nc) {
+    if (na < 1 || nb < 1 || nc < 1)
+        return mf_set_error("specific-kmers-3: every group needs at least one sample (|A| = %d, |B| = %d, |C| = %d)", na, nb, nc);
+    if ((int64_t)na + nb + nc > MF_STATS_MAX_N)
+        return mf_set_error("specific-kmers-3: %lld samples, this build supports at most %d (|A| + |B| + |C|)", (long long)na + nb + nc, MF_STATS_MAX_N);
+    return MF_OK;
+}
+
+extern "C" int mf_specific_kmers3_tables(mf_ctx *ctx, mf_table *const *a, int na, mf_table *const *b, int nb, mf_table *const *c, int nc, double p_chi2,
+                                         double p_mw, mf_table **group_a, mf_table **group_b, mf_table **group_c, uint64_t *counters) {
+    mf_range rng_("mf:specific_kmers3");
+    if (!ctx || !group_a || !group_b || !group_c || !counters || (na && !a) || (nb && !b) || (nc && !c))
+        return mf_set_error("mf_specific_kmers3_tables: NULL argument");
+    *group_a = *group_b = *group_c = nullptr;
+    MF_TRY(check_specific3(na, nb, nc));
+    MF_TRY(mf_stats_check_p(p_chi2));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    std::vector<mf_table *> all(a, a + na);
+    all.insert(all.end(), b, b + nb);
+    all.insert(all.end(), c, c + nc);
+    MF_TRY(tables_total(ctx, all.data(), na + nb + nc, "mf_specific_kmers3_tables", &total));
+    mf_table *grp[3] = {nullptr, nullptr, nullptr};
+    const int rc = specific3_run(ctx, mf_join_tables(all.data()), na, nb, nc, total, p_chi2, p_mw, grp, counters);
+    *group_a = grp[0]; *group_b = grp[1]; *group_c = grp[2];
+    return rc;
+}
+
+extern "C" int mf_specific_kmers3(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, const char *const *c_files, int nc,
+                                  double p_chi2, double p_mw, const char *out_dir, uint64_t *counters) {
+    mf_range rng_("mf:specific_kmers3(files)");
+    if (!ctx || !out_dir || (na && !a_files) || (nb && !b_files) || (nc && !c_files)) return mf_set_error("mf_specific_kmers3: NULL argument");
+    MF_TRY(check_specific3(na, nb, nc));
+    MF_TRY(mf_stats_check_p(p_chi2));
+    MF_HIP(hipSetDevice(ctx->device));
+    uint64_t ta = 0, tb = 0, tc = 0;
+    MF_TRY(file_records(a_files, na, &ta));
+    MF_TRY(file_records(b_files, nb, &tb));
+    MF_TRY(file_records(c_files, nc, &tc));
+    std::vector<const char *> files(a_files, a_files + na);   // (keys and k as in mf_stats_kmers)
+    files.insert(files.end(), b_files, b_files + nb);
+    files.insert(files.end(), c_files, c_files + nc);
+    mf_table *grp[3] = {nullptr, nullptr, nullptr};
+    uint64_t c[MF_SPECIFIC3_COUNTERS] = {0};
+    int rc = specific3_run(ctx, mf_join_files(files.data(), 0, 31), na, nb, nc, ta + tb + tc, p_chi2, p_mw, grp, c);
+    const std::string d(out_dir);
+    uint64_t w = 0;
+    static const char *names[3] = {"/filtered_groupA.kmers.bin", "/filtered_groupB.kmers.bin", "/filtered_groupC.kmers.bin"};
+    for (int g = 0; g < 3; g++)
+        if (rc == MF_OK) rc = mf_table_write_kmers(grp[g], -1, (d + names[g]).c_str(), nullptr, &w);
     for (int g = 0; g < 3; g++) mf_table_destroy(grp[g]);
     if (rc == MF_OK && counters) memcpy(counters, c, sizeof c);
     return rc;

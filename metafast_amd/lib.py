@@ -169,6 +169,12 @@ _SIGS = {
     "mf_kmers_samples_count": (i32, [vp, C.POINTER(cp), i32, i32, i32, cp, cp, pu64]),
     "mf_stats_kmers3_tables": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, C.c_double, C.c_double, pvp, pvp, pvp, pvp, vp]),
     "mf_stats_kmers3": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, C.c_double, C.c_double, cp, vp]),
+    "mf_specific_kmers_tables": (i32, [vp, vp, i32, vp, i32, C.c_double, C.c_double, pvp, pvp, vp]),
+    "mf_specific_kmers": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.c_double, C.c_double, cp, vp]),
+    "mf_specific_kmers3_tables": (i32, [vp, vp, i32, vp, i32, vp, i32, C.c_double, C.c_double, pvp, pvp, pvp, vp]),
+    "mf_specific_kmers3": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, C.c_double, C.c_double, cp, vp]),
+    "mf_unique_kmers_tables": (i32, [vp, vp, i32, vp, i32, i32, pvp, pu64]),
+    "mf_unique_kmers": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, cp, cp, pu64, pu64]),
     "mf_kmers_grouped_count_tables": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, u64, pu64]),
     "mf_kmers_grouped_count": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, cp, pu64]),
     "mf_kmers_per_sample_tables": (i32, [vp, vp, i32, i32, i32, i32, pvp]),
@@ -199,6 +205,7 @@ _SIGS = {
 MAX_PATHS_COUNT = 10 ** 6       # ComponentPathsMain.java:30
 STATS_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "unique_left")
 STATS3_COUNTERS = ("n", "scarce", "in_all", "unique", "chi2_rejected", "mw_rejected", "group_a", "group_b", "group_c", "unique_left")
+SPECIFIC_COUNTERS = ("n", "unique", "scarce", "chi2_rejected", "mw_rejected", "unique_left", "group_a", "group_b")      # MF_SPECIFIC_* of the header
 
 
 class MetafastError(RuntimeError):
@@ -614,6 +621,56 @@ class Context:
         _check(lib().mf_stats_kmers3(self.h, _cfiles(a_files), len(a_files), _cfiles(b_files), len(b_files), _cfiles(c_files), len(c_files),
                                      max_bad, p_chi2, p_mw, os.fsencode(out_dir), ctr.ctypes.data))
         return dict(zip(STATS3_COUNTERS, map(int, ctr)))
+
+    def specific_kmers(self, a_tables, b_tables, p_chi2=0.05, p_mw=0.05):
+        """SpecificKmersFinder (src/tools/SpecificKmersFinder.java:65-245) on resident tables -> (group A, group B, dict of the eight
+        counters)"""
+        ha = (C.c_void_p * max(len(a_tables), 1))(*[t.h for t in a_tables])
+        hb = (C.c_void_p * max(len(b_tables), 1))(*[t.h for t in b_tables])
+        ga, gb = C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(len(SPECIFIC_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_specific_kmers_tables(self.h, ha, len(a_tables), hb, len(b_tables), p_chi2, p_mw, C.byref(ga), C.byref(gb), ctr.ctypes.data))
+        return Table(self, ga), Table(self, gb), dict(zip(SPECIFIC_COUNTERS, map(int, ctr)))
+
+    def specific_kmers_files(self, a_files, b_files, out_dir, p_chi2=0.05, p_mw=0.05):
+        """the same from .kmers.bin files -> out_dir/filtered_{groupA,groupB}.kmers.bin; returns the counters"""
+        ctr = np.zeros(len(SPECIFIC_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_specific_kmers(self.h, _cfiles(a_files), len(a_files), _cfiles(b_files), len(b_files), p_chi2, p_mw, os.fsencode(out_dir),
+                                       ctr.ctypes.data))
+        return dict(zip(SPECIFIC_COUNTERS, map(int, ctr)))
+
+    def specific_kmers3(self, a_tables, b_tables, c_tables, p_chi2=0.05, p_mw=0.05):
+        """SpecificKmers3GroupsFinder (src/tools/SpecificKmers3GroupsFinder.java:70-280) on resident tables -> (group A, group B, group C,
+        dict of the ten counters, named as stats_kmers3's)"""
+        hs = [(C.c_void_p * max(len(g), 1))(*[t.h for t in g]) for g in (a_tables, b_tables, c_tables)]
+        ga, gb, gc = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(len(STATS3_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_specific_kmers3_tables(self.h, hs[0], len(a_tables), hs[1], len(b_tables), hs[2], len(c_tables), p_chi2, p_mw,
+                                               C.byref(ga), C.byref(gb), C.byref(gc), ctr.ctypes.data))
+        return Table(self, ga), Table(self, gb), Table(self, gc), dict(zip(STATS3_COUNTERS, map(int, ctr)))
+
+    def specific_kmers3_files(self, a_files, b_files, c_files, out_dir, p_chi2=0.05, p_mw=0.05):
+        """the same from .kmers.bin files -> out_dir/filtered_{groupA,groupB,groupC}.kmers.bin; returns the counters"""
+        ctr = np.zeros(len(STATS3_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_specific_kmers3(self.h, _cfiles(a_files), len(a_files), _cfiles(b_files), len(b_files), _cfiles(c_files), len(c_files),
+                                        p_chi2, p_mw, os.fsencode(out_dir), ctr.ctypes.data))
+        return dict(zip(STATS3_COUNTERS, map(int, ctr)))
+
+    def unique_kmers(self, inputs, filters, max_bad=1):
+        """UniqueKmersFinder (src/tools/UniqueKmersFinder.java:73-144) on resident tables -> (Table of the pooled k-mers that no filter
+        table holds, size of the pooled map)"""
+        hi = (C.c_void_p * max(len(inputs), 1))(*[t.h for t in inputs])
+        hf = (C.c_void_p * max(len(filters), 1))(*[t.h for t in filters])
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mf_unique_kmers_tables(self.h, hi, len(inputs), hf, len(filters), max_bad, C.byref(out), C.byref(n)))
+        return Table(self, out), n.value
+
+    def unique_kmers_files(self, in_files, filter_files, k, kmers_bin, stat_txt=None, max_bad=1):
+        """the same from .kmers.bin files -> kmers_bin (+ stat_txt); returns (size of the pooled map, records written)"""
+        n, good = C.c_uint64(), C.c_uint64()
+        _check(lib().mf_unique_kmers(self.h, _cfiles(in_files), len(in_files), _cfiles(filter_files), len(filter_files), max_bad, k,
+                                     os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n), C.byref(good)))
+        return n.value, good.value
 
     def kmers_grouped_count(self, kmers, cd, uc, nonibd, max_bad=1):
         """KmersGroupedSamplesCounter (src/tools/KmersGroupedSamplesCounter.java:82-190) on resident tables -> (uint64[n] the k-mers of
