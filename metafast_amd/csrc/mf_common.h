@@ -125,6 +125,7 @@ struct mf_ctx {
     uint64_t n_streamed = 0, n_stream_stepped_back = 0;     // streamed counts that went that way / that started that way and were done again from whole files
     void *up_stream = nullptr;     // hipStream_t of the streamed count's uploads (lazy)
     int64_t dcc_test_calls[3] = {0, 0, 0};   // (option dcc_test_fail: the calls made so far, by which)
+    struct mf_skm_snap *skm_snap = nullptr;  // tests only (mf_debug_skm_records, mf_skm.hip): the counting run hands its records over in front of k_skm_count and ends there; null otherwise
     // workspace arena: a few large hipMalloc'd regions, sub-allocated with first-fit + coalescing free lists.
     // Everything runs on one stream, so a block can be handed out again as soon as it is released.
     struct span { size_t off, sz; };

@@ -1652,7 +1652,17 @@ static int skm_pilot(mf_ctx *ctx, const skm_rec *bufA, const uint64_t *pstart, c
 // input does not suit this path (a partition too rich for the LDS table, too many levels, not enough memory).
 // what the slices of one run add up to: the dense table (grouped by partition, slice after slice = partition order), the
 // partition offsets, the tallies
+// What mf_debug_skm_records (the end of this file) takes out of a run: the state of every slice at the point where count + gather would begin
+struct skm_snap_slice {
+    std::vector<uint64_t> rec;             // the record buffer over [0, cap): x, y of record 0, x, y of record 1, ...
+    std::vector<uint64_t> pstart, l1_pstart; std::vector<uint32_t> plen, pocc, l1_plen;      // the final directory; the slice's level-1 directory
+    std::vector<int> lv;                   // the levels' bits as they were run (after the pilot)
+    uint64_t cap = 0, wpb = 0, n_valid = 0; uint32_t dlo = 0, dhi = 0; int G = 0, one_pass = 0, repeated = 0, fast = 0;
+};
+struct mf_skm_snap { std::vector<skm_snap_slice> slices; };
+#define MF_SKM_SNAPPED 3           /* skm_run: the records went to ctx->skm_snap, nothing was counted */
 struct skm_acc {
+    mf_skm_snap *snap = nullptr;           // (null in production)
     mf_buf<uint64_t> dk; mf_buf<uint16_t> dc; uint64_t dused = 0, dcap = 0;
     mf_buf<uint64_t> doff;                 // [np_total + 1]: the TABLE's partitions (two per counting partition, k_gather_split)
     mf_buf<unsigned long long> dhist, c2p;
@@ -1724,6 +1734,8 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
     // minimizer pass just to count (k_skm_hist over everything costs 17 ms of 300 at 100 M reads).  If a region turns out
     // too small the level is repeated with exact ranges.  skm_dyn: 0 never, 1 auto, 2 always (tests).
     bool dyn = !l1_only && (ctx->opt_skm_dyn == 2 || (ctx->opt_skm_dyn == 1 && n_words >= (1ull << 24)));
+    int snap_one_pass = 0, snap_repeated = 0;             // (what A.snap reports: level 1 in the one-pass form / again with exact ranges after an overflow)
+    if (A.snap && SH && SH->ready && !A.snap->slices.empty()) { snap_one_pass = A.snap->slices.back().one_pass; snap_repeated = A.snap->slices.back().repeated; }   // (the first slice's level 1)
     for (int attempt = dyn ? 0 : 1; attempt < 2 && !(SH && SH->ready); attempt++) {
         const bool D = attempt == 0;
         const int stride = D ? (ctx->opt_skm_dyn == 2 ? 3 : 16) : 1;
@@ -1762,7 +1774,8 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
             unsigned long long ovf = 0;
             MF_HIP(hipMemcpyAsync(&ovf, &scal[5], 8, hipMemcpyDeviceToHost, st));
             MF_HIP(hipStreamSynchronize(st));
-            if (!ovf) break;
+            if (!ovf) { snap_one_pass = 1; break; }
+            snap_repeated = 1;
             if (ctx->opt_verbose) fprintf(stderr, "[mf] skm: a sampled digit region was too small, level 1 again with exact ranges\n");
             bufA.reset();
             continue;
@@ -1860,6 +1873,13 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
         MF_HIP(hipMemcpyAsync(po.p, pocc.p + dlo, (size_t)np * 4, hipMemcpyDeviceToDevice, st));
         pstart.swap(ps); plen.swap(pl); pocc.swap(po);
     }
+    skm_snap_slice snap;
+    if (A.snap) {
+        snap.l1_pstart.resize(np); snap.l1_plen.resize(np);
+        MF_HIP(hipMemcpyAsync(snap.l1_pstart.data(), pstart.p, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(snap.l1_plen.data(), plen.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipStreamSynchronize(st));
+    }
     int used = 0;
     mf_buf<skm_rec> spare;                                // the buffer a level has read from: the next level writes into it
     for (size_t li = 1; li < lv.size(); li++) {
@@ -1929,6 +1949,23 @@ static int skm_slice(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, cons
     }
 
     spare.reset();
+    if (A.snap) {
+        // (pocc of a shared level 1 without a split level does not exist: S > 1 needs two levels)
+        snap.cap = std::min<unsigned long long>(cap, bufA.n); snap.lv = lv; snap.dlo = dlo; snap.dhi = dhi; snap.G = G; snap.wpb = wpb;
+        snap.one_pass = snap_one_pass; snap.repeated = snap_repeated; snap.fast = fast_lds != 0;
+        snap.rec.resize((size_t)snap.cap * 2); snap.pstart.resize(np); snap.plen.resize(np); snap.pocc.resize(np);
+        unsigned long long nv = 0;
+        if (snap.cap) MF_HIP(hipMemcpyAsync(snap.rec.data(), bufA.p, (size_t)snap.cap * sizeof(skm_rec), hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(snap.pstart.data(), pstart.p, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(snap.plen.data(), plen.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(snap.pocc.data(), pocc.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(&nv, &scal[6], 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipStreamSynchronize(st));
+        MF_HIP(hipGetLastError());
+        snap.n_valid = nv;
+        A.snap->slices.push_back(std::move(snap));
+        return MF_OK;
+    }
     // ---- count + gather, a batch of partitions at a time.  A partition's (key,count) slice is sized by its k-mer count
     // (it cannot hold more distinct k-mers than it has k-mers, nor more than the LDS table), i.e. all slices together
     // are as large as the k-mer stream itself: the buffer holds ONE batch of slices and is redused, the dense table grows
@@ -2137,6 +2174,8 @@ static int skm_run(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, const 
         if (pre && !(shared && SH.ready)) return MF_SKM_FALLBACK;
         skm_acc A;                                              // (A.np_total, A.doff: set by the first slice, once the plan stands)
         A.table_bits = table_bits;
+        A.snap = ctx->skm_snap;
+        if (A.snap) A.snap->slices.clear();
         if (kthr >= 0) { MF_TRY(A.dhist.alloc(ctx, (size_t)MF_MAX_COUNT + 1)); MF_HIP(hipMemsetAsync(A.dhist.p, 0, A.dhist.bytes(), st)); }
         MF_TRY(A.c2p.alloc(ctx, 16)); MF_HIP(hipMemsetAsync(A.c2p.p, 0, 128, st));     // [7] counters found non-zero under an empty key (verbose), [8,16) overflow diagnostics
         MF_HIP(hipMemsetAsync(&scal[7], 0, 8, st));
@@ -2144,6 +2183,7 @@ static int skm_run(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, const 
         for (uint32_t sl = 0; sl < S && rc == MF_OK; sl++)
             rc = skm_slice<K>(ctx, d_bases, n_bases, vmask, n_words, n_occ, lv, scal, kthr, own_lo + (uint32_t)((uint64_t)(own_hi - own_lo) * sl / S),
                               own_lo + (uint32_t)((uint64_t)(own_hi - own_lo) * (sl + 1) / S), sl, S, A, shared ? &SH : nullptr, sl + 1 == S, &plan_open);
+        if (rc == MF_OK && A.snap) { SH.clear(); return MF_SKM_SNAPPED; }
         total_bits = 0; for (int b : lv) total_bits += b;
         if (rc == MF_OK && W > 1) {
             // the other ranks' partitions are empty here: offsets 0 before the owner's range, the table's size after it
@@ -2381,4 +2421,62 @@ int mf_count_skm(mf_ctx *ctx, const uint8_t *d_bases, uint64_t n_bases, const ui
         default: return MF_SKM_FALLBACK;
     }
     return skm_cut_above(rc, thr, out);
+}
+
+// =============================================================================================
+// Debugging aid of tests/test_skm_records_gpu.py (not part of the C-ABI): the records of a counting run as they stand in front of k_skm_count.
+// The call is mf_count_device's own (mask, plan, S1, S2, the pilot, every S3 level: mf_count_core with the context's options) with ctx->skm_snap set, which makes
+// skm_slice copy its record buffer and directory to the host where count + gather would start, and end there.  A call that would not take this path
+// (k < MF_SKM_MIN_K, option skm = 0, an input the path hands back) is an error.
+//   mf_debug_skm_records  -> *out: the snapshot (mf_debug_skm_free)
+//   mf_debug_skm_info     slice < 0: info[0] = number of slices; else info[0..10) = cap, partitions, dlo, dhi, G, words per block, one-pass level 1 (0 / 1),
+//                         level 1 repeated with exact ranges after an overflow, the valid-record counter (scal[6]), number of levels; info[10..18) = the
+//                         levels' bits; info[18] = FAST form of the scatter (0 / 1); info[19] = partitions of the slice's level 1
+//   mf_debug_skm_copy     rec[2 cap] (x, y of every record), pstart / plen / pocc [partitions], l1_pstart / l1_plen [level-1 partitions]; null: not wanted
+// =============================================================================================
+int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_len, mf_table **out, int thr,
+                  uint64_t *n_all);
+extern "C" void mf_debug_skm_free(mf_skm_snap *s) { delete s; }
+extern "C" int mf_debug_skm_records(mf_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_len, mf_skm_snap **out) {
+    if (!ctx || !out) return mf_set_error("mf_debug_skm_records: NULL argument");
+    *out = nullptr;
+    if (k < MF_SKM_MIN_K || k > 31 || !ctx->opt_skm)
+        return mf_set_error("mf_debug_skm_records: k = %d, option skm = %d: the call would not take the super-k-mer path", k, (int)ctx->opt_skm);
+    std::unique_ptr<mf_skm_snap> S(new mf_skm_snap());
+    mf_table *t = nullptr;
+    ctx->skm_snap = S.get();
+    const int rc = mf_count_core(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_reads, n_bases, k, min_len, &t, -1, nullptr);
+    ctx->skm_snap = nullptr;
+    if (rc < 0) return rc;
+    if (rc != MF_SKM_SNAPPED) {
+        const bool empty = t && t->n_occ == 0;
+        if (t) mf_table_destroy(t);
+        if (!empty) return mf_set_error("mf_debug_skm_records: the input did not go through the super-k-mer path");
+        S->slices.clear();                                 // (no k-mer occurrence at all: no records)
+    }
+    *out = S.release();
+    return MF_OK;
+}
+extern "C" int mf_debug_skm_info(const mf_skm_snap *s, int slice, uint64_t *info) {
+    if (!s || !info) return mf_set_error("mf_debug_skm_info: NULL argument");
+    if (slice < 0) { info[0] = s->slices.size(); return MF_OK; }
+    if ((size_t)slice >= s->slices.size()) return mf_set_error("mf_debug_skm_info: slice %d of %zu", slice, s->slices.size());
+    const skm_snap_slice &x = s->slices[(size_t)slice];
+    if (x.lv.size() > 8) return mf_set_error("mf_debug_skm_info: %zu levels", x.lv.size());
+    const uint64_t v[10] = {x.cap, x.pstart.size(), x.dlo, x.dhi, (uint64_t)x.G, x.wpb, (uint64_t)x.one_pass, (uint64_t)x.repeated, x.n_valid, x.lv.size()};
+    for (int i = 0; i < 10; i++) info[i] = v[i];
+    for (size_t i = 0; i < 8; i++) info[10 + i] = i < x.lv.size() ? (uint64_t)x.lv[i] : 0;
+    info[18] = (uint64_t)x.fast; info[19] = x.l1_pstart.size();
+    return MF_OK;
+}
+extern "C" int mf_debug_skm_copy(const mf_skm_snap *s, int slice, uint64_t *rec, uint64_t *pstart, uint32_t *plen, uint32_t *pocc, uint64_t *l1_pstart, uint32_t *l1_plen) {
+    if (!s || slice < 0 || (size_t)slice >= s->slices.size()) return mf_set_error("mf_debug_skm_copy: no such slice");
+    const skm_snap_slice &x = s->slices[(size_t)slice];
+    if (rec) std::copy(x.rec.begin(), x.rec.end(), rec);
+    if (pstart) std::copy(x.pstart.begin(), x.pstart.end(), pstart);
+    if (plen) std::copy(x.plen.begin(), x.plen.end(), plen);
+    if (pocc) std::copy(x.pocc.begin(), x.pocc.end(), pocc);
+    if (l1_pstart) std::copy(x.l1_pstart.begin(), x.l1_pstart.end(), l1_pstart);
+    if (l1_plen) std::copy(x.l1_plen.begin(), x.l1_plen.end(), l1_plen);
+    return MF_OK;
 }
