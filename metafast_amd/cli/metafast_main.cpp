@@ -135,6 +135,12 @@ static string timestamp() {                                 // Tool.java:664 "yy
     char b[64]; strftime(b, sizeof b, "%Y.%m.%d_%H.%M.%S", &tmv);
     return b;
 }
+static void mkparent(const string &path) { const size_t s = path.find_last_of('/'); if (s != string::npos) mkdirs(path.substr(0, s)); }
+static string with_dt(string p, const string &ts) { const size_t q = p.find("$DT"); if (q != string::npos) p.replace(q, 3, ts); return p; }
+static string percent_or_nan(uint64_t part, uint64_t whole) {       // Java's "%.1f" of part * 100.0 / whole: 0 / 0 prints NaN
+    char b[64]; if (whole) snprintf(b, sizeof b, "%.1f", part * 100.0 / whole); else snprintf(b, sizeof b, "NaN");
+    return b;
+}
 static void touch(const string &p) { FILE *f = fopen(p.c_str(), "w"); if (f) fclose(f); }
 static string abspath(const string &p) {                    // File.getAbsolutePath: no normalisation
     if (!p.empty() && p[0] == '/') return p;
@@ -162,19 +168,36 @@ struct Args {
         char *e; double v = strtod(it->second[0].c_str(), &e); if (*e || it->second[0].empty()) die("Can't parse double value '%s' of option --%s", it->second[0].c_str(), k.c_str());
         return v;
     }
+    bool flag(const string &k) const { return get(k, "false") == "true"; }
     vector<string> list(const string &k) const { auto it = opt.find(k); return it == opt.end() ? vector<string>() : it->second; }
 };
+// ------------------------------------------------------------------------------------------------ a tool, as the table at the end declares it
+// (the reference's Tool with its Parameter fields, itmo!/utils/tool/Tool.java + Parameter.java): one row of TOOLS and one run function
+enum Kind { VAL, FILE1, FILES, FLAG, LIST, DTFILE };      // plain value, file, list of files, boolean, list of plain values, file with $DT = the run's time stamp
+struct Param { const char *name; Kind kind; const char *dflt; };          // dflt == nullptr: none, the parameter is null unless given; "$WD/x": x in the work directory
+struct Short { const char *sht, *lng; };                                  // what an overloaded short option means for this tool, where OPTS' first match is not it
+struct Need { const char *name, *sht; };                                  // a mandatory argument; sht == nullptr: the message names no short option
+struct PV;
+struct Run;
+struct Tool {
+    const char *name, *desc;
+    vector<PV> (*run)(Run &);                                             // does the work, returns the entries of out.properties
+    Short shorts[4]; Need needs[6]; Param params[18];                     // each ends at its first empty entry; params in the reference's declaration order
+    const Param *param(const string &n) const { for (auto &p : params) if (p.name && n == p.name) return &p; return nullptr; }
+};
+static const Tool *find_tool(const string &name);
 struct OptDef { const char *lng; const char *sht; bool multi; bool flag; };
 // every option of the tools on the path (short names as in the reference; note --maximal-bad-frequence in the counters,
-// KmersCounterMain.java:40, vs --maximal-bad-frequency elsewhere)
+// KmersCounterMain.java:40, vs --maximal-bad-frequency elsewhere).  A short name that several options share means the FIRST of them
+// unless the tool's row says otherwise.
 static const OptDef OPTS[] = {
     {"tool", "t", false, false}, {"tools", "ts", false, true}, {"version", "", false, true}, {"work-dir", "w", false, false},
     {"available-processors", "p", false, false}, {"continue", "c", false, true}, {"force", "", false, true},
     {"start", "s", false, false}, {"finish", "f", false, false}, {"verbose", "v", false, true}, {"help", "h", false, true},
     {"help-all", "ha", false, true}, {"memory", "m", false, false},
     {"k", "k", false, false}, {"reads", "i", true, false}, {"k-mers", "i", true, false}, {"sequences", "i", true, false},
-    {"maximal-bad-frequence", "b", false, false}, {"maximal-bad-frequency", "b", false, false},
-    {"bottom-cut-percent", "bp", false, false}, {"sequence-len", "l", false, false}, {"min-seq-len", "l", false, false},
+    {"maximal-bad-frequency", "b", false, false}, {"maximal-bad-frequence", "b", false, false},
+    {"bottom-cut-percent", "bp", false, false}, {"min-seq-len", "l", false, false}, {"sequence-len", "l", false, false},
     {"output-dir", "o", false, false}, {"stats-dir", "", false, false},
     {"min-component-size", "b1", false, false}, {"max-component-size", "b2", false, false}, {"components-file", "cm", false, false},
     {"kmers", "ka", true, false}, {"selected", "", true, false}, {"threshold", "", false, false},
@@ -189,42 +212,19 @@ static const OptDef OPTS[] = {
     {"nonibd-filter-kmers", "nonibd", true, false}, {"c-kmers", "C", true, false},
     {"cd-kmers", "cd", true, false}, {"uc-kmers", "uc", true, false}, {"nonibd-kmers", "nonibd", true, false},
     {"class", "", false, false}, {"val", "val", false, true}, {"n_groups", "group", false, false}, {"separate", "", false, true},
-    {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false}, {"percent-present", "perc", false, false},
+    {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false}, {"percent-present", "", false, false},
     {"coverage", "cov", false, true}, {"graph-file", "", false, false},
     {"seq", "", true, false}, {"components", "", true, false}, {"all-components", "a", false, true}, {"min-length", "", false, false},
 };
-// `ctx_i` says what -i means for the selected tool
 static Args parse_args(int argc, char **argv, string *tool_out) {
     // first pass: find the tool (needed to resolve the overloaded short options)
     string tool = "matrix-builder";                                         // src/Runner.java:29
     for (int i = 1; i + 1 < argc; i++) if (!strcmp(argv[i], "-t") || !strcmp(argv[i], "--tool")) tool = argv[i + 1];
     *tool_out = tool;
+    const Tool *row = find_tool(tool);
     auto long_of_short = [&](const string &s) -> string {
-        if (s == "i") {
-            if (tool == "heatmap-maker") return "matrix-file";                 // HeatMapMakerMain.java:34-36
-            if (tool == "seq-builder" || tool == "seq-builder-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "component-colored" || tool == "kmers-per-sample" || tool == "comp2graph" ||
-                tool == "unique-kmers") return "k-mers";
-            if (tool == "component-cutter" || tool == "seq2comp") return "sequences";
-            return "reads";
-        }
-        if (s == "b") return (tool == "kmer-counter" || tool == "kmer-counter-many" || tool == "kmers-filter" || tool == "kmers-samples-counter" || tool == "stats-kmers" ||
-                              tool == "unique-kmers-multi" || tool == "kmers-multiple-filters" || tool == "stats-kmers-3" || tool == "kmers-grouped-counter" || tool == "unique-kmers")
-                                 ? "maximal-bad-frequence" : "maximal-bad-frequency";
-        if (tool == "component-paths") {                                   // ComponentPathsMain.java:52-71 (features-calculator: -cm is the components' file)
-            if (s == "cm") return "components";
-            if (s == "l") return "min-length";
-        }
-        if (s == "l") return (tool == "seq-builder" || tool == "seq-builder-many") ? "sequence-len" : "min-seq-len";
-        if (s == "o") return (tool == "view" || tool == "bin2fasta") ? "output-file" : "output-dir";
-        if (s == "kf" && tool == "kmers-color") return "k-mers";            // ColorKmersMain.java:39-43 (view, bin2fasta: kmers-file)
-        if (tool == "kmers-grouped-counter") {                             // KmersGroupedSamplesCounter.java:44-60 (kmers-multiple-filters: *-filter-kmers)
-            if (s == "cd") return "cd-kmers";
-            if (s == "uc") return "uc-kmers";
-            if (s == "nonibd") return "nonibd-kmers";
-        }
+        if (row) for (auto &o : row->shorts) if (o.sht && s == o.sht) return o.lng;
         if (s == "cf") return "components-file";                           // ViewMain.java:45, BinaryToFasta.java:47
-        if (s == "perc") return tool == "kmers-per-sample" ? "percent-present" : "";   // KmersPerSampleCounter.java:43-48 (component-colored: --perc only)
         for (auto &o : OPTS) if (o.sht[0] && s == o.sht) return o.lng;
         return "";
     };
@@ -248,8 +248,9 @@ static Args parse_args(int argc, char **argv, string *tool_out) {
             continue;
         }
         if (i >= argc) die("Missing argument for option: %s", tok.c_str());
-        // (--kmers-file is a list in kmers-grouped-counter, KmersGroupedSamplesCounter.java:38-42, one file in view and bin2fasta)
-        if (def->multi || (tool == "kmers-grouped-counter" && name == "kmers-file")) { while (i < argc && !(argv[i][0] == '-' && strlen(argv[i]) > 1 && !isdigit((unsigned char)argv[i][1]))) vals.push_back(argv[i++]); }
+        // (a list where the tool declares one: --kmers-file in kmers-grouped-counter, KmersGroupedSamplesCounter.java:38-42, one file in view and bin2fasta)
+        const Param *decl = row ? row->param(name) : nullptr;
+        if (def->multi || (decl && (decl->kind == FILES || decl->kind == LIST))) { while (i < argc && !(argv[i][0] == '-' && strlen(argv[i]) > 1 && !isdigit((unsigned char)argv[i][1]))) vals.push_back(argv[i++]); }
         else vals.push_back(argv[i++]);
     }
     return a;
@@ -391,10 +392,9 @@ static string run_kmer_counter(Env &e, const Args &a, const vector<string> &file
     return out;
 }
 // kmer-counter-many (src/tools/KmersCounterForManyFilesMain.java:66-108): sort, pair _r1/_r2, one counter per sample
-static vector<string> run_kmer_counter_many(Env &e, const Args &a, vector<string> files, int k, int b, const string &wd) {
+static vector<string> run_kmer_counter_many(Env &e, const Args &a, vector<string> files, int k, int b, const string &wd, const string &out_dir, const string &stats_dir) {
     if (files.empty()) die("Mandatory option --reads is not set");
     std::sort(files.begin(), files.end());
-    string out_dir = a.get("output-dir", wd + "/kmers"), stats_dir = a.get("stats-dir", wd + "/stats");
     mkdirs(wd + "/sub-counter");
     auto ends = [](const string &s, const char *x) { return s.size() >= 3 && s.compare(s.size() - 3, 3, x) == 0; };
     vector<vector<string>> libs;                                             // :80-108, one entry per library
@@ -607,7 +607,7 @@ static string format_cell(const string &fmt, double v) {
 }
 // DistanceMatrixCalculatorMain.printMatrix (:91-123): perm == nullptr prints the original order
 static void print_matrix(const vector<double> &m, int n, const string &path, const vector<string> *names, const int *perm, const string &fmt) {
-    size_t slash = path.find_last_of('/'); if (slash != string::npos) mkdirs(path.substr(0, slash));
+    mkparent(path);
     FILE *out = fopen(path.c_str(), "w");
     if (!out) die("Failed to print matrix to %s", path.c_str());
     if (names) { fprintf(out, "#"); for (int i = 0; i < n; i++) fprintf(out, "\t%s", (*names)[perm ? perm[i] : i].c_str()); fprintf(out, "\n"); }
@@ -663,7 +663,7 @@ static vector<int> heatmap_order(const vector<double> &m, int n) {
     hm_group(t, root, perm);
     return perm;
 }
-static string run_heatmap_maker(Env &e, const Args &a, const string &matrix_path, const string &new_matrix_tpl) {
+static string run_heatmap_maker(Env &e, const string &matrix_path, const string &new_matrix_tpl, bool without_renumbering, const string &fmt) {
     FILE *fp = fopen(matrix_path.c_str(), "r");
     if (!fp) die("Can't read matrix file %s", matrix_path.c_str());
     vector<vector<string>> rows; char *line = nullptr; size_t cap = 0;
@@ -694,11 +694,10 @@ static string run_heatmap_maker(Env &e, const Args &a, const string &matrix_path
             if (*end) die("Can't parse matrix, '%s' is not a number", cell.c_str());
         }
     }
-    if (a.get("without-renumbering", "false") == "true") return matrix_path;
+    if (without_renumbering) return matrix_path;
     vector<int> perm = heatmap_order(m, n);
-    string path = new_matrix_tpl.empty() ? remove_ext(matrix_path, {".txt"}) + "_renumbered.txt" : new_matrix_tpl;
-    size_t p = path.find("$DT"); if (p != string::npos) path.replace(p, 3, e.start_ts);
-    print_matrix(m, n, path, with_names ? &names : nullptr, perm.data(), a.get("output-format", "%.4f"));
+    const string path = with_dt(new_matrix_tpl.empty() ? remove_ext(matrix_path, {".txt"}) + "_renumbered.txt" : new_matrix_tpl, e.start_ts);
+    print_matrix(m, n, path, with_names ? &names : nullptr, perm.data(), fmt);
     logmsg("INFO", "Renumbered matrix saved to %s", path.c_str());
     return path;
 }
@@ -744,7 +743,7 @@ static void run_view(const Args &a, int k) {
     if (kf.empty() && cf.empty()) { logmsg("WARN", "No input file is selected  --->  no data to display!"); return; }
     FILE *out = open_out(a.get("output-file"));
     if (!kf.empty()) {
-        const int rec = a.get("long", "false") == "true" ? 16 : 10;          // IOUtils.loadLongKmers / loadKmers
+        const int rec = a.flag("long") ? 16 : 10;          // IOUtils.loadLongKmers / loadKmers
         vector<unsigned char> b = slurp(kf);
         fprintf(out, "Kmer\tCount\n");
         for (size_t p = 0; p + rec <= b.size(); p += rec)
@@ -765,7 +764,7 @@ static void run_view(const Args &a, int k) {
 static void run_bin2fasta(const Args &a, int k) {
     const string kf = a.get("kmers-file"), cf = a.get("components-file"), prefix = a.get("output-file");
     if (kf.empty() && cf.empty()) { logmsg("WARN", "No input file is selected  --->  no data to display!"); return; }
-    if (!prefix.empty()) { size_t s = prefix.find_last_of('/'); if (s != string::npos) mkdirs(prefix.substr(0, s)); }
+    if (!prefix.empty()) mkparent(prefix);
     if (!kf.empty()) {
         FILE *out = open_out(prefix.empty() ? "" : prefix + ".fasta");
         vector<unsigned char> b = slurp(kf);
@@ -776,7 +775,7 @@ static void run_bin2fasta(const Args &a, int k) {
     if (!cf.empty()) {
         vector<HostComp> cs = read_components(cf);
         logmsg("INFO", "%zu components loaded from %s", cs.size(), cf.c_str());
-        if (a.get("split", "false") == "true") {
+        if (a.flag("split")) {
             for (size_t i = 0; i < cs.size(); i++) {
                 FILE *out = open_out(prefix.empty() ? "" : prefix + "_" + std::to_string(i + 1) + ".fasta");
                 size_t j = 1;
@@ -792,7 +791,7 @@ static void run_bin2fasta(const Args &a, int k) {
 }
 
 // dist-matrix-calculator (src/tools/DistanceMatrixCalculatorMain.java:51-123)
-static string run_dist_matrix(Env &e, const Args &a, const vector<string> &features, const string &matrix_path_tpl) {
+static string run_dist_matrix(Env &e, const vector<string> &features, const string &matrix_path_tpl, bool without_names, const string &fmt) {
     if (features.empty()) die("Mandatory option --features is not set");
     vector<vector<int64_t>> vs;
     for (auto &f : features) {
@@ -809,11 +808,10 @@ static string run_dist_matrix(Env &e, const Args &a, const vector<string> &featu
     int ns = (int)vs.size();
     vector<double> m((size_t)ns * ns, 0.0);
     check(mf_bray_curtis(flat.data(), ns, (int)nc, m.data()));
-    string path = matrix_path_tpl;
-    size_t p = path.find("$DT"); if (p != string::npos) path.replace(p, 3, e.start_ts);
+    const string path = with_dt(matrix_path_tpl, e.start_ts);
     vector<string> names;
     for (auto &f : features) names.push_back(remove_ext(basename_of(f), {"vec"}));
-    print_matrix(m, ns, path, a.get("without-names", "false") != "true" ? &names : nullptr, nullptr, a.get("output-format", "%.4f"));
+    print_matrix(m, ns, path, without_names ? nullptr : &names, nullptr, fmt);
     logmsg("INFO", "Distance matrix printed to %s", path.c_str());
     return path;
 }
@@ -901,141 +899,772 @@ static vector<string> g_desc_files;
 static void describe(const string &path, const char *msg) {
     for (auto &d : g_desc_files) { FILE *f = fopen(d.c_str(), "a"); if (!f) continue; fprintf(f, "\n%s\n   %s\n", path.c_str(), msg); fclose(f); }
 }
-static const char *TOOLS_TEXT =
-    "kmer-counter\t\tCount k-mers in given reads\n"
-    "kmer-counter-many\tCount k-mers in many files (one library = one output)\n"
-    "seq-builder\t\tMetagenome De Bruijn graph analysis and sequences building\n"
-    "seq-builder-many\tseq-builder for many k-mers files\n"
-    "component-cutter\tBuild graph components from sequences\n"
-    "features-calculator\tCalculate features values for input reads/k-mers files\n"
-    "dist-matrix-calculator\tCalculate the distance matrix using features values\n"
-    "heatmap-maker\t\tCluster the samples of a distance matrix and renumber it (no image)\n"
-    "kmer-counter-posneg\tCount k-mers for files from two groups independently\n"
-    "kmers-filter\t\tFilter k-mers from test set according to known samples\n"
-    "kmers-samples-counter\tCount number of samples containing k-mers from multiple samples\n"
-    "stats-kmers\t\tFind k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)\n"
-    "stats-kmers-3\t\tFind k-mers that differ significantly between three groups of samples (chi-squared + Mann-Whitney)\n"
-    "specific-kmers\t\tOutput k-mers specific to groups of samples based on chi-squared & Mann-Whitney tests\n"
-    "specific-kmers-3\tOutput k-mers specific to each of three groups of samples based on chi-squared & Mann-Whitney tests\n"
-    "kmers-grouped-counter\tCount number of samples from 3 groups containing specified k-mers\n"
-    "kmers-per-sample\tCounts the abundance of frequent k-mers from dataset in each sample\n"
-    "unique-kmers\t\tOutput k-mers present in one dataset and missing in other\n"
-    "unique-kmers-multi\tOutput k-mers present in one dataset in fixed number of samples and missing in other\n"
-    "kmers-multiple-filters\tFilter k-mers from test set according to three specified sets\n"
-    "kmers-color\t\tColor k-mers based on their occurrences in three groups of samples\n"
-    "component-colored\tExtract graph components from tangled graph based on k-mers coloring\n"
-    "comp2seq\t\tTransforms components in binary format to FASTA sequences (contigs)\n"
-    "comp2graph\t\tTransforms components in binary format to de Bruijn graph in GFA format\n"
-    "seq2comp\t\tTransforms sequences to components\n"
-    "component-paths\t\tExtracts paths in the components\n"
-    "view\t\t\tView different binary objects (k-mers files, components)\n"
-    "bin2fasta\t\tConverts different binary objects to FASTA format\n"
-    "matrix-builder\t\tBuild the distance matrix for input sequences (default tool)\n";
-
-// input parameters of a tool as in.properties lists them: declaration order of the reference's Parameter fields, values
-// = what the run will use (defaults filled in).  matrix-builder: its own, then the sub-tools' parameters it does not fix
-// (Tool.addSubTool :168-207).
-static vector<PV> tool_inputs(const string &tool, const Args &a, const string &wd, const string &ts) {
-    auto dt = [&](string p) { size_t q = p.find("$DT"); if (q != string::npos) p.replace(q, 3, ts); return p; };
-    auto opt_i = [&](const char *n) { return a.has(n) ? PV(n, a.get(n)) : PV::null(n); };
-    auto opt_f = [&](const char *n) { return a.has(n) ? PV::file(n, a.get(n)) : PV::null(n); };
-    auto flag = [&](const char *n) { return PV::flag(n, a.get(n, "false") == "true"); };
+// input parameters of a tool as in.properties lists them: the row's declaration, values = what the run will use (defaults filled in)
+static string param_default(const Param &p, const string &wd) { string d = p.dflt ? p.dflt : ""; if (d.rfind("$WD", 0) == 0) d.replace(0, 3, wd); return d; }
+static vector<PV> tool_inputs(const Tool &t, const Args &a, const string &wd, const string &ts) {
     vector<PV> v;
-    if (tool == "kmer-counter" || tool == "kmer-counter-many") {
-        v = {opt_i("k"), PV::files("reads", a.list("reads")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "seq-builder" || tool == "seq-builder-many") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")),
-             tool == "seq-builder" ? PV("maximal-bad-frequency", a.get("maximal-bad-frequency", "1")) : opt_i("maximal-bad-frequency"),
-             opt_i("bottom-cut-percent"), opt_i("sequence-len"), PV::file("output-dir", a.get("output-dir", wd + "/sequences"))};
-    } else if (tool == "component-cutter") {
-        v = {opt_i("k"), PV("min-seq-len", a.get("min-seq-len", "100")), PV("min-component-size", a.get("min-component-size", "1000")),
-             PV("max-component-size", a.get("max-component-size", "10000")), PV::files("sequences", a.list("sequences")),
-             PV::file("components-file", a.get("components-file", wd + "/components.bin"))};
-    } else if (tool == "features-calculator") {
-        v = {opt_i("k"), opt_f("components-file"), PV::files("reads", a.list("reads")), PV::files("kmers", a.list("kmers")),
-             a.has("selected") ? PV::files("selected", a.list("selected")) : PV::null("selected"), PV("threshold", a.get("threshold", "0"))};
-    } else if (tool == "dist-matrix-calculator") {
-        v = {PV::files("features", a.list("features")), flag("without-names"),
-             PV::file("matrix-file", dt(a.get("matrix-file", wd + "/dist_matrix_$DT_original_order.txt"))), PV("output-format", a.get("output-format", "%.4f"))};
-    } else if (tool == "heatmap-maker") {
-        v = {opt_f("matrix-file"), opt_f("colors-file"), flag("without-renumbering"), opt_f("newMatrix-file"), opt_f("heatmap-file"),
-             flag("invert-colors"), PV("output-format", a.get("output-format", "%.4f"))};
-    } else if (tool == "matrix-builder") {
-        v = {PV("k", a.get("k", "31")), PV::files("reads", a.list("reads")), PV("maximal-bad-frequency", a.get("maximal-bad-frequency", "1")),
-             PV("min-seq-len", a.get("min-seq-len", "100")), flag("use-reads-for-calculating-features"),
-             PV::file("matrix-file", dt(a.get("matrix-file", wd + "/matrices/dist_matrix_$DT.txt"))),
-             PV::file("heatmap-file", dt(a.get("heatmap-file", wd + "/matrices/dist_matrix_$DT_heatmap.png"))),
-             PV::file("stats-dir", a.get("stats-dir", wd + "/kmer-counter-many/stats")), opt_i("bottom-cut-percent"),
-             PV("min-component-size", a.get("min-component-size", "1000")), PV("max-component-size", a.get("max-component-size", "10000")),
-             a.has("selected") ? PV::files("selected", a.list("selected")) : PV::null("selected"), flag("without-names"),
-             PV("output-format", a.get("output-format", "%.4f")), opt_f("colors-file"), flag("without-renumbering"), flag("invert-colors")};
-    } else if (tool == "kmer-counter-posneg") {
-        v = {opt_i("k"), PV::files("positiveReads", a.list("positiveReads")), PV::files("negativeReads", a.list("negativeReads")),
-             PV("maximal-bad-frequency", a.get("maximal-bad-frequency", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers_posneg"))};
-    } else if (tool == "kmers-filter") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
-             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV("max-thresh", a.get("max-thresh", "0")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "kmers-samples-counter") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "stats-kmers") {
-        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV("p-value-chi2", a.get("p-value-chi2", "0.05")),
-             PV("p-value-mw", a.get("p-value-mw", "0.05")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
-    } else if (tool == "stats-kmers-3") {
-        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV::files("c-kmers", a.list("c-kmers")),
-             PV("p-value-chi2", a.get("p-value-chi2", "0.05")), PV("p-value-mw", a.get("p-value-mw", "0.05")),
-             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "0")), PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
-    } else if (tool == "specific-kmers") {                                 // (SpecificKmersFinder.java:30-57: no maximal-bad-frequence)
-        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV("p-value-chi2", a.get("p-value-chi2", "0.05")),
-             PV("p-value-mw", a.get("p-value-mw", "0.05")), PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
-    } else if (tool == "specific-kmers-3") {
-        v = {PV::files("a-kmers", a.list("a-kmers")), PV::files("b-kmers", a.list("b-kmers")), PV::files("c-kmers", a.list("c-kmers")),
-             PV("p-value-chi2", a.get("p-value-chi2", "0.05")), PV("p-value-mw", a.get("p-value-mw", "0.05")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers"))};
-    } else if (tool == "unique-kmers") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
-             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
-             PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "kmers-grouped-counter") {
-        v = {opt_i("k"), PV::files("kmers-file", a.list("kmers-file")), PV::files("cd-kmers", a.list("cd-kmers")), PV::files("uc-kmers", a.list("uc-kmers")),
-             PV::files("nonibd-kmers", a.list("nonibd-kmers")), PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers")), PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "kmers-per-sample") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("percent-present", a.get("percent-present", "20")),
-             PV::file("output-dir", a.get("output-dir", wd + "/kmers_per_samples"))};
-    } else if (tool == "unique-kmers-multi") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("filter-kmers", a.list("filter-kmers")),
-             PV("min-samples", a.get("min-samples", "1")), PV("max-samples", a.get("max-samples", "1")),
-             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
-             PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "kmers-multiple-filters") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV::files("cd-filter-kmers", a.list("cd-filter-kmers")),
-             PV::files("uc-filter-kmers", a.list("uc-filter-kmers")), PV::files("nonibd-filter-kmers", a.list("nonibd-filter-kmers")),
-             PV("maximal-bad-frequence", a.get("maximal-bad-frequence", "1")), PV::file("output-dir", a.get("output-dir", wd + "/kmers")),
-             PV::file("stats-dir", a.get("stats-dir", wd + "/stats"))};
-    } else if (tool == "kmers-color") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), opt_f("class"), PV("maximal-bad-frequency", a.get("maximal-bad-frequency", "1")), flag("val"),
-             PV::file("output-dir", a.get("output-dir", wd + "/colored-kmers"))};
-    } else if (tool == "component-colored") {
-        v = {opt_i("k"), PV::files("k-mers", a.list("k-mers")), PV("n_groups", a.get("n_groups", "3")), flag("separate"), flag("linear"),
-             PV("n_comps", a.get("n_comps", "-1")), PV("perc", a.get("perc", "0.9")), PV::file("output-dir", a.get("output-dir", wd + "/colored-components"))};
-    } else if (tool == "comp2seq") {
-        v = {PV("k", a.get("k", "31")), opt_f("components-file"), flag("split")};
-    } else if (tool == "comp2graph") {
-        v = {opt_i("k"), opt_f("components-file"), a.has("k-mers") ? PV::files("k-mers", a.list("k-mers")) : PV::null("k-mers"), flag("coverage"),
-             PV::file("graph-file", a.get("graph-file", wd + "/components-graph.gfa"))};
-    } else if (tool == "seq2comp") {
-        v = {opt_i("k"), PV::files("sequences", a.list("sequences")), PV::file("components-file", a.get("components-file", wd + "/components.bin"))};
-    } else if (tool == "component-paths") {
-        v = {opt_i("k"), opt_f("components-file"), PV::files("seq", a.list("seq")), PV("components", a.list("components")), flag("all-components"),
-             PV("min-length", a.get("min-length", "50")), PV::file("output-dir", a.get("output-dir", wd + "/paths"))};
-    } else if (tool == "view" || tool == "bin2fasta") {
-        v = {opt_i("k"), opt_f("kmers-file"), opt_f("components-file"), opt_f("output-file")};
+    for (auto &p : t.params) {
+        if (!p.name) break;
+        const string n = p.name, d = param_default(p, wd);
+        switch (p.kind) {
+            case VAL: v.push_back(a.has(n) || p.dflt ? PV(n, a.get(n, d)) : PV::null(n)); break;
+            case FILE1: v.push_back(PV::file(n, a.get(n, d))); break;
+            case DTFILE: v.push_back(PV::file(n, with_dt(a.get(n, d), ts))); break;
+            case FILES: v.push_back(PV::files(n, a.list(n))); break;
+            case LIST: v.push_back(PV(n, a.list(n))); break;
+            case FLAG: v.push_back(PV::flag(n, a.flag(n))); break;
+        }
     }
     return v;
+}
+// what a run function sees: the launch, and the tool's parameters -- given on the command line, else taken from last run's in.properties
+// under --continue (main), else the default its row declares
+struct Run {
+    Env &e; const Args &a; const Tool &t; const string wd, start, finish; bool force; int k;
+    string dflt(const char *n, const Tool *of = nullptr, const string *dir = nullptr) const { const Param *p = (of ? of : &t)->param(n); return p ? param_default(*p, dir ? *dir : wd) : string(); }
+    string str(const char *n) const { return a.get(n, dflt(n)); }
+    int num(const char *n) const { const string d = dflt(n); return a.geti(n, d.empty() ? -1 : atoi(d.c_str())); }      // (-1: not given and no default)
+    double real(const char *n) const { return a.getd(n, atof(dflt(n).c_str())); }
+    mf_ctx *ctx() { return ctx_of(e, a); }
+    void entry(bool present, const char *fn) const { if (!present) die("%s: this build of the library has no %s", t.name, fn); }
+};
+// the default that another tool's row declares, in that tool's work directory `dir`: what a sub-step runs with
+static string sub_default(const Run &r, const char *tool, const char *n, const string &dir) { return r.dflt(n, find_tool(tool), &dir); }
+static string cutter_stat(const string &wd, int b1, int b2) { return wd + "/components-stat-" + std::to_string(b1) + "-" + std::to_string(b2) + ".txt"; }
+
+// ------------------------------------------------------------------------------------------------ the tools' run functions
+static vector<PV> tool_kmer_counter(Run &r) {
+    return {PV::file("resulting-kmers-file", run_kmer_counter(r.e, r.a, r.a.list("reads"), r.k, r.num("maximal-bad-frequence"), r.str("output-dir"), r.str("stats-dir")))};
+}
+static vector<PV> tool_kmer_counter_many(Run &r) {
+    check_k(r.k);
+    return {PV::files("resulting-kmers-files", run_kmer_counter_many(r.e, r.a, r.a.list("reads"), r.k, r.num("maximal-bad-frequence"), r.wd, r.str("output-dir"), r.str("stats-dir")))};
+}
+// seq-builder-many declares no default for -b (it may not be given next to -bp) and hands a null on: seq-builder's own default applies
+static vector<PV> tool_seq_builder(Run &r) {
+    const bool many = !strcmp(r.t.name, "seq-builder-many");
+    if (many && r.a.has("maximal-bad-frequency") && r.a.has("bottom-cut-percent")) die("-b and -bp can not be set both");
+    const int b = r.a.geti("maximal-bad-frequency", atoi(r.dflt("maximal-bad-frequency", find_tool("seq-builder")).c_str()));
+    const int bp = r.num("bottom-cut-percent"), l = r.num("sequence-len");
+    if (!many) return {PV::file("output-file", run_seq_builder(r.e, r.a, r.a.list("k-mers"), r.k, b, bp, l, r.wd, r.str("output-dir")))};
+    return {PV::files("output-files", run_seq_builder_many(r.e, r.a, r.a.list("k-mers"), r.k, b, bp, l, r.wd, r.str("output-dir")))};
+}
+static vector<PV> tool_component_cutter(Run &r) {
+    const int b1 = r.num("min-component-size"), b2 = r.num("max-component-size");
+    const string cf = run_component_cutter(r.e, r.a, r.a.list("sequences"), r.k, r.num("min-seq-len"), b1, b2, r.wd, r.str("components-file"));
+    return {PV::file("components-file", cf), PV::file("components-stat", cutter_stat(r.wd, b1, b2))};
+}
+static vector<PV> tool_features(Run &r) {
+    return {PV::files("features-files", run_features(r.e, r.a, r.str("components-file"), r.a.list("reads"), r.a.list("kmers"), r.k, r.num("threshold"), r.wd)),
+            PV::file("features-dir", r.wd + "/vectors")};
+}
+static vector<PV> tool_dist_matrix(Run &r) {
+    run_dist_matrix(r.e, r.a.list("features"), r.str("matrix-file"), r.a.flag("without-names"), r.str("output-format"));
+    return {};
+}
+static vector<PV> tool_posneg(Run &r) {
+    // KmersCounterPositiveNegative.java:66-108: two kmer-counter-many steps with the work directories <workDir>/pos and /neg
+    const int k = r.k;
+    vector<string> pos = r.a.list("positiveReads"), neg = r.a.list("negativeReads");
+    logmsg("INFO", "Found %zu samples in positive class and %zu samples in negative class to process", pos.size(), neg.size());
+    if (pos.empty() || neg.empty()) die("No libraries to process!!! Can't continue the calculations.");
+    check_k(k);
+    const int b = r.num("maximal-bad-frequency");
+    vector<string> kp, kn;
+    for (int side = 0; side < 2; side++) {                                 // (each step with the counter's own defaults in ITS work directory)
+        const string d = r.wd + (side ? "/neg" : "/pos"), od = sub_default(r, "kmer-counter-many", "output-dir", d), sd = sub_default(r, "kmer-counter-many", "stats-dir", d);
+        const vector<string> &files = side ? neg : pos;
+        vector<string> &res = side ? kn : kp;
+        run_as_step("kmer-counter-many", d, {PV("k", k), PV::files("reads", files), PV("maximal-bad-frequence", b), PV::file("output-dir", od), PV::file("stats-dir", sd)},
+                    r.start, r.force,
+                    [&]() { res = run_kmer_counter_many(r.e, r.a, files, k, b, d, od, sd); return vector<PV>{PV::files("resulting-kmers-files", res)}; },
+                    [&](const Props &o) { res = props_list(o, "resulting-kmers-files"); });
+    }
+    return {PV::files("resulting-pos-kmers-files", kp), PV::files("resulting-neg-kmers-files", kn)};
+}
+static vector<PV> tool_kmers_filter(Run &r) {
+    // KmersFilter.java:80-121: every input k-mers file is written again with the records whose k-mer is frequent enough
+    // in the filter files (IOUtils.filterAndPrintKmers, src/io/IOUtils.java:101-123)
+    const int k = r.k;
+    check_k(k);
+    const int b = r.num("maximal-bad-frequence"), mt = r.num("max-thresh");
+    const string out_dir = r.str("output-dir");
+    mkdirs(out_dir);
+    mf_ctx *ctx = r.ctx();
+    const vector<string> ff = r.a.list("filter-kmers");
+    auto fp = cptrs(ff);
+    mf_table *filter = nullptr;
+    check(mf_table_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &filter));
+    vector<string> written;
+    for (auto &f : r.a.list("k-mers")) {
+        mf_table *t = nullptr;
+        const char *one[1] = {f.c_str()};
+        check(mf_table_load_kmers(ctx, one, 1, b, k, &t));
+        string name = basename_of(f);
+        for (size_t q; (q = name.find(".kmers.bin")) != string::npos;) name.erase(q, 10);        // replaceAll(".kmers.bin", "")
+        const string out = out_dir + "/" + name + ".kmers.bin";
+        uint64_t c = 0, size = 0;
+        check(mf_table_write_kmers_filtered(t, b, filter, mt * (int)ff.size(), out.c_str(), &c));
+        check(mf_table_stats(t, &size, nullptr));
+        logmsg("INFO", "%s k-mers found, %s (%.1f%%) of them survived after filtering", group_digits(size).c_str(), group_digits(c).c_str(),
+               size ? c * 100.0 / size : 0.0);
+        logmsg("INFO", "Filtered k-mers printed to %s", out.c_str());
+        mf_table_destroy(t);
+        written.push_back(out);
+    }
+    mf_table_destroy(filter);
+    return {written.empty() ? PV::null("resulting-kmers-file") : PV::file("resulting-kmers-file", written.back())};
+}
+static vector<PV> tool_kmers_samples_counter(Run &r) {
+    // KmersSamplesCounter.java:69-140: the number of input files that hold each k-mer with a count > b
+    const int k = r.k;
+    check_k(k);
+    const int b = r.num("maximal-bad-frequence");
+    const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
+    const vector<string> files = r.a.list("k-mers");
+    mkdirs(out_dir); mkdirs(st_dir);
+    r.entry(mf_kmers_samples_count != nullptr, "mf_kmers_samples_count");
+    mf_ctx *ctx = r.ctx();
+    auto fp = cptrs(files);
+    const string out = out_dir + "/n_samples.kmers.bin", st = st_dir + "/n_samples.stat.txt";
+    uint64_t c = 0;
+    check(mf_kmers_samples_count(ctx, fp.data(), (int)fp.size(), b, k, out.c_str(), st.c_str(), &c));
+    logmsg("INFO", "%s k-mers found, %s (100.0%%) of them is good (not erroneous)", group_digits(c).c_str(), group_digits(c).c_str());
+    if (c == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
+    logmsg("INFO", "Good k-mers printed to %s", out.c_str());
+    return {PV::file("resulting-kmers-file", out)};
+}
+// the group comparisons (no -k: the joins work on the files' 64-bit keys).  What the library refuses is refused here first, in its words.
+struct Groups { vector<string> files[3]; double pchi2, pmw; string out_dir; };
+static Groups groups_of(Run &r, int n) {
+    Groups g;
+    for (int i = 0; i < n; i++) g.files[i] = r.a.list(i == 0 ? "a-kmers" : i == 1 ? "b-kmers" : "c-kmers");
+    g.pchi2 = r.real("p-value-chi2"); g.pmw = r.real("p-value-mw");
+    return g;
+}
+static void check_groups(const Run &r, const Groups &g, int n) {
+    const vector<string> &af = g.files[0], &bf = g.files[1], &cf = g.files[2];
+    if (n == 2 && (af.empty() || bf.empty())) die("%s: both groups need at least one sample (|A| = %zu, |B| = %zu)", r.t.name, af.size(), bf.size());
+    if (n == 3 && (af.empty() || bf.empty() || cf.empty()))
+        die("%s: every group needs at least one sample (|A| = %zu, |B| = %zu, |C| = %zu)", r.t.name, af.size(), bf.size(), cf.size());
+    if (!(g.pchi2 >= 0.0 && g.pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", g.pchi2);
+}
+static void log_group_files(const string &out_dir, int n) {
+    for (int i = 0; i < n; i++) logmsg("INFO", "Group %c k-mers printed to %s", 'A' + i, (out_dir + "/filtered_group" + char('A' + i) + ".kmers.bin").c_str());
+}
+// the counters of stats-kmers (n = 2) and stats-kmers-3 (n = 3): c[6 .. 6 + n) the groups, c[6 + n] the unique k-mers left
+static void log_stats_counters(const uint64_t *c, int n) {
+    uint64_t left = 0; for (int i = 0; i < n; i++) left += c[6 + i];
+    logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
+    logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
+    logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
+    logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)left);
+    logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[6 + n]);
+    for (int i = 0; i < n; i++) logmsg("INFO", "Total group %c k-mers = %llu", 'A' + i, (unsigned long long)c[6 + i]);
+    logmsg("DEBUG", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
+    logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
+    logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
+}
+static vector<PV> tool_stats_kmers(Run &r) {
+    // StatsKmersFinder.java:89-297, StatsKmers3GroupsFinder.java:92-343
+    const int n = !strcmp(r.t.name, "stats-kmers-3") ? 3 : 2;
+    const Groups g = groups_of(r, n);
+    const int b = r.num("maximal-bad-frequence");
+    const string out_dir = r.str("output-dir");
+    if (n == 3) check_groups(r, g, n);
+    mkdirs(out_dir);
+    if (n == 3) r.entry(mf_stats_kmers3 != nullptr, "mf_stats_kmers3"); else r.entry(mf_stats_kmers != nullptr, "mf_stats_kmers");
+    mf_ctx *ctx = r.ctx();
+    logmsg("INFO", "Loading k-mers occurrences...");
+    auto pa = cptrs(g.files[0]), pb = cptrs(g.files[1]), pc = cptrs(g.files[2]);
+    uint64_t c[MF_STATS3_COUNTERS] = {0};
+    static_assert(MF_STATS_COUNTERS <= MF_STATS3_COUNTERS, "one array for both");
+    if (n == 3) check(mf_stats_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), b, g.pchi2, g.pmw, out_dir.c_str(), c));
+    else check(mf_stats_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), b, g.pchi2, g.pmw, out_dir.c_str(), c));
+    logmsg("INFO", "Survived after chi-squared test k-mers printed to: %s", (out_dir + "/filtered_chisquared.kmers.bin").c_str());
+    log_group_files(out_dir, n);
+    log_stats_counters(c, n);
+    if (n == 3) return {PV::file("filtered-kmers-file", out_dir + "/filtered_chisquared.kmers.bin")};
+    return {PV::files("resulting-kmers-file", {out_dir + "/filtered_groupA.kmers.bin"})};
+}
+static vector<PV> tool_specific_kmers(Run &r) {
+    // SpecificKmersFinder.java:65-216 (no -b either: every file is read at threshold 0)
+    const Groups g = groups_of(r, 2);
+    const string out_dir = r.str("output-dir");
+    check_groups(r, g, 2);
+    mkdirs(out_dir);
+    r.entry(mf_specific_kmers != nullptr, "mf_specific_kmers");
+    mf_ctx *ctx = r.ctx();
+    logmsg("INFO", "Splitting k-mers...");
+    auto pa = cptrs(g.files[0]), pb = cptrs(g.files[1]);
+    uint64_t c[MF_SPECIFIC_COUNTERS] = {0};
+    check(mf_specific_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), g.pchi2, g.pmw, out_dir.c_str(), c));
+    log_group_files(out_dir, 2);
+    logmsg("INFO", "Total specific k-mers in Group A = %llu", (unsigned long long)c[MF_SPECIFIC_GROUP_A]);
+    logmsg("INFO", "Total specific k-mers in Group B = %llu", (unsigned long long)c[MF_SPECIFIC_GROUP_B]);
+    logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[MF_SPECIFIC_UNIQUE]);
+    logmsg("DEBUG", "Total scarce k-mers = = %llu", (unsigned long long)c[MF_SPECIFIC_SCARCE]);
+    logmsg("DEBUG", "Total skipped by chi-squared test = %llu", (unsigned long long)c[MF_SPECIFIC_SKIP_CHI2]);
+    logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[MF_SPECIFIC_SKIP_MW]);
+    logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[MF_SPECIFIC_UNIQUE_LEFT]);
+    logmsg("DEBUG", "Total kmers left = %llu", (unsigned long long)(c[MF_SPECIFIC_GROUP_A] + c[MF_SPECIFIC_GROUP_B]));
+    logmsg("DEBUG", "Processed %llu k-mers", (unsigned long long)c[MF_SPECIFIC_TOTAL]);
+    return {};
+}
+static vector<PV> tool_specific_kmers3(Run &r) {
+    // SpecificKmers3GroupsFinder.java:70-280.  The counters are those of stats-kmers-3, logged at other levels: the groups at DEBUG, "scarce" at INFO
+    const Groups g = groups_of(r, 3);
+    const string out_dir = r.str("output-dir");
+    check_groups(r, g, 3);
+    mkdirs(out_dir);
+    r.entry(mf_specific_kmers3 != nullptr, "mf_specific_kmers3");
+    mf_ctx *ctx = r.ctx();
+    logmsg("INFO", "Splitting k-mers...");
+    auto pa = cptrs(g.files[0]), pb = cptrs(g.files[1]), pc = cptrs(g.files[2]);
+    uint64_t c[MF_SPECIFIC3_COUNTERS] = {0};
+    check(mf_specific_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), g.pchi2, g.pmw, out_dir.c_str(), c));
+    log_group_files(out_dir, 3);
+    logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
+    logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
+    logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
+    logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7] + c[8]));
+    logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[9]);
+    logmsg("DEBUG", "Total group A k-mers = %llu", (unsigned long long)c[6]);
+    logmsg("DEBUG", "Total group B k-mers = %llu", (unsigned long long)c[7]);
+    logmsg("DEBUG", "Total group C k-mers = %llu", (unsigned long long)c[8]);
+    logmsg("INFO", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
+    logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
+    logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
+    return {};
+}
+static vector<PV> tool_unique_kmers(Run &r) {
+    // UniqueKmersFinder.java:73-144: the pooled k-mers of the input files that no filter file holds
+    const int k = r.k;
+    check_k(k);
+    const int b = r.num("maximal-bad-frequence");
+    const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
+    const vector<string> files = r.a.list("k-mers"), filt = r.a.list("filter-kmers");
+    r.entry(mf_unique_kmers != nullptr, "mf_unique_kmers");
+    mf_ctx *ctx = r.ctx();
+    mkdirs(out_dir); mkdirs(st_dir);
+    auto fp = cptrs(files), ff = cptrs(filt);
+    const string out = out_dir + "/filtered.kmers.bin", st = st_dir + "/filtered.stat.txt";
+    uint64_t n = 0, c = 0;
+    logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
+    check(mf_unique_kmers(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, out.c_str(), st.c_str(), &n, &c));
+    logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n).c_str(),
+           group_digits(c).c_str(), percent_or_nan(c, n).c_str());
+    if (n == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
+    else if (c == 0 || c < (uint64_t)(int64_t)(n * 0.03))
+        logmsg("WARN", "Too few good k-mers were found! Perhaps you should decrease k-mer size or --maximal-bad-frequency value");
+    const uint64_t all_kmers = (1ull << (2 * k)) / 2;                   // (4^k)/2
+    if (n == all_kmers) logmsg("WARN", "All possible k-mers were found in reads! Perhaps you should increase k-mer size");
+    else if (n >= (uint64_t)(int64_t)(all_kmers * 0.99)) logmsg("WARN", "Almost all possible k-mers were found in reads! Perhaps you should increase k-mer size");
+    logmsg("INFO", "Good k-mers printed to %s", out.c_str());
+    return {PV::file("resulting-kmers-file", out)};
+}
+static vector<PV> tool_kmers_grouped_counter(Run &r) {
+    // KmersGroupedSamplesCounter.java:82-190: per k-mer of -kf the CD, UC and nonIBD files that hold it with a count > b
+    const int k = r.k;
+    check_k(k);
+    const int b = r.num("maximal-bad-frequence");
+    const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
+    const vector<string> kf = r.a.list("kmers-file"), cd = r.a.list("cd-kmers"), uc = r.a.list("uc-kmers"), ni = r.a.list("nonibd-kmers");
+    mkdirs(out_dir); mkdirs(st_dir);
+    r.entry(mf_kmers_grouped_count != nullptr, "mf_kmers_grouped_count");
+    mf_ctx *ctx = r.ctx();
+    auto pkf = cptrs(kf), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni);
+    const string out = out_dir + "/kmers.groups.txt";
+    uint64_t c = 0;
+    logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
+    check(mf_kmers_grouped_count(ctx, pkf.data(), (int)pkf.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(), b, k,
+                                 out.c_str(), &c));
+    logmsg("INFO", "K-mers printed to %s", out.c_str());
+    return {};
+}
+static vector<PV> tool_kmers_per_sample(Run &r) {
+    // KmersPerSampleCounter.java:56-157: the abundance in every file of the k-mers that enough files hold (no -b: every load is at 0).
+    // The first file is not counted, as in the reference (:82-96): count_first = 0.
+    const int k = r.k;
+    check_k(k);
+    const int perc = r.num("percent-present");
+    const string out_dir = r.str("output-dir");
+    const vector<string> files = r.a.list("k-mers");
+    mkdirs(out_dir);
+    r.entry(mf_kmers_per_sample != nullptr, "mf_kmers_per_sample");
+    mf_ctx *ctx = r.ctx();
+    auto fp = cptrs(files);
+    const string out = out_dir + "/selected_kmers_" + std::to_string(perc) + ".txt";
+    uint64_t c = 0;
+    logmsg("INFO", "Loading all k-mers...");
+    logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
+    check(mf_kmers_per_sample(ctx, fp.data(), (int)fp.size(), k, perc, 0, out.c_str(), &c));
+    logmsg("DEBUG", "Selected k-mers = %s", group_digits(c).c_str());
+    logmsg("INFO", "K-mers printed to %s", out.c_str());
+    return {};
+}
+static vector<PV> tool_unique_kmers_multi(Run &r) {
+    // UniqueKmersMultipleSamplesFinder.java:84-185: the k-mers that enough input files hold and no filter file does
+    const int k = r.k;
+    check_k(k);
+    const int mn = r.num("min-samples"), mx = r.num("max-samples"), b = r.num("maximal-bad-frequence");
+    if (mn > mx) die("--min-samples parameter cannot be greater than --max-samples parameter.");
+    const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
+    const vector<string> files = r.a.list("k-mers"), filt = r.a.list("filter-kmers");
+    r.entry(mf_unique_kmers_multi != nullptr, "mf_unique_kmers_multi");
+    mf_ctx *ctx = r.ctx();
+    mkdirs(out_dir); mkdirs(st_dir);
+    auto fp = cptrs(files), ff = cptrs(filt);
+    const int64_t top = std::min<int64_t>(mx, std::max<int64_t>(mn, (int64_t)files.size() + 1));
+    vector<uint64_t> c((size_t)std::max<int64_t>(1, top - mn + 1), 0);
+    int n_out = 0; uint64_t n_union = 0;
+    check(mf_unique_kmers_multi(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, mn, mx, out_dir.c_str(), &n_out, &n_union, c.data()));
+    for (int q = 0; q < n_out; q++) {
+        const string out = out_dir + "/filtered_" + std::to_string(mn + q) + ".kmers.bin";
+        logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n_union).c_str(),
+               group_digits(c[(size_t)q]).c_str(), percent_or_nan(c[(size_t)q], n_union).c_str());
+        if (c[(size_t)q] == 0) { logmsg("INFO", "No good k-mers found. Stop at maxSamples=%d", mn + q); break; }
+        logmsg("INFO", "Good k-mers printed to %s", out.c_str());
+    }
+    return {PV::files("resulting-kmers-file", {out_dir + "/filtered_" + std::to_string(mn) + ".kmers.bin"})};
+}
+static vector<PV> tool_kmers_multiple_filters(Run &r) {
+    // KmersMultipleFilters.java:77-133: every input file against the CD, UC and nonIBD sets of n_samples files
+    const int k = r.k;
+    check_k(k);
+    const int b = r.num("maximal-bad-frequence");
+    const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
+    const vector<string> files = r.a.list("k-mers"), cd = r.a.list("cd-filter-kmers"), uc = r.a.list("uc-filter-kmers"), ni = r.a.list("nonibd-filter-kmers");
+    r.entry(mf_kmers_multiple_filters != nullptr, "mf_kmers_multiple_filters");
+    mf_ctx *ctx = r.ctx();
+    mkdirs(out_dir); mkdirs(st_dir);
+    vector<string> ok, os;
+    for (auto &f : files) {
+        // file.getName().replaceAll(".kmers.bin", ""): a regular expression, every '.' matches any character but a line end
+        const string base = basename_of(f), pat = ".kmers.bin";
+        string name;
+        for (size_t q = 0; q < base.size();) {
+            bool m = q + pat.size() <= base.size();
+            for (size_t r = 0; m && r < pat.size(); r++) m = pat[r] == '.' ? (base[q + r] != '\n' && base[q + r] != '\r') : base[q + r] == pat[r];
+            if (m) q += pat.size(); else name.push_back(base[q++]);
+        }
+        ok.push_back(out_dir + "/" + name + ".kmers.bin"); os.push_back(st_dir + "/" + name + ".stat.txt");
+    }
+    auto fp = cptrs(files), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni), pok = cptrs(ok), pos = cptrs(os);
+    vector<uint64_t> fk(2 * files.size() + 2, 0);
+    check(mf_kmers_multiple_filters(ctx, fp.data(), (int)fp.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(),
+                                    b, k, pok.data(), pos.data(), fk.data()));
+    for (size_t j = 0; j < files.size(); j++) {
+        logmsg("INFO", "%s k-mers found, %s (%s%%) of them survived after filtering", group_digits(fk[2 * j]).c_str(), group_digits(fk[2 * j + 1]).c_str(),
+               percent_or_nan(fk[2 * j + 1], fk[2 * j]).c_str());
+        logmsg("INFO", "Filtered k-mers printed to %s", ok[j].c_str());
+    }
+    return {};
+}
+static vector<PV> tool_kmers_color(Run &r) {
+    // ColorKmersMain.java:89-136: per k-mer and class 0 / 1 / 2 the number of samples that hold it (-val: their summed coverage)
+    const int k = r.k;
+    check_k(k);
+    const int b = r.num("maximal-bad-frequency");
+    const bool val = r.a.flag("val");
+    const string out_dir = r.str("output-dir"), cls = r.str("class");
+    const vector<string> files = r.a.list("k-mers");
+    logmsg("INFO", "Loading class file...");
+    // readFileToColor :70-82: tab-separated lines, name (the file name without .kmers.bin) and class
+    std::map<string, int> color;
+    {
+        FILE *f = fopen(cls.c_str(), "r");
+        if (!f) die("Cannot read file: %s", cls.c_str());
+        char line[8192]; int ln = 0;
+        while (fgets(line, sizeof line, f)) {
+            ln++;
+            string l(line);
+            while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+            const size_t t1 = l.find('\t');
+            if (t1 == string::npos) { fclose(f); die("class file %s, line %d: no tab-separated class after '%s'", cls.c_str(), ln, l.c_str()); }
+            const size_t t2 = l.find('\t', t1 + 1);
+            const string name = l.substr(0, t1), cv = l.substr(t1 + 1, t2 == string::npos ? string::npos : t2 - t1 - 1);
+            char *end; const long c = strtol(cv.c_str(), &end, 10);
+            if (cv.empty() || *end) { fclose(f); die("class file %s, line %d: can't parse class '%s' of sample '%s'", cls.c_str(), ln, cv.c_str(), name.c_str()); }
+            if (c < 0 || c > 2) { fclose(f); die("class file %s, line %d: sample '%s' has class %ld (the classes are 0, 1 and 2)", cls.c_str(), ln, name.c_str(), c); }
+            color[name] = (int)c;
+        }
+        fclose(f);
+    }
+    vector<int> classes;
+    for (auto &fn : files) {
+        const string name = remove_ext(basename_of(fn), {".kmers.bin"});
+        auto it = color.find(name);
+        if (it == color.end()) die("class file %s has no line for sample '%s' (%s)", cls.c_str(), name.c_str(), fn.c_str());
+        classes.push_back(it->second);
+    }
+    if (files.size() > 1024) die("kmers-color: %zu k-mers files, at most 1024 (a field of the packed value holds 20 bits)", files.size());
+    mkdirs(out_dir);
+    r.entry(mf_kmers_color != nullptr, "mf_kmers_color");
+    mf_ctx *ctx = r.ctx();
+    logmsg("INFO", "Loading kmers files...");
+    auto fp = cptrs(files);
+    const string out = out_dir + "/colored_kmers.kmers.bin", st = out_dir + "/colored_kmers.stat.txt";
+    uint64_t c = 0;
+    check(mf_kmers_color(ctx, fp.data(), classes.data(), (int)fp.size(), b, val ? 1 : 0, k, out.c_str(), st.c_str(), &c));
+    logmsg("INFO", "%s colored k-mers printed to %s", group_digits(c).c_str(), out.c_str());
+    return {PV::file("resulting-kmers-file", out)};
+}
+static vector<PV> tool_component_colored(Run &r) {
+    // ColoredComponentMain.java:83-119, default and --separate modes of ColoredComponentsBuilder
+    const int k = r.k;
+    check_k(k);
+    const int groups = r.num("n_groups"), ncomps = r.num("n_comps");
+    const bool separate = r.a.flag("separate");
+    const double perc = r.real("perc");
+    if (r.a.flag("linear"))
+        die("component-colored: --linear is not supported: its result depends on the iteration order of the reference's hash map");
+    if (ncomps != -1)
+        die("component-colored: --n_comps %d is not supported (only -1, all components): which components are selected depends on the iteration order of the reference's hash map", ncomps);
+    if (groups < 1) die("component-colored: --n_groups %d: at least 1", groups);
+    const string out_dir = r.str("output-dir"), stat = r.wd + "/components-stat.txt";
+    const vector<string> files = r.a.list("k-mers");
+    mkdirs(out_dir);
+    r.entry(mf_colored_components != nullptr, "mf_colored_components");
+    mf_ctx *ctx = r.ctx();
+    logmsg("DEBUG", "Loading colored k-mers...");
+    logmsg("INFO", "Searching for colored components...");
+    auto fp = cptrs(files);
+    vector<uint64_t> cnt((size_t)groups, 0);
+    // (IOUtils.loadLongKmers(files, k, ...): the reference passes k where the loader takes its value threshold)
+    check(mf_colored_components(ctx, fp.data(), (int)fp.size(), k, (int64_t)k, groups, separate ? 1 : 0, perc, out_dir.c_str(), stat.c_str(), cnt.data()));
+    uint64_t total = 0;
+    vector<string> written;
+    for (int c = 0; c < groups; c++) {
+        total += cnt[(size_t)c];
+        logmsg("INFO", "%s components were found for class %d", group_digits(cnt[(size_t)c]).c_str(), c);
+        written.push_back(out_dir + "/components_color_" + std::to_string(c) + ".bin");
+    }
+    logmsg("INFO", "Total %s components were found", group_digits(total).c_str());
+    return {PV::files("components-files", written)};
+}
+static vector<PV> tool_comp2seq(Run &r) {
+    // ComponentsToSequences.java:41-76: bin2fasta, kmer-counter-many -b 0, seq-builder-many -b 0 -l k as sub-steps with the work
+    // directories kmers_fasta, kmer-counter-many and seq-builder-many -- here one segmented build of all components (mf_comp2seq)
+    const int k = r.k; const string &wd = r.wd;
+    check_k(k);
+    const bool split = r.a.flag("split");
+    const string cf = r.str("components-file");
+    r.entry(mf_comp2seq != nullptr, "mf_comp2seq");
+    mf_ctx *ctx = r.ctx();
+    uint64_t nf = 0, ns = 0;
+    check(mf_comp2seq(ctx, cf.c_str(), k, split ? 1 : 0, wd.c_str(), &nf, &ns));
+    if (split) logmsg("INFO", "%s components loaded from %s", group_digits(nf).c_str(), cf.c_str());
+    logmsg("INFO", "%s sequences found", group_digits(ns).c_str());
+    if (ns == 0) logmsg("WARN", "No sequences were found! Perhaps you should decrease --min-seq-len or --maximal-bad-frequency values");
+    logmsg("INFO", "Sequences printed to %s", (wd + "/seq-builder-many/sequences").c_str());
+    vector<string> written;
+    for (uint64_t i = 0; i < nf; i++) written.push_back(wd + "/seq-builder-many/sequences/component" + (split ? "_" + std::to_string(i + 1) : string()) + ".seq.fasta");
+    return {PV::files("output-files", written)};
+}
+static vector<PV> tool_comp2graph(Run &r) {
+    // ComponentsToGraph.java:70-130: one Comp2Graph per component on a thread pool, a HashMap of strings and a quadratic merge loop
+    // each -- here the graphs of all components in one pass, the text formatted on the device (mf_comp2graph)
+    const int k = r.k;
+    check_k(k);
+    const string cf = r.str("components-file"), gf = r.str("graph-file");
+    const vector<string> files = r.a.list("k-mers");
+    const bool cov = r.a.flag("coverage");                                // (without -i: accepted and ignored, as in the reference)
+    r.entry(mf_comp2graph != nullptr, "mf_comp2graph");
+    mf_ctx *ctx = r.ctx();
+    auto fp = cptrs(files);
+    uint64_t nc = 0, ns = 0, nl = 0;
+    check(mf_comp2graph(ctx, cf.c_str(), k, files.empty() ? nullptr : fp.data(), (int)files.size(), cov ? 1 : 0, gf.c_str(), &nc, &ns, &nl));
+    logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
+    logmsg("INFO", "Graph components saved to GFA format!");
+    return {PV::file("graph-file", gf)};
+}
+static vector<PV> tool_seq2comp(Run &r) {
+    // SequencesToComponents.java:61-103: a component per sequence that survives the readers, its members the distinct canonical k-mers
+    // (a LongArraySet with a linear scan per add there: quadratic in the sequence's length) -- here a segmented set-build on the
+    // device (mf_seq2comp).  Components in file order, then record order (the reference: as its thread pool finishes); a sequence
+    // shorter than k keeps its place as an empty component
+    const int k = r.k;
+    check_k(k);
+    const vector<string> files = r.a.list("sequences");
+    const string cf = r.str("components-file"), sf = r.wd + "/components-stat.txt";
+    for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
+    r.entry(mf_seq2comp != nullptr, "mf_seq2comp");
+    mf_ctx *ctx = r.ctx();
+    logmsg("DEBUG", "Loading sequences from files...");
+    auto fp = cptrs(files);
+    vector<uint64_t> per(files.size() + 1, 0);
+    uint64_t nc = 0;
+    mkparent(cf);
+    check(mf_seq2comp(ctx, files.empty() ? nullptr : fp.data(), (int)files.size(), k, cf.c_str(), sf.c_str(), &nc, per.data()));
+    for (size_t i = 0; i < files.size(); i++) {          // (the reference logs each pair as it goes; the numbers are the same)
+        logmsg("INFO", "Loading file %s...", basename_of(files[i]).c_str());
+        logmsg("INFO", "%llu components added", (unsigned long long)per[i]);
+    }
+    logmsg("INFO", "Total %s components were found", group_digits(nc).c_str());
+    logmsg("INFO", "Components saved to %s", cf.c_str());
+    describe(sf, "File with components' statistics (in text format)");
+    describe(cf, "File with components made from the input sequences, one per sequence (in binary format)");
+    return {PV::file("components-file", cf), PV::file("components-stat", sf)};
+}
+static vector<PV> tool_component_paths(Run &r) {
+    // ComponentPathsMain.java:82-190: for every sequence one hash set per selected component is probed, O(components x bases) -- here
+    // one lookup per k-mer position in an index over the members of all selected components, the runs found, paired, capped, sorted
+    // and printed on the device (mf_comppaths.hip).  Without a selection the reference logs its message and ends cleanly; here the
+    // run fails with it.  A number out of range is an exception there and an error here.
+    const int k = r.k;
+    check_k(k);
+    const string cf = r.str("components-file"), od = r.str("output-dir");
+    const vector<string> files = r.a.list("seq");
+    const bool all = r.a.flag("all-components");
+    const int min_len = r.num("min-length");
+    vector<uint32_t> sel;
+    for (auto &v : r.a.list("components")) {
+        char *end = nullptr; const long long no = strtoll(v.c_str(), &end, 10);
+        if (v.empty() || *end) die("Can't parse integer value '%s' of option --components", v.c_str());
+        if (no < 1 || no > 0xFFFFFFFFll) die("There is no component %s (components are numbered from 1)", v.c_str());
+        sel.push_back((uint32_t)no);
+    }
+    if (!all && sel.empty()) die("No components to process!!! Do you forget to set --all-components or --components n1,n2,...?");
+    if (!exists(cf)) die("Can't load components: file not found (%s)", cf.c_str());
+    for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
+    r.entry(mf_paths_create && mf_paths_add && mf_paths_finish && mf_paths_destroy && mf_paths_slots && mf_paths_write && mf_paths_stats && mf_comps_load &&
+            mf_comps_set_k && mf_comps_stats && mf_comps_destroy && mf_reads_load && mf_reads_stats && mf_reads_device_view && mf_reads_destroy, "mf_paths_create");
+    mf_ctx *ctx = r.ctx();
+    logmsg("DEBUG", "Loading components...");
+    mf_comps *c = nullptr;
+    check(mf_comps_load(ctx, cf.c_str(), &c));
+    check(mf_comps_set_k(c, k));
+    uint64_t nc = 0;
+    check(mf_comps_stats(c, &nc, nullptr));
+    logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
+    if (all && nc == 0) die("No components to process!!!");
+    logmsg("DEBUG", "Preparing...");
+    mf_paths *paths = nullptr;
+    const uint64_t max_paths = 1000000;                                   // MAX_PATHS_COUNT (:30)
+    check(mf_paths_create(ctx, c, all ? nullptr : sel.data(), all ? 0 : sel.size(), min_len, max_paths, &paths));
+    logmsg("DEBUG", "Loading sequences and extracting paths...");
+    for (auto &f : files) {                                               // one file resident at a time
+        logmsg("INFO", "Loading file %s...", basename_of(f).c_str());
+        const char *fp = f.c_str();
+        mf_reads *r = nullptr;
+        check(mf_reads_load(ctx, &fp, 1, &r));
+        const void *db = nullptr, *doff = nullptr; uint64_t nr = 0, nb = 0;
+        check(mf_reads_stats(r, &nr, &nb));
+        check(mf_reads_device_view(r, &db, &doff));
+        check(mf_paths_add(paths, db, doff, nr, nb));
+        mf_reads_destroy(r);
+    }
+    check(mf_paths_finish(paths));
+    uint64_t nslots = 0;
+    check(mf_paths_stats(paths, &nslots, nullptr, nullptr, nullptr));
+    vector<uint32_t> no(nslots + 1, 0); vector<uint8_t> reached(nslots + 1, 0);
+    check(mf_paths_slots(paths, no.data(), nullptr, nullptr, reached.data()));
+    for (uint64_t i = 0; i < nslots; i++)
+        if (reached[i]) logmsg("WARN", "Too many paths in component %u, keeping only first %llu of them!", no[i], (unsigned long long)max_paths);
+    logmsg("INFO", "Sorting...");
+    logmsg("INFO", "Saving to files...");
+    mkparent(od);
+    uint64_t np = 0;
+    check(mf_paths_write(paths, od.c_str(), &np));
+    mf_paths_destroy(paths);
+    mf_comps_destroy(c);
+    logmsg("INFO", "Paths for %llu component(s) were saved in directory %s", (unsigned long long)nslots, od.c_str());
+    return {};
+}
+static vector<PV> tool_view(Run &r) { run_view(r.a, r.k); return {}; }
+static vector<PV> tool_bin2fasta(Run &r) { run_bin2fasta(r.a, r.k); return {}; }
+static vector<PV> tool_heatmap_maker(Run &r) {
+    const bool wr = r.a.flag("without-renumbering");
+    const string nm = run_heatmap_maker(r.e, r.str("matrix-file"), r.str("newMatrix-file"), wr, r.str("output-format"));
+    return {PV::null("heatmap-file"), wr ? PV::null("newMatrix-file-out") : PV::file("newMatrix-file-out", nm)};
+}
+static vector<PV> tool_matrix_builder(Run &r) {
+    // DistanceMatrixBuilderMain.java:88-175: steps kmer-counter-many, seq-builder-many, component-cutter, features-calculator,
+    // dist-matrix-calculator, heatmap-maker (its image is not rendered here).  What the builder does not fix is the step's own default.
+    Env &e = r.e; const Args &a = r.a; const string &wd = r.wd, &start = r.start, &finish = r.finish; const int k = r.k; bool &force = r.force;
+    vector<string> reads = a.list("reads");
+    logmsg("INFO", "Found %zu libraries to process", reads.size());
+    if (reads.empty()) die("No libraries to process!!! Can't continue the calculations.");
+    const bool use_reads = a.flag("use-reads-for-calculating-features");                       // DistanceMatrixBuilderMain.java:162-165
+    check_k(k);
+    // (-b in either spelling: the counters' --maximal-bad-frequence is taken where --maximal-bad-frequency is not given)
+    const int b = a.geti("maximal-bad-frequency", a.geti("maximal-bad-frequence", atoi(r.dflt("maximal-bad-frequency").c_str()))), l = r.num("min-seq-len");
+    const int b1 = r.num("min-component-size"), b2 = r.num("max-component-size");
+    static const char *STEPS[] = {"kmer-counter-many", "seq-builder-many", "component-cutter", "features-calculator", "dist-matrix-calculator", "heatmap-maker"};
+    for (const string *bound : {&start, &finish})                           // Tool.checkBoundExistence :726-741
+        if (!bound->empty() && std::find_if(std::begin(STEPS), std::end(STEPS), [&](const char *n) { return *bound == n; }) == std::end(STEPS))
+            die("There is no substep with name '%s' in step matrix-builder!", bound->c_str());
+    {   // createOutputDescFiles :178-200
+        g_desc_files = {"output_description.txt", wd + "/output_description.txt"};
+        time_t t = time(nullptr); struct tm tmv; localtime_r(&t, &tmv);
+        char hdr[128]; strftime(hdr, sizeof hdr, "%d-%b-%Y (%a) %H:%M:%S", &tmv);
+        for (auto &d : g_desc_files) {
+            FILE *f = fopen(d.c_str(), "w");
+            if (!f) { logmsg("WARN", "Can't create file %s, skipping", d.c_str()); continue; }
+            fprintf(f, "# Output files' description for run started at %s\n\n%s\n%s\n   Identical files with run log\n\n%s\n%s\n   Identical files with output files' description\n",
+                    hdr, (wd + "/log").c_str(), (wd + "/logs/log_" + e.start_ts).c_str(), g_desc_files[0].c_str(), g_desc_files[1].c_str());
+            fclose(f);
+        }
+    }
+    const string d1 = wd + "/kmer-counter-many", d2 = wd + "/seq-builder-many", d3 = wd + "/component-cutter", d4 = wd + "/features-calculator",
+                 d5 = wd + "/dist-matrix-calculator", d6 = wd + "/heatmap-maker";
+    const string dirs[] = {d1, d2, d3, d4, d5, d6};
+    // --finish <step>: stop after it; the next step's results are outdated then (:512-527)
+    auto finished = [&](int i) {
+        if (finish.empty() || finish != STEPS[i]) return false;
+        if (i + 1 < 6) { unlink((dirs[i + 1] + "/SUCCESS").c_str()); unlink((dirs[i + 1] + "/in.properties").c_str()); }
+        return true;
+    };
+    auto done = [&]() -> vector<PV> { for (mf_ctx *c : e.ctxs) if (c) mf_ctx_destroy(c); exit(0); };      // (a run cut short by --finish ends here: no out.properties, no SUCCESS)
+    vector<string> kmers, seqs, vecs;
+    // 1 kmer-counter-many
+    const string stats_dir = r.str("stats-dir"), kmers_dir = sub_default(r, STEPS[0], "output-dir", d1);
+    run_as_step(STEPS[0], d1, {PV("k", k), PV::files("reads", reads), PV("maximal-bad-frequence", b), PV::file("output-dir", kmers_dir), PV::file("stats-dir", stats_dir)},
+                start, force,
+                [&]() { kmers = run_kmer_counter_many(e, a, reads, k, b, d1, kmers_dir, stats_dir); return vector<PV>{PV::files("resulting-kmers-files", kmers)}; },
+                [&](const Props &o) { kmers = props_list(o, "resulting-kmers-files"); });
+    describe(stats_dir, "Directory with kmer frequency statistics (statistics files is in text format for every input reads file)");
+    if (finished(0)) return done();
+    // 2 seq-builder-many
+    const int bp = r.num("bottom-cut-percent");
+    const string seq_dir = sub_default(r, STEPS[1], "output-dir", d2);
+    run_as_step(STEPS[1], d2, {PV("k", k), PV::files("k-mers", kmers), PV("maximal-bad-frequency", b), bp >= 0 ? PV("bottom-cut-percent", bp) : PV::null("bottom-cut-percent"),
+                               PV("sequence-len", l), PV::file("output-dir", seq_dir)},
+                start, force,
+                [&]() { seqs = run_seq_builder_many(e, a, kmers, k, b, bp, l, d2, seq_dir);
+                        return vector<PV>{PV::files("output-files", seqs)}; },
+                [&](const Props &o) { seqs = props_list(o, "output-files"); });
+    describe(seq_dir, "Directory with FASTA files - paths from reads for every library");
+    if (finished(1)) return done();
+    // 3 component-cutter
+    const string comp = sub_default(r, STEPS[2], "components-file", d3), cstat = cutter_stat(d3, b1, b2);
+    run_as_step(STEPS[2], d3, {PV("k", k), PV("min-seq-len", l), PV("min-component-size", b1), PV("max-component-size", b2), PV::files("sequences", seqs), PV::file("components-file", comp)},
+                start, force,
+                [&]() { run_component_cutter(e, a, seqs, k, l, b1, b2, d3, comp); return vector<PV>{PV::file("components-file", comp), PV::file("components-stat", cstat)}; },
+                [&](const Props &) {});
+    describe(cstat, "File with components' statistics (in text format)");
+    describe(comp, "File with extracted components (in binary format)");
+    if (finished(2)) return done();
+    // 4 features-calculator
+    const vector<string> none;
+    const int thr = atoi(sub_default(r, STEPS[3], "threshold", d4).c_str());
+    run_as_step(STEPS[3], d4, {PV("k", k), PV::file("components-file", comp), PV::files("reads", use_reads ? reads : none), PV::files("kmers", use_reads ? none : kmers),
+                               PV::files("selected", a.list("selected")), PV("threshold", thr)},
+                start, force,
+                [&]() { vecs = use_reads ? run_features(e, a, comp, reads, {}, k, thr, d4) : run_features(e, a, comp, {}, kmers, k, thr, d4);
+                        return vector<PV>{PV::files("features-files", vecs), PV::file("features-dir", d4 + "/vectors")}; },
+                [&](const Props &o) { vecs = props_list(o, "features-files"); });
+    describe(d4 + "/vectors", "Directory with features values files for every library (in text format)");
+    if (finished(3)) return done();
+    // 5 dist-matrix-calculator: the matrix in the original order goes to <workDir>/matrices (:132-134)
+    string mpath = wd + "/matrices/dist_matrix_" + e.start_ts + "_original_order.txt";
+    const bool wn = a.flag("without-names");
+    const string fmt = r.str("output-format");
+    run_as_step(STEPS[4], d5, {PV::files("features", vecs), PV::flag("without-names", wn), PV::file("matrix-file", mpath), PV("output-format", fmt)},
+                start, force,
+                [&]() { mkdirs(wd + "/matrices"); mpath = run_dist_matrix(e, vecs, mpath, wn, fmt); return vector<PV>(); },
+                [&](const Props &) {});
+    describe(mpath, "File with resulted distance matrix between samples keeping original order");
+    if (finished(4)) return done();
+    // 6 heatmap-maker, numeric half: dendrogram order + renumbered matrix (:137-145)
+    const string npath = with_dt(r.str("matrix-file"), e.start_ts);
+    const bool wr = a.flag("without-renumbering");
+    run_as_step(STEPS[5], d6, {PV::file("matrix-file", mpath), PV::file("colors-file", r.str("colors-file")), PV::flag("without-renumbering", wr), PV::file("newMatrix-file", npath),
+                               PV::file("heatmap-file", with_dt(r.str("heatmap-file"), e.start_ts)), PV::flag("invert-colors", a.flag("invert-colors")), PV("output-format", fmt)},
+                start, force,
+                [&]() { run_heatmap_maker(e, mpath, npath, wr, fmt); return vector<PV>{PV::null("heatmap-file"), wr ? PV::null("newMatrix-file-out") : PV::file("newMatrix-file-out", npath)}; },
+                [&](const Props &) {});
+    if (!wr) describe(npath, "File with resulted distance matrix between samples with new order based on adjacency of the samples");
+    logmsg("INFO", "heatmap image (dist_matrix_<date>_heatmap.png) is not rendered by the HIP path");
+    if (finished(5)) return done();
+    return {};
+}
+
+// ------------------------------------------------------------------------------------------------ the table: one row per tool, in the order of -ts
+// name, description, run function; {short option, what it means here}; {mandatory argument, its short name in the message} in checking
+// order; {parameter, kind, default} in the reference's declaration order.  A new tool is one row here and one run function above.
+#define K_ {"k", VAL}
+#define B_(spelling, dflt) {"maximal-bad-" spelling, VAL, dflt}
+#define OUT_(dir) {"output-dir", FILE1, "$WD/" dir}
+#define STATS_ {"stats-dir", FILE1, "$WD/stats"}
+#define PVALUES_ {"p-value-chi2", VAL, "0.05"}, {"p-value-mw", VAL, "0.05"}
+static const Tool TOOLS[] = {
+    {"kmer-counter", "Count k-mers in given reads", tool_kmer_counter, {{"b", "maximal-bad-frequence"}}, {{"k", "k"}, {"reads", "i"}},
+     {K_, {"reads", FILES}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    {"kmer-counter-many", "Count k-mers in many files (one library = one output)", tool_kmer_counter_many, {{"b", "maximal-bad-frequence"}}, {{"k", "k"}, {"reads", "i"}},
+     {K_, {"reads", FILES}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    {"seq-builder", "Metagenome De Bruijn graph analysis and sequences building", tool_seq_builder, {{"i", "k-mers"}, {"l", "sequence-len"}},
+     {{"k", "k"}, {"k-mers", "i"}, {"sequence-len", "l"}}, {K_, {"k-mers", FILES}, B_("frequency", "1"), {"bottom-cut-percent", VAL}, {"sequence-len", VAL}, OUT_("sequences")}},
+    {"seq-builder-many", "seq-builder for many k-mers files", tool_seq_builder, {{"i", "k-mers"}, {"l", "sequence-len"}},
+     {{"k", "k"}, {"k-mers", "i"}, {"sequence-len", "l"}}, {K_, {"k-mers", FILES}, B_("frequency", nullptr), {"bottom-cut-percent", VAL}, {"sequence-len", VAL}, OUT_("sequences")}},
+    {"component-cutter", "Build graph components from sequences", tool_component_cutter, {{"i", "sequences"}}, {{"k", "k"}, {"sequences", "i"}},
+     {K_, {"min-seq-len", VAL, "100"}, {"min-component-size", VAL, "1000"}, {"max-component-size", VAL, "10000"}, {"sequences", FILES}, {"components-file", FILE1, "$WD/components.bin"}}},
+    {"features-calculator", "Calculate features values for input reads/k-mers files", tool_features, {}, {{"k", "k"}, {"components-file", "cm"}},
+     {K_, {"components-file", FILE1}, {"reads", FILES}, {"kmers", FILES}, {"selected", FILES}, {"threshold", VAL, "0"}}},
+    {"dist-matrix-calculator", "Calculate the distance matrix using features values", tool_dist_matrix, {}, {{"features"}},
+     {{"features", FILES}, {"without-names", FLAG}, {"matrix-file", DTFILE, "$WD/dist_matrix_$DT_original_order.txt"}, {"output-format", VAL, "%.4f"}}},
+    {"heatmap-maker", "Cluster the samples of a distance matrix and renumber it (no image)", tool_heatmap_maker, {{"i", "matrix-file"}}, {{"matrix-file", "i"}},   // HeatMapMakerMain.java:34-36
+     {{"matrix-file", FILE1}, {"colors-file", FILE1}, {"without-renumbering", FLAG}, {"newMatrix-file", FILE1}, {"heatmap-file", FILE1}, {"invert-colors", FLAG},
+      {"output-format", VAL, "%.4f"}}},
+    {"kmer-counter-posneg", "Count k-mers for files from two groups independently", tool_posneg, {}, {{"k", "k"}, {"positiveReads", "pos"}, {"negativeReads", "neg"}},
+     {K_, {"positiveReads", FILES}, {"negativeReads", FILES}, B_("frequency", "1"), OUT_("kmers_posneg")}},
+    {"kmers-filter", "Filter k-mers from test set according to known samples", tool_kmers_filter, {{"i", "k-mers"}, {"b", "maximal-bad-frequence"}},
+     {{"k", "k"}, {"k-mers", "i"}, {"filter-kmers"}}, {K_, {"k-mers", FILES}, {"filter-kmers", FILES}, B_("frequence", "1"), {"max-thresh", VAL, "0"}, OUT_("kmers"), STATS_}},
+    {"kmers-samples-counter", "Count number of samples containing k-mers from multiple samples", tool_kmers_samples_counter, {{"i", "k-mers"}, {"b", "maximal-bad-frequence"}},
+     {{"k", "k"}, {"k-mers", "i"}}, {K_, {"k-mers", FILES}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    // (stats-kmers: -i means --k-mers, which the tool does not declare: accepted and ignored)
+    {"stats-kmers", "Find k-mers that differ significantly between two groups of samples (chi-squared + Mann-Whitney)", tool_stats_kmers,
+     {{"i", "k-mers"}, {"b", "maximal-bad-frequence"}}, {{"a-kmers", "A"}, {"b-kmers", "B"}}, {{"a-kmers", FILES}, {"b-kmers", FILES}, PVALUES_, B_("frequence", "0"), OUT_("kmers")}},
+    {"stats-kmers-3", "Find k-mers that differ significantly between three groups of samples (chi-squared + Mann-Whitney)", tool_stats_kmers,
+     {{"b", "maximal-bad-frequence"}}, {{"a-kmers", "A"}, {"b-kmers", "B"}, {"c-kmers", "C"}},
+     {{"a-kmers", FILES}, {"b-kmers", FILES}, {"c-kmers", FILES}, PVALUES_, B_("frequence", "0"), OUT_("kmers")}},
+    {"specific-kmers", "Output k-mers specific to groups of samples based on chi-squared & Mann-Whitney tests", tool_specific_kmers, {}, {{"a-kmers", "A"}, {"b-kmers", "B"}},
+     {{"a-kmers", FILES}, {"b-kmers", FILES}, PVALUES_, OUT_("kmers")}},                                         // (SpecificKmersFinder.java:30-57: no maximal-bad-frequence)
+    {"specific-kmers-3", "Output k-mers specific to each of three groups of samples based on chi-squared & Mann-Whitney tests", tool_specific_kmers3, {},
+     {{"a-kmers", "A"}, {"b-kmers", "B"}, {"c-kmers", "C"}}, {{"a-kmers", FILES}, {"b-kmers", FILES}, {"c-kmers", FILES}, PVALUES_, OUT_("kmers")}},
+    {"kmers-grouped-counter", "Count number of samples from 3 groups containing specified k-mers", tool_kmers_grouped_counter,              // KmersGroupedSamplesCounter.java:38-60
+     {{"b", "maximal-bad-frequence"}, {"cd", "cd-kmers"}, {"uc", "uc-kmers"}, {"nonibd", "nonibd-kmers"}}, {{"k", "k"}, {"cd-kmers", "cd"}, {"uc-kmers", "uc"}, {"nonibd-kmers", "nonibd"}},
+     {K_, {"kmers-file", FILES}, {"cd-kmers", FILES}, {"uc-kmers", FILES}, {"nonibd-kmers", FILES}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    {"kmers-per-sample", "Counts the abundance of frequent k-mers from dataset in each sample", tool_kmers_per_sample, {{"i", "k-mers"}, {"perc", "percent-present"}},   // KmersPerSampleCounter.java:43-48
+     {{"k", "k"}, {"k-mers", "i"}}, {K_, {"k-mers", FILES}, {"percent-present", VAL, "20"}, OUT_("kmers_per_samples")}},
+    {"unique-kmers", "Output k-mers present in one dataset and missing in other", tool_unique_kmers, {{"i", "k-mers"}, {"b", "maximal-bad-frequence"}},
+     {{"k", "k"}, {"k-mers", "i"}, {"filter-kmers"}}, {K_, {"k-mers", FILES}, {"filter-kmers", FILES}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    {"unique-kmers-multi", "Output k-mers present in one dataset in fixed number of samples and missing in other", tool_unique_kmers_multi,
+     {{"i", "k-mers"}, {"b", "maximal-bad-frequence"}}, {{"k", "k"}, {"k-mers", "i"}, {"filter-kmers"}},
+     {K_, {"k-mers", FILES}, {"filter-kmers", FILES}, {"min-samples", VAL, "1"}, {"max-samples", VAL, "1"}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    {"kmers-multiple-filters", "Filter k-mers from test set according to three specified sets", tool_kmers_multiple_filters, {{"i", "k-mers"}, {"b", "maximal-bad-frequence"}},
+     {{"k", "k"}, {"k-mers", "i"}, {"cd-filter-kmers", "cd"}, {"uc-filter-kmers", "uc"}, {"nonibd-filter-kmers", "nonibd"}},
+     {K_, {"k-mers", FILES}, {"cd-filter-kmers", FILES}, {"uc-filter-kmers", FILES}, {"nonibd-filter-kmers", FILES}, B_("frequence", "1"), OUT_("kmers"), STATS_}},
+    {"kmers-color", "Color k-mers based on their occurrences in three groups of samples", tool_kmers_color, {{"kf", "k-mers"}},                     // ColorKmersMain.java:39-43
+     {{"k", "k"}, {"k-mers", "kf"}, {"class"}}, {K_, {"k-mers", FILES}, {"class", FILE1}, B_("frequency", "1"), {"val", FLAG}, OUT_("colored-kmers")}},
+    {"component-colored", "Extract graph components from tangled graph based on k-mers coloring", tool_component_colored, {{"i", "k-mers"}}, {{"k", "k"}, {"k-mers", "i"}},
+     {K_, {"k-mers", FILES}, {"n_groups", VAL, "3"}, {"separate", FLAG}, {"linear", FLAG}, {"n_comps", VAL, "-1"}, {"perc", VAL, "0.9"}, OUT_("colored-components")}},
+    {"comp2seq", "Transforms components in binary format to FASTA sequences (contigs)", tool_comp2seq, {}, {{"components-file", "cf"}},
+     {{"k", VAL, "31"}, {"components-file", FILE1}, {"split", FLAG}}},                                           // (ComponentsToSequences.java:21-26: k has a default)
+    {"comp2graph", "Transforms components in binary format to de Bruijn graph in GFA format", tool_comp2graph, {{"i", "k-mers"}}, {{"k", "k"}, {"components-file", "cf"}},
+     {K_, {"components-file", FILE1}, {"k-mers", FILES}, {"coverage", FLAG}, {"graph-file", FILE1, "$WD/components-graph.gfa"}}},
+    {"seq2comp", "Transforms sequences to components", tool_seq2comp, {{"i", "sequences"}}, {{"k", "k"}, {"sequences", "i"}},
+     {K_, {"sequences", FILES}, {"components-file", FILE1, "$WD/components.bin"}}},
+    {"component-paths", "Extracts paths in the components", tool_component_paths, {{"cm", "components"}, {"l", "min-length"}},                          // ComponentPathsMain.java:52-71
+     {{"k", "k"}, {"components-file", "cf"}, {"seq"}},
+     {K_, {"components-file", FILE1}, {"seq", FILES}, {"components", LIST}, {"all-components", FLAG}, {"min-length", VAL, "50"}, OUT_("paths")}},
+    {"view", "View different binary objects (k-mers files, components)", tool_view, {{"o", "output-file"}}, {},
+     {K_, {"kmers-file", FILE1}, {"components-file", FILE1}, {"output-file", FILE1}}},
+    {"bin2fasta", "Converts different binary objects to FASTA format", tool_bin2fasta, {{"o", "output-file"}}, {},
+     {K_, {"kmers-file", FILE1}, {"components-file", FILE1}, {"output-file", FILE1}}},
+    // matrix-builder: its own parameters, then the sub-tools' parameters it does not fix (Tool.addSubTool :168-207)
+    {"matrix-builder", "Build the distance matrix for input sequences (default tool)", tool_matrix_builder, {}, {{"reads", "i"}},
+     {{"k", VAL, "31"}, {"reads", FILES}, B_("frequency", "1"), {"min-seq-len", VAL, "100"}, {"use-reads-for-calculating-features", FLAG},
+      {"matrix-file", DTFILE, "$WD/matrices/dist_matrix_$DT.txt"}, {"heatmap-file", DTFILE, "$WD/matrices/dist_matrix_$DT_heatmap.png"},
+      {"stats-dir", FILE1, "$WD/kmer-counter-many/stats"}, {"bottom-cut-percent", VAL}, {"min-component-size", VAL, "1000"}, {"max-component-size", VAL, "10000"},
+      {"selected", FILES}, {"without-names", FLAG}, {"output-format", VAL, "%.4f"}, {"colors-file", FILE1}, {"without-renumbering", FLAG}, {"invert-colors", FLAG}}},
+};
+static const Tool *find_tool(const string &name) { for (auto &t : TOOLS) if (name == t.name) return &t; return nullptr; }
+static string tools_text() {                                // the -ts listing: the descriptions start in the fourth tab column
+    string s;
+    for (auto &t : TOOLS) s += string(t.name) + string(3 - strlen(t.name) / 8, '\t') + t.desc + "\n";
+    return s;
 }
 
 static double since_start() {
@@ -1048,22 +1677,18 @@ int main(int argc, char **argv) {
     string tool;
     Args a = parse_args(argc, argv, &tool);
     if (a.has("version")) { printf("MetaFast (MI355X HIP hot path) %s\n", mf_version()); return 0; }
-    if (a.has("tools")) { printf("Available tools:\n%s", TOOLS_TEXT); return 0; }
+    if (a.has("tools")) { printf("Available tools:\n%s", tools_text().c_str()); return 0; }
     if (a.has("help") || a.has("help-all")) {
         printf("Usage: metafast.sh [-t <tool>] [options]\n\nTools:\n%s\nLaunch options: -w/--work-dir <dir>  -p/--available-processors <n>  -c/--continue  --force  "
-               "-s/--start <step>  -f/--finish <step>  -v/--verbose  --devices <a,b,...> (default: every visible device, twice where two libraries fit side by side; the per-library steps run one library per entry)  --device <n>\nTool options follow the reference (see SURVEY.md 8(b1)).\n", TOOLS_TEXT);
+               "-s/--start <step>  -f/--finish <step>  -v/--verbose  --devices <a,b,...> (default: every visible device, twice where two libraries fit side by side; the per-library steps run one library per entry)  --device <n>\nTool options follow the reference (see SURVEY.md 8(b1)).\n", tools_text().c_str());
         return 0;
     }
-    static const char *KNOWN[] = {"kmer-counter", "kmer-counter-many", "seq-builder", "seq-builder-many", "component-cutter", "features-calculator",
-                                  "dist-matrix-calculator", "heatmap-maker", "view", "bin2fasta", "matrix-builder", "kmer-counter-posneg", "kmers-filter",
-                                  "kmers-samples-counter", "stats-kmers", "unique-kmers-multi", "kmers-multiple-filters", "kmers-color", "component-colored",
-                                  "stats-kmers-3", "specific-kmers", "specific-kmers-3", "unique-kmers", "seq2comp", "component-paths", "comp2graph",
-                                  "kmers-per-sample", "kmers-grouped-counter", "comp2seq"};
-    if (std::find_if(std::begin(KNOWN), std::end(KNOWN), [&](const char *n) { return tool == n; }) == std::end(KNOWN)) {
+    const Tool *t = find_tool(tool);
+    if (!t) {
         fprintf(stderr, "ERROR: Tool '%s' not found !\n", tool.c_str());          // itmo!/Runner.java:136-139
         return 1;
     }
-    g_verbose = a.get("verbose", "false") == "true";
+    g_verbose = a.flag("verbose");
     Env e;
     e.work_dir = a.get("work-dir", "workDir");
     e.start_ts = timestamp();
@@ -1078,17 +1703,17 @@ int main(int argc, char **argv) {
     }
     // ---- --continue / --force (Tool.run :400-462).  matrix-builder forces by default, unless -c or -s is given
     // (DistanceMatrixBuilderMain.java:23-26, 211-216).
-    bool cont = a.get("continue", "false") == "true", force = a.get("force", "false") == "true";
-    if (tool == "matrix-builder") {
+    const bool builder = t->run == tool_matrix_builder;
+    bool cont = a.flag("continue"), force = a.flag("force");
+    if (builder) {
         if (a.has("force")) die("Cannot parse command line: Unrecognized option: --force");       // (removed from its launch options, :25)
         force = !(a.has("continue") || a.has("start"));
     }
-    const string start = a.get("start"), finish = a.get("finish");
     const string inprop = wd + "/in.properties";
     if (cont && force) die("Continue and force options can't be set simultaneously");
     if (exists(inprop)) {
         if (cont) {}
-        else if (force) { if (tool != "matrix-builder") logmsg("WARN", "Force run, all data in working directory will be rewritten!"); }
+        else if (force) { if (!builder) logmsg("WARN", "Force run, all data in working directory will be rewritten!"); }
         else {
             fprintf(stderr, "Working directory (%s/) contains files from previous run, rewrite them? [Yes(y)/No(n), default:No] ", wd.c_str());
             char ans[64] = ""; if (!fgets(ans, sizeof ans, stdin)) ans[0] = 0;
@@ -1105,678 +1730,26 @@ int main(int argc, char **argv) {
         if (props_read(inprop, stored)) {
             // parameters not given on the command line take last run's values (loadUnsetParametersFromProperties :757-793)
             for (auto &kv : stored) if (!a.has(kv.first)) a.opt[kv.first] = kv.second;
-            can = can && props_equal(tool_inputs(tool, a, wd, e.start_ts), stored);
+            can = can && props_equal(tool_inputs(*t, a, wd, e.start_ts), stored);
         } else can = false;
     }
-    if (!force && start.empty() && can) {
+    Run r{e, a, *t, wd, a.get("start"), a.get("finish"), force, 0};
+    if (!force && r.start.empty() && can) {
         logmsg("INFO", "SUCCESS file found for tool %s - loading results...", tool.c_str());
         return 0;
     }
     unlink((wd + "/SUCCESS").c_str()); unlink((wd + "/out.properties").c_str());
-    const int k_dflt = (tool == "matrix-builder" || tool == "comp2seq") ? 31 : -1;      // (ComponentsToSequences.java:21-26)
-    int k = a.geti("k", k_dflt);
-    vector<PV> outs;
-
+    r.k = r.num("k");
     // mandatory parameters are checked before anything is written (Tool.checkArguments :712-724)
-    auto need = [&](const char *n, const char *shrt) { if (!a.has(n)) die("Mandatory argument --%s (-%s) not set", n, shrt); };
-    if (tool == "kmer-counter" || tool == "kmer-counter-many") { need("k", "k"); need("reads", "i"); }
-    else if (tool == "seq-builder" || tool == "seq-builder-many") { need("k", "k"); need("k-mers", "i"); need("sequence-len", "l"); }
-    else if (tool == "component-cutter") { need("k", "k"); need("sequences", "i"); }
-    else if (tool == "features-calculator") { need("k", "k"); need("components-file", "cm"); }
-    else if (tool == "dist-matrix-calculator") { if (!a.has("features")) die("Mandatory argument --features not set"); }
-    else if (tool == "heatmap-maker") need("matrix-file", "i");
-    else if (tool == "matrix-builder") need("reads", "i");
-    else if (tool == "kmer-counter-posneg") { need("k", "k"); need("positiveReads", "pos"); need("negativeReads", "neg"); }
-    else if (tool == "kmers-filter") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
-    else if (tool == "kmers-samples-counter") { need("k", "k"); need("k-mers", "i"); }
-    else if (tool == "stats-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
-    else if (tool == "stats-kmers-3") { need("a-kmers", "A"); need("b-kmers", "B"); need("c-kmers", "C"); }
-    else if (tool == "specific-kmers") { need("a-kmers", "A"); need("b-kmers", "B"); }
-    else if (tool == "specific-kmers-3") { need("a-kmers", "A"); need("b-kmers", "B"); need("c-kmers", "C"); }
-    else if (tool == "unique-kmers") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
-    else if (tool == "kmers-grouped-counter") { need("k", "k"); need("cd-kmers", "cd"); need("uc-kmers", "uc"); need("nonibd-kmers", "nonibd"); }
-    else if (tool == "kmers-per-sample") { need("k", "k"); need("k-mers", "i"); }
-    else if (tool == "unique-kmers-multi") { need("k", "k"); need("k-mers", "i"); if (!a.has("filter-kmers")) die("Mandatory argument --filter-kmers not set"); }
-    else if (tool == "kmers-multiple-filters") {
-        need("k", "k"); need("k-mers", "i"); need("cd-filter-kmers", "cd"); need("uc-filter-kmers", "uc"); need("nonibd-filter-kmers", "nonibd");
+    for (auto &n : t->needs) {
+        if (!n.name) break;
+        if (!a.has(n.name)) { if (n.sht) die("Mandatory argument --%s (-%s) not set", n.name, n.sht); else die("Mandatory argument --%s not set", n.name); }
     }
-    else if (tool == "kmers-color") { need("k", "k"); need("k-mers", "kf"); if (!a.has("class")) die("Mandatory argument --class not set"); }
-    else if (tool == "component-colored") { need("k", "k"); need("k-mers", "i"); }
-    else if (tool == "comp2seq") need("components-file", "cf");
-    else if (tool == "comp2graph") { need("k", "k"); need("components-file", "cf"); }
-    else if (tool == "seq2comp") { need("k", "k"); need("sequences", "i"); }
-    else if (tool == "component-paths") { need("k", "k"); need("components-file", "cf"); if (!a.has("seq")) die("Mandatory argument --seq not set"); }
-    props_write(inprop, tool_inputs(tool, a, wd, e.start_ts));
-
-    if (tool == "kmer-counter") {
-        outs = {PV::file("resulting-kmers-file", run_kmer_counter(e, a, a.list("reads"), k, a.geti("maximal-bad-frequence", 1), a.get("output-dir", wd + "/kmers"),
-                                                                  a.get("stats-dir", wd + "/stats")))};
-    } else if (tool == "kmer-counter-many") {
-        check_k(k);
-        outs = {PV::files("resulting-kmers-files", run_kmer_counter_many(e, a, a.list("reads"), k, a.geti("maximal-bad-frequence", 1), wd))};
-    } else if (tool == "seq-builder" || tool == "seq-builder-many") {
-        if (a.has("maximal-bad-frequency") && a.has("bottom-cut-percent") && tool == "seq-builder-many") die("-b and -bp can not be set both");
-        int b = a.geti("maximal-bad-frequency", 1), bp = a.has("bottom-cut-percent") ? a.geti("bottom-cut-percent", 0) : -1, l = a.geti("sequence-len", 100);
-        string out_dir = a.get("output-dir", wd + "/sequences");
-        if (tool == "seq-builder") outs = {PV::file("output-file", run_seq_builder(e, a, a.list("k-mers"), k, b, bp, l, wd, out_dir))};
-        else outs = {PV::files("output-files", run_seq_builder_many(e, a, a.list("k-mers"), k, b, bp, l, wd, out_dir))};
-    } else if (tool == "component-cutter") {
-        const int b1 = a.geti("min-component-size", 1000), b2 = a.geti("max-component-size", 10000);
-        string cf = run_component_cutter(e, a, a.list("sequences"), k, a.geti("min-seq-len", 100), b1, b2, wd, a.get("components-file", wd + "/components.bin"));
-        outs = {PV::file("components-file", cf), PV::file("components-stat", wd + "/components-stat-" + std::to_string(b1) + "-" + std::to_string(b2) + ".txt")};
-    } else if (tool == "features-calculator") {
-        outs = {PV::files("features-files", run_features(e, a, a.get("components-file"), a.list("reads"), a.list("kmers"), k, a.geti("threshold", 0), wd)),
-                PV::file("features-dir", wd + "/vectors")};
-    } else if (tool == "dist-matrix-calculator") {
-        run_dist_matrix(e, a, a.list("features"), a.get("matrix-file", wd + "/dist_matrix_$DT_original_order.txt"));
-    } else if (tool == "kmer-counter-posneg") {
-        // KmersCounterPositiveNegative.java:66-108: two kmer-counter-many steps with the work directories <workDir>/pos and /neg
-        vector<string> pos = a.list("positiveReads"), neg = a.list("negativeReads");
-        logmsg("INFO", "Found %zu samples in positive class and %zu samples in negative class to process", pos.size(), neg.size());
-        if (pos.empty() || neg.empty()) die("No libraries to process!!! Can't continue the calculations.");
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequency", 1);
-        vector<string> kp, kn;
-        for (int side = 0; side < 2; side++) {
-            const string d = wd + (side ? "/neg" : "/pos");
-            const vector<string> &files = side ? neg : pos;
-            vector<string> &res = side ? kn : kp;
-            run_as_step("kmer-counter-many", d, {PV("k", k), PV::files("reads", files), PV("maximal-bad-frequence", b), PV::file("output-dir", d + "/kmers"),
-                                                 PV::file("stats-dir", d + "/stats")},
-                        start, force,
-                        [&]() { Args sub = a; sub.opt["output-dir"] = {d + "/kmers"}; sub.opt["stats-dir"] = {d + "/stats"};
-                                res = run_kmer_counter_many(e, sub, files, k, b, d); return vector<PV>{PV::files("resulting-kmers-files", res)}; },
-                        [&](const Props &o) { res = props_list(o, "resulting-kmers-files"); });
-        }
-        outs = {PV::files("resulting-pos-kmers-files", kp), PV::files("resulting-neg-kmers-files", kn)};
-    } else if (tool == "kmers-filter") {
-        // KmersFilter.java:80-121: every input k-mers file is written again with the records whose k-mer is frequent enough
-        // in the filter files (IOUtils.filterAndPrintKmers, src/io/IOUtils.java:101-123)
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequence", 1), mt = a.geti("max-thresh", 0);
-        const string out_dir = a.get("output-dir", wd + "/kmers");
-        mkdirs(out_dir);
-        mf_ctx *ctx = ctx_of(e, a);
-        const vector<string> ff = a.list("filter-kmers");
-        auto fp = cptrs(ff);
-        mf_table *filter = nullptr;
-        check(mf_table_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &filter));
-        vector<string> written;
-        for (auto &f : a.list("k-mers")) {
-            mf_table *t = nullptr;
-            const char *one[1] = {f.c_str()};
-            check(mf_table_load_kmers(ctx, one, 1, b, k, &t));
-            string name = basename_of(f);
-            for (size_t q; (q = name.find(".kmers.bin")) != string::npos;) name.erase(q, 10);        // replaceAll(".kmers.bin", "")
-            const string out = out_dir + "/" + name + ".kmers.bin";
-            uint64_t c = 0, size = 0;
-            check(mf_table_write_kmers_filtered(t, b, filter, mt * (int)ff.size(), out.c_str(), &c));
-            check(mf_table_stats(t, &size, nullptr));
-            logmsg("INFO", "%s k-mers found, %s (%.1f%%) of them survived after filtering", group_digits(size).c_str(), group_digits(c).c_str(),
-                   size ? c * 100.0 / size : 0.0);
-            logmsg("INFO", "Filtered k-mers printed to %s", out.c_str());
-            mf_table_destroy(t);
-            written.push_back(out);
-        }
-        mf_table_destroy(filter);
-        outs = {written.empty() ? PV::null("resulting-kmers-file") : PV::file("resulting-kmers-file", written.back())};
-    } else if (tool == "kmers-samples-counter") {
-        // KmersSamplesCounter.java:69-140: the number of input files that hold each k-mer with a count > b
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequence", 1);
-        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
-        const vector<string> files = a.list("k-mers");
-        mkdirs(out_dir); mkdirs(st_dir);
-        if (!mf_kmers_samples_count) die("kmers-samples-counter: this build of the library has no mf_kmers_samples_count");
-        mf_ctx *ctx = ctx_of(e, a);
-        auto fp = cptrs(files);
-        const string out = out_dir + "/n_samples.kmers.bin", st = st_dir + "/n_samples.stat.txt";
-        uint64_t c = 0;
-        check(mf_kmers_samples_count(ctx, fp.data(), (int)fp.size(), b, k, out.c_str(), st.c_str(), &c));
-        logmsg("INFO", "%s k-mers found, %s (100.0%%) of them is good (not erroneous)", group_digits(c).c_str(), group_digits(c).c_str());
-        if (c == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
-        logmsg("INFO", "Good k-mers printed to %s", out.c_str());
-        outs = {PV::file("resulting-kmers-file", out)};
-    } else if (tool == "stats-kmers") {
-        // StatsKmersFinder.java:89-297 (no -k: the join works on the files' 64-bit keys)
-        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers");
-        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
-        const int b = a.geti("maximal-bad-frequence", 0);
-        const string out_dir = a.get("output-dir", wd + "/kmers");
-        mkdirs(out_dir);
-        if (!mf_stats_kmers) die("stats-kmers: this build of the library has no mf_stats_kmers");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("INFO", "Loading k-mers occurrences...");
-        auto pa = cptrs(af), pb = cptrs(bf);
-        uint64_t c[MF_STATS_COUNTERS] = {0};
-        check(mf_stats_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), b, pchi2, pmw, out_dir.c_str(), c));
-        logmsg("INFO", "Survived after chi-squared test k-mers printed to: %s", (out_dir + "/filtered_chisquared.kmers.bin").c_str());
-        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
-        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
-        logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
-        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
-        logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
-        logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7]));
-        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[8]);
-        logmsg("INFO", "Total group A k-mers = %llu", (unsigned long long)c[6]);
-        logmsg("INFO", "Total group B k-mers = %llu", (unsigned long long)c[7]);
-        logmsg("DEBUG", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
-        logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
-        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
-        outs = {PV::files("resulting-kmers-file", {out_dir + "/filtered_groupA.kmers.bin"})};
-    } else if (tool == "stats-kmers-3") {
-        // StatsKmers3GroupsFinder.java:92-343 (no -k, as stats-kmers).  What the library refuses is refused here first, in its words.
-        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers"), cf = a.list("c-kmers");
-        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
-        const int b = a.geti("maximal-bad-frequence", 0);
-        const string out_dir = a.get("output-dir", wd + "/kmers");
-        if (af.empty() || bf.empty() || cf.empty())
-            die("stats-kmers-3: every group needs at least one sample (|A| = %zu, |B| = %zu, |C| = %zu)", af.size(), bf.size(), cf.size());
-        if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
-        mkdirs(out_dir);
-        if (!mf_stats_kmers3) die("stats-kmers-3: this build of the library has no mf_stats_kmers3");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("INFO", "Loading k-mers occurrences...");
-        auto pa = cptrs(af), pb = cptrs(bf), pc = cptrs(cf);
-        uint64_t c[MF_STATS3_COUNTERS] = {0};
-        check(mf_stats_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), b, pchi2, pmw, out_dir.c_str(), c));
-        logmsg("INFO", "Survived after chi-squared test k-mers printed to: %s", (out_dir + "/filtered_chisquared.kmers.bin").c_str());
-        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
-        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
-        logmsg("INFO", "Group C k-mers printed to %s", (out_dir + "/filtered_groupC.kmers.bin").c_str());
-        logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
-        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
-        logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
-        logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7] + c[8]));
-        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[9]);
-        logmsg("INFO", "Total group A k-mers = %llu", (unsigned long long)c[6]);
-        logmsg("INFO", "Total group B k-mers = %llu", (unsigned long long)c[7]);
-        logmsg("INFO", "Total group C k-mers = %llu", (unsigned long long)c[8]);
-        logmsg("DEBUG", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
-        logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
-        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
-        outs = {PV::file("filtered-kmers-file", out_dir + "/filtered_chisquared.kmers.bin")};
-    } else if (tool == "specific-kmers") {
-        // SpecificKmersFinder.java:65-216 (no -k and no -b: every file is read at threshold 0).  What the library refuses is refused here
-        // first, in its words.
-        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers");
-        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
-        const string out_dir = a.get("output-dir", wd + "/kmers");
-        if (af.empty() || bf.empty()) die("specific-kmers: both groups need at least one sample (|A| = %zu, |B| = %zu)", af.size(), bf.size());
-        if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
-        mkdirs(out_dir);
-        if (!mf_specific_kmers) die("specific-kmers: this build of the library has no mf_specific_kmers");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("INFO", "Splitting k-mers...");
-        auto pa = cptrs(af), pb = cptrs(bf);
-        uint64_t c[MF_SPECIFIC_COUNTERS] = {0};
-        check(mf_specific_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pchi2, pmw, out_dir.c_str(), c));
-        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
-        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
-        logmsg("INFO", "Total specific k-mers in Group A = %llu", (unsigned long long)c[MF_SPECIFIC_GROUP_A]);
-        logmsg("INFO", "Total specific k-mers in Group B = %llu", (unsigned long long)c[MF_SPECIFIC_GROUP_B]);
-        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[MF_SPECIFIC_UNIQUE]);
-        logmsg("DEBUG", "Total scarce k-mers = = %llu", (unsigned long long)c[MF_SPECIFIC_SCARCE]);
-        logmsg("DEBUG", "Total skipped by chi-squared test = %llu", (unsigned long long)c[MF_SPECIFIC_SKIP_CHI2]);
-        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[MF_SPECIFIC_SKIP_MW]);
-        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[MF_SPECIFIC_UNIQUE_LEFT]);
-        logmsg("DEBUG", "Total kmers left = %llu", (unsigned long long)(c[MF_SPECIFIC_GROUP_A] + c[MF_SPECIFIC_GROUP_B]));
-        logmsg("DEBUG", "Processed %llu k-mers", (unsigned long long)c[MF_SPECIFIC_TOTAL]);
-    } else if (tool == "specific-kmers-3") {
-        // SpecificKmers3GroupsFinder.java:70-280
-        const vector<string> af = a.list("a-kmers"), bf = a.list("b-kmers"), cf = a.list("c-kmers");
-        const double pchi2 = a.getd("p-value-chi2", 0.05), pmw = a.getd("p-value-mw", 0.05);
-        const string out_dir = a.get("output-dir", wd + "/kmers");
-        if (af.empty() || bf.empty() || cf.empty())
-            die("specific-kmers-3: every group needs at least one sample (|A| = %zu, |B| = %zu, |C| = %zu)", af.size(), bf.size(), cf.size());
-        if (!(pchi2 >= 0.0 && pchi2 <= 1.0)) die("Error calculating chi-squared value! (p-value-chi2 = %g is not in [0, 1])", pchi2);
-        mkdirs(out_dir);
-        if (!mf_specific_kmers3) die("specific-kmers-3: this build of the library has no mf_specific_kmers3");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("INFO", "Splitting k-mers...");
-        auto pa = cptrs(af), pb = cptrs(bf), pc = cptrs(cf);
-        uint64_t c[MF_SPECIFIC3_COUNTERS] = {0};
-        check(mf_specific_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), pchi2, pmw, out_dir.c_str(), c));
-        logmsg("INFO", "Group A k-mers printed to %s", (out_dir + "/filtered_groupA.kmers.bin").c_str());
-        logmsg("INFO", "Group B k-mers printed to %s", (out_dir + "/filtered_groupB.kmers.bin").c_str());
-        logmsg("INFO", "Group C k-mers printed to %s", (out_dir + "/filtered_groupC.kmers.bin").c_str());
-        logmsg("DEBUG", "Total k-mers count = %llu", (unsigned long long)c[0]);
-        logmsg("DEBUG", "Total unique k-mers = %llu", (unsigned long long)c[3]);
-        logmsg("DEBUG", "Total k-mers present in all files = %llu", (unsigned long long)c[2]);
-        logmsg("DEBUG", "Total k-mers left = %llu", (unsigned long long)(c[6] + c[7] + c[8]));
-        logmsg("DEBUG", "Total unique left = %llu", (unsigned long long)c[9]);
-        logmsg("DEBUG", "Total group A k-mers = %llu", (unsigned long long)c[6]);
-        logmsg("DEBUG", "Total group B k-mers = %llu", (unsigned long long)c[7]);
-        logmsg("DEBUG", "Total group C k-mers = %llu", (unsigned long long)c[8]);
-        logmsg("INFO", "Total scarce k-mers = %llu", (unsigned long long)c[1]);
-        logmsg("DEBUG", "Total skipped by Chi-squared test = %llu", (unsigned long long)c[4]);
-        logmsg("DEBUG", "Total skipped by Mann-Whitney test = %llu", (unsigned long long)c[5]);
-    } else if (tool == "unique-kmers") {
-        // UniqueKmersFinder.java:73-144: the pooled k-mers of the input files that no filter file holds
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequence", 1);
-        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
-        const vector<string> files = a.list("k-mers"), filt = a.list("filter-kmers");
-        if (!mf_unique_kmers) die("unique-kmers: this build of the library has no mf_unique_kmers");
-        mf_ctx *ctx = ctx_of(e, a);
-        mkdirs(out_dir); mkdirs(st_dir);
-        auto fp = cptrs(files), ff = cptrs(filt);
-        const string out = out_dir + "/filtered.kmers.bin", st = st_dir + "/filtered.stat.txt";
-        uint64_t n = 0, c = 0;
-        logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
-        check(mf_unique_kmers(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, out.c_str(), st.c_str(), &n, &c));
-        char pct[64];
-        if (n) snprintf(pct, sizeof pct, "%.1f", c * 100.0 / n); else snprintf(pct, sizeof pct, "NaN");
-        logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n).c_str(),
-               group_digits(c).c_str(), pct);
-        if (n == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
-        else if (c == 0 || c < (uint64_t)(int64_t)(n * 0.03))
-            logmsg("WARN", "Too few good k-mers were found! Perhaps you should decrease k-mer size or --maximal-bad-frequency value");
-        const uint64_t all_kmers = (1ull << (2 * k)) / 2;                   // (4^k)/2
-        if (n == all_kmers) logmsg("WARN", "All possible k-mers were found in reads! Perhaps you should increase k-mer size");
-        else if (n >= (uint64_t)(int64_t)(all_kmers * 0.99)) logmsg("WARN", "Almost all possible k-mers were found in reads! Perhaps you should increase k-mer size");
-        logmsg("INFO", "Good k-mers printed to %s", out.c_str());
-        outs = {PV::file("resulting-kmers-file", out)};
-    } else if (tool == "kmers-grouped-counter") {
-        // KmersGroupedSamplesCounter.java:82-190: per k-mer of -kf the CD, UC and nonIBD files that hold it with a count > b
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequence", 1);
-        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
-        const vector<string> kf = a.list("kmers-file"), cd = a.list("cd-kmers"), uc = a.list("uc-kmers"), ni = a.list("nonibd-kmers");
-        mkdirs(out_dir); mkdirs(st_dir);
-        if (!mf_kmers_grouped_count) die("kmers-grouped-counter: this build of the library has no mf_kmers_grouped_count");
-        mf_ctx *ctx = ctx_of(e, a);
-        auto pkf = cptrs(kf), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni);
-        const string out = out_dir + "/kmers.groups.txt";
-        uint64_t c = 0;
-        logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
-        check(mf_kmers_grouped_count(ctx, pkf.data(), (int)pkf.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(), b, k,
-                                     out.c_str(), &c));
-        logmsg("INFO", "K-mers printed to %s", out.c_str());
-    } else if (tool == "kmers-per-sample") {
-        // KmersPerSampleCounter.java:56-157: the abundance in every file of the k-mers that enough files hold (no -b: every load is at 0).
-        // The first file is not counted, as in the reference (:82-96): count_first = 0.
-        check_k(k);
-        const int perc = a.geti("percent-present", 20);
-        const string out_dir = a.get("output-dir", wd + "/kmers_per_samples");
-        const vector<string> files = a.list("k-mers");
-        mkdirs(out_dir);
-        if (!mf_kmers_per_sample) die("kmers-per-sample: this build of the library has no mf_kmers_per_sample");
-        mf_ctx *ctx = ctx_of(e, a);
-        auto fp = cptrs(files);
-        const string out = out_dir + "/selected_kmers_" + std::to_string(perc) + ".txt";
-        uint64_t c = 0;
-        logmsg("INFO", "Loading all k-mers...");
-        logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
-        check(mf_kmers_per_sample(ctx, fp.data(), (int)fp.size(), k, perc, 0, out.c_str(), &c));
-        logmsg("DEBUG", "Selected k-mers = %s", group_digits(c).c_str());
-        logmsg("INFO", "K-mers printed to %s", out.c_str());
-    } else if (tool == "unique-kmers-multi") {
-        // UniqueKmersMultipleSamplesFinder.java:84-185: the k-mers that enough input files hold and no filter file does
-        check_k(k);
-        const int mn = a.geti("min-samples", 1), mx = a.geti("max-samples", 1), b = a.geti("maximal-bad-frequence", 1);
-        if (mn > mx) die("--min-samples parameter cannot be greater than --max-samples parameter.");
-        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
-        const vector<string> files = a.list("k-mers"), filt = a.list("filter-kmers");
-        if (!mf_unique_kmers_multi) die("unique-kmers-multi: this build of the library has no mf_unique_kmers_multi");
-        mf_ctx *ctx = ctx_of(e, a);
-        mkdirs(out_dir); mkdirs(st_dir);
-        auto fp = cptrs(files), ff = cptrs(filt);
-        const int64_t top = std::min<int64_t>(mx, std::max<int64_t>(mn, (int64_t)files.size() + 1));
-        vector<uint64_t> c((size_t)std::max<int64_t>(1, top - mn + 1), 0);
-        int n_out = 0; uint64_t n_union = 0;
-        check(mf_unique_kmers_multi(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, mn, mx, out_dir.c_str(), &n_out, &n_union, c.data()));
-        for (int q = 0; q < n_out; q++) {
-            const string out = out_dir + "/filtered_" + std::to_string(mn + q) + ".kmers.bin";
-            char pct[64];
-            if (n_union) snprintf(pct, sizeof pct, "%.1f", c[(size_t)q] * 100.0 / n_union); else snprintf(pct, sizeof pct, "NaN");
-            logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n_union).c_str(),
-                   group_digits(c[(size_t)q]).c_str(), pct);
-            if (c[(size_t)q] == 0) { logmsg("INFO", "No good k-mers found. Stop at maxSamples=%d", mn + q); break; }
-            logmsg("INFO", "Good k-mers printed to %s", out.c_str());
-        }
-        outs = {PV::files("resulting-kmers-file", {out_dir + "/filtered_" + std::to_string(mn) + ".kmers.bin"})};
-    } else if (tool == "kmers-multiple-filters") {
-        // KmersMultipleFilters.java:77-133: every input file against the CD, UC and nonIBD sets of n_samples files
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequence", 1);
-        const string out_dir = a.get("output-dir", wd + "/kmers"), st_dir = a.get("stats-dir", wd + "/stats");
-        const vector<string> files = a.list("k-mers"), cd = a.list("cd-filter-kmers"), uc = a.list("uc-filter-kmers"), ni = a.list("nonibd-filter-kmers");
-        if (!mf_kmers_multiple_filters) die("kmers-multiple-filters: this build of the library has no mf_kmers_multiple_filters");
-        mf_ctx *ctx = ctx_of(e, a);
-        mkdirs(out_dir); mkdirs(st_dir);
-        vector<string> ok, os;
-        for (auto &f : files) {
-            // file.getName().replaceAll(".kmers.bin", ""): a regular expression, every '.' matches any character but a line end
-            const string base = basename_of(f), pat = ".kmers.bin";
-            string name;
-            for (size_t q = 0; q < base.size();) {
-                bool m = q + pat.size() <= base.size();
-                for (size_t r = 0; m && r < pat.size(); r++) m = pat[r] == '.' ? (base[q + r] != '\n' && base[q + r] != '\r') : base[q + r] == pat[r];
-                if (m) q += pat.size(); else name.push_back(base[q++]);
-            }
-            ok.push_back(out_dir + "/" + name + ".kmers.bin"); os.push_back(st_dir + "/" + name + ".stat.txt");
-        }
-        auto fp = cptrs(files), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni), pok = cptrs(ok), pos = cptrs(os);
-        vector<uint64_t> fk(2 * files.size() + 2, 0);
-        check(mf_kmers_multiple_filters(ctx, fp.data(), (int)fp.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(),
-                                        b, k, pok.data(), pos.data(), fk.data()));
-        for (size_t j = 0; j < files.size(); j++) {
-            char pct[64];
-            if (fk[2 * j]) snprintf(pct, sizeof pct, "%.1f", fk[2 * j + 1] * 100.0 / fk[2 * j]); else snprintf(pct, sizeof pct, "NaN");
-            logmsg("INFO", "%s k-mers found, %s (%s%%) of them survived after filtering", group_digits(fk[2 * j]).c_str(), group_digits(fk[2 * j + 1]).c_str(), pct);
-            logmsg("INFO", "Filtered k-mers printed to %s", ok[j].c_str());
-        }
-    } else if (tool == "kmers-color") {
-        // ColorKmersMain.java:89-136: per k-mer and class 0 / 1 / 2 the number of samples that hold it (-val: their summed coverage)
-        check_k(k);
-        const int b = a.geti("maximal-bad-frequency", 1);
-        const bool val = a.get("val", "false") == "true";
-        const string out_dir = a.get("output-dir", wd + "/colored-kmers"), cls = a.get("class");
-        const vector<string> files = a.list("k-mers");
-        logmsg("INFO", "Loading class file...");
-        // readFileToColor :70-82: tab-separated lines, name (the file name without .kmers.bin) and class
-        std::map<string, int> color;
-        {
-            FILE *f = fopen(cls.c_str(), "r");
-            if (!f) die("Cannot read file: %s", cls.c_str());
-            char line[8192]; int ln = 0;
-            while (fgets(line, sizeof line, f)) {
-                ln++;
-                string l(line);
-                while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
-                const size_t t1 = l.find('\t');
-                if (t1 == string::npos) { fclose(f); die("class file %s, line %d: no tab-separated class after '%s'", cls.c_str(), ln, l.c_str()); }
-                const size_t t2 = l.find('\t', t1 + 1);
-                const string name = l.substr(0, t1), cv = l.substr(t1 + 1, t2 == string::npos ? string::npos : t2 - t1 - 1);
-                char *end; const long c = strtol(cv.c_str(), &end, 10);
-                if (cv.empty() || *end) { fclose(f); die("class file %s, line %d: can't parse class '%s' of sample '%s'", cls.c_str(), ln, cv.c_str(), name.c_str()); }
-                if (c < 0 || c > 2) { fclose(f); die("class file %s, line %d: sample '%s' has class %ld (the classes are 0, 1 and 2)", cls.c_str(), ln, name.c_str(), c); }
-                color[name] = (int)c;
-            }
-            fclose(f);
-        }
-        vector<int> classes;
-        for (auto &fn : files) {
-            const string name = remove_ext(basename_of(fn), {".kmers.bin"});
-            auto it = color.find(name);
-            if (it == color.end()) die("class file %s has no line for sample '%s' (%s)", cls.c_str(), name.c_str(), fn.c_str());
-            classes.push_back(it->second);
-        }
-        if (files.size() > 1024) die("kmers-color: %zu k-mers files, at most 1024 (a field of the packed value holds 20 bits)", files.size());
-        mkdirs(out_dir);
-        if (!mf_kmers_color) die("kmers-color: this build of the library has no mf_kmers_color");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("INFO", "Loading kmers files...");
-        auto fp = cptrs(files);
-        const string out = out_dir + "/colored_kmers.kmers.bin", st = out_dir + "/colored_kmers.stat.txt";
-        uint64_t c = 0;
-        check(mf_kmers_color(ctx, fp.data(), classes.data(), (int)fp.size(), b, val ? 1 : 0, k, out.c_str(), st.c_str(), &c));
-        logmsg("INFO", "%s colored k-mers printed to %s", group_digits(c).c_str(), out.c_str());
-        outs = {PV::file("resulting-kmers-file", out)};
-    } else if (tool == "component-colored") {
-        // ColoredComponentMain.java:83-119, default and --separate modes of ColoredComponentsBuilder
-        check_k(k);
-        const int groups = a.geti("n_groups", 3), ncomps = a.geti("n_comps", -1);
-        const bool separate = a.get("separate", "false") == "true";
-        const double perc = a.getd("perc", 0.9);
-        if (a.get("linear", "false") == "true")
-            die("component-colored: --linear is not supported: its result depends on the iteration order of the reference's hash map");
-        if (ncomps != -1)
-            die("component-colored: --n_comps %d is not supported (only -1, all components): which components are selected depends on the iteration order of the reference's hash map", ncomps);
-        if (groups < 1) die("component-colored: --n_groups %d: at least 1", groups);
-        const string out_dir = a.get("output-dir", wd + "/colored-components"), stat = wd + "/components-stat.txt";
-        const vector<string> files = a.list("k-mers");
-        mkdirs(out_dir);
-        if (!mf_colored_components) die("component-colored: this build of the library has no mf_colored_components");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("DEBUG", "Loading colored k-mers...");
-        logmsg("INFO", "Searching for colored components...");
-        auto fp = cptrs(files);
-        vector<uint64_t> cnt((size_t)groups, 0);
-        // (IOUtils.loadLongKmers(files, k, ...): the reference passes k where the loader takes its value threshold)
-        check(mf_colored_components(ctx, fp.data(), (int)fp.size(), k, (int64_t)k, groups, separate ? 1 : 0, perc, out_dir.c_str(), stat.c_str(), cnt.data()));
-        uint64_t total = 0;
-        vector<string> written;
-        for (int c = 0; c < groups; c++) {
-            total += cnt[(size_t)c];
-            logmsg("INFO", "%s components were found for class %d", group_digits(cnt[(size_t)c]).c_str(), c);
-            written.push_back(out_dir + "/components_color_" + std::to_string(c) + ".bin");
-        }
-        logmsg("INFO", "Total %s components were found", group_digits(total).c_str());
-        outs = {PV::files("components-files", written)};
-    } else if (tool == "comp2seq") {
-        // ComponentsToSequences.java:41-76: bin2fasta, kmer-counter-many -b 0, seq-builder-many -b 0 -l k as sub-steps with the work
-        // directories kmers_fasta, kmer-counter-many and seq-builder-many -- here one segmented build of all components (mf_comp2seq)
-        check_k(k);
-        const bool split = a.get("split", "false") == "true";
-        const string cf = a.get("components-file");
-        if (!mf_comp2seq) die("comp2seq: this build of the library has no mf_comp2seq");
-        mf_ctx *ctx = ctx_of(e, a);
-        uint64_t nf = 0, ns = 0;
-        check(mf_comp2seq(ctx, cf.c_str(), k, split ? 1 : 0, wd.c_str(), &nf, &ns));
-        if (split) logmsg("INFO", "%s components loaded from %s", group_digits(nf).c_str(), cf.c_str());
-        logmsg("INFO", "%s sequences found", group_digits(ns).c_str());
-        if (ns == 0) logmsg("WARN", "No sequences were found! Perhaps you should decrease --min-seq-len or --maximal-bad-frequency values");
-        logmsg("INFO", "Sequences printed to %s", (wd + "/seq-builder-many/sequences").c_str());
-        vector<string> written;
-        for (uint64_t i = 0; i < nf; i++) written.push_back(wd + "/seq-builder-many/sequences/component" + (split ? "_" + std::to_string(i + 1) : string()) + ".seq.fasta");
-        outs = {PV::files("output-files", written)};
-    } else if (tool == "comp2graph") {
-        // ComponentsToGraph.java:70-130: one Comp2Graph per component on a thread pool, a HashMap of strings and a quadratic merge loop
-        // each -- here the graphs of all components in one pass, the text formatted on the device (mf_comp2graph)
-        check_k(k);
-        const string cf = a.get("components-file"), gf = a.get("graph-file", wd + "/components-graph.gfa");
-        const vector<string> files = a.list("k-mers");
-        const bool cov = a.get("coverage", "false") == "true";                // (without -i: accepted and ignored, as in the reference)
-        if (!mf_comp2graph) die("comp2graph: this build of the library has no mf_comp2graph");
-        mf_ctx *ctx = ctx_of(e, a);
-        auto fp = cptrs(files);
-        uint64_t nc = 0, ns = 0, nl = 0;
-        check(mf_comp2graph(ctx, cf.c_str(), k, files.empty() ? nullptr : fp.data(), (int)files.size(), cov ? 1 : 0, gf.c_str(), &nc, &ns, &nl));
-        logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
-        logmsg("INFO", "Graph components saved to GFA format!");
-        outs = {PV::file("graph-file", gf)};
-    } else if (tool == "seq2comp") {
-        // SequencesToComponents.java:61-103: a component per sequence that survives the readers, its members the distinct canonical k-mers
-        // (a LongArraySet with a linear scan per add there: quadratic in the sequence's length) -- here a segmented set-build on the
-        // device (mf_seq2comp).  Components in file order, then record order (the reference: as its thread pool finishes); a sequence
-        // shorter than k keeps its place as an empty component
-        check_k(k);
-        const vector<string> files = a.list("sequences");
-        const string cf = a.get("components-file", wd + "/components.bin"), sf = wd + "/components-stat.txt";
-        for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
-        if (!mf_seq2comp) die("seq2comp: this build of the library has no mf_seq2comp");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("DEBUG", "Loading sequences from files...");
-        auto fp = cptrs(files);
-        vector<uint64_t> per(files.size() + 1, 0);
-        uint64_t nc = 0;
-        { const size_t q = cf.find_last_of('/'); if (q != string::npos && q > 0) mkdirs(cf.substr(0, q)); }
-        check(mf_seq2comp(ctx, files.empty() ? nullptr : fp.data(), (int)files.size(), k, cf.c_str(), sf.c_str(), &nc, per.data()));
-        for (size_t i = 0; i < files.size(); i++) {          // (the reference logs each pair as it goes; the numbers are the same)
-            logmsg("INFO", "Loading file %s...", basename_of(files[i]).c_str());
-            logmsg("INFO", "%llu components added", (unsigned long long)per[i]);
-        }
-        logmsg("INFO", "Total %s components were found", group_digits(nc).c_str());
-        logmsg("INFO", "Components saved to %s", cf.c_str());
-        describe(sf, "File with components' statistics (in text format)");
-        describe(cf, "File with components made from the input sequences, one per sequence (in binary format)");
-        outs = {PV::file("components-file", cf), PV::file("components-stat", sf)};
-    } else if (tool == "component-paths") {
-        // ComponentPathsMain.java:82-190: for every sequence one hash set per selected component is probed, O(components x bases) -- here
-        // one lookup per k-mer position in an index over the members of all selected components, the runs found, paired, capped, sorted
-        // and printed on the device (mf_comppaths.hip).  Without a selection the reference logs its message and ends cleanly; here the
-        // run fails with it.  A number out of range is an exception there and an error here.
-        check_k(k);
-        const string cf = a.get("components-file"), od = a.get("output-dir", wd + "/paths");
-        const vector<string> files = a.list("seq");
-        const bool all = a.get("all-components", "false") == "true";
-        const int min_len = a.geti("min-length", 50);
-        vector<uint32_t> sel;
-        for (auto &v : a.list("components")) {
-            char *end = nullptr; const long long no = strtoll(v.c_str(), &end, 10);
-            if (v.empty() || *end) die("Can't parse integer value '%s' of option --components", v.c_str());
-            if (no < 1 || no > 0xFFFFFFFFll) die("There is no component %s (components are numbered from 1)", v.c_str());
-            sel.push_back((uint32_t)no);
-        }
-        if (!all && sel.empty()) die("No components to process!!! Do you forget to set --all-components or --components n1,n2,...?");
-        if (!exists(cf)) die("Can't load components: file not found (%s)", cf.c_str());
-        for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
-        if (!mf_paths_create || !mf_paths_add || !mf_paths_finish || !mf_paths_destroy || !mf_paths_slots || !mf_paths_write || !mf_paths_stats || !mf_comps_load ||
-            !mf_comps_set_k || !mf_comps_stats || !mf_comps_destroy || !mf_reads_load || !mf_reads_stats || !mf_reads_device_view || !mf_reads_destroy)
-            die("component-paths: this build of the library has no mf_paths_create");
-        mf_ctx *ctx = ctx_of(e, a);
-        logmsg("DEBUG", "Loading components...");
-        mf_comps *c = nullptr;
-        check(mf_comps_load(ctx, cf.c_str(), &c));
-        check(mf_comps_set_k(c, k));
-        uint64_t nc = 0;
-        check(mf_comps_stats(c, &nc, nullptr));
-        logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
-        if (all && nc == 0) die("No components to process!!!");
-        logmsg("DEBUG", "Preparing...");
-        mf_paths *paths = nullptr;
-        const uint64_t max_paths = 1000000;                                   // MAX_PATHS_COUNT (:30)
-        check(mf_paths_create(ctx, c, all ? nullptr : sel.data(), all ? 0 : sel.size(), min_len, max_paths, &paths));
-        logmsg("DEBUG", "Loading sequences and extracting paths...");
-        for (auto &f : files) {                                               // one file resident at a time
-            logmsg("INFO", "Loading file %s...", basename_of(f).c_str());
-            const char *fp = f.c_str();
-            mf_reads *r = nullptr;
-            check(mf_reads_load(ctx, &fp, 1, &r));
-            const void *db = nullptr, *doff = nullptr; uint64_t nr = 0, nb = 0;
-            check(mf_reads_stats(r, &nr, &nb));
-            check(mf_reads_device_view(r, &db, &doff));
-            check(mf_paths_add(paths, db, doff, nr, nb));
-            mf_reads_destroy(r);
-        }
-        check(mf_paths_finish(paths));
-        uint64_t nslots = 0;
-        check(mf_paths_stats(paths, &nslots, nullptr, nullptr, nullptr));
-        vector<uint32_t> no(nslots + 1, 0); vector<uint8_t> reached(nslots + 1, 0);
-        check(mf_paths_slots(paths, no.data(), nullptr, nullptr, reached.data()));
-        for (uint64_t i = 0; i < nslots; i++)
-            if (reached[i]) logmsg("WARN", "Too many paths in component %u, keeping only first %llu of them!", no[i], (unsigned long long)max_paths);
-        logmsg("INFO", "Sorting...");
-        logmsg("INFO", "Saving to files...");
-        { const size_t q = od.find_last_of('/'); if (q != string::npos && q > 0) mkdirs(od.substr(0, q)); }
-        uint64_t np = 0;
-        check(mf_paths_write(paths, od.c_str(), &np));
-        mf_paths_destroy(paths);
-        mf_comps_destroy(c);
-        logmsg("INFO", "Paths for %llu component(s) were saved in directory %s", (unsigned long long)nslots, od.c_str());
-        outs = {};
-    } else if (tool == "view") {
-        run_view(a, k);
-    } else if (tool == "bin2fasta") {
-        run_bin2fasta(a, k);
-    } else if (tool == "heatmap-maker") {
-        string nm = run_heatmap_maker(e, a, a.get("matrix-file"), a.get("newMatrix-file"));
-        outs = {PV::null("heatmap-file"), a.get("without-renumbering", "false") == "true" ? PV::null("newMatrix-file-out") : PV::file("newMatrix-file-out", nm)};
-    } else if (tool == "matrix-builder") {
-        // DistanceMatrixBuilderMain.java:88-175: steps kmer-counter-many, seq-builder-many, component-cutter, features-calculator,
-        // dist-matrix-calculator, heatmap-maker (its image is not rendered here)
-        vector<string> reads = a.list("reads");
-        logmsg("INFO", "Found %zu libraries to process", reads.size());
-        if (reads.empty()) die("No libraries to process!!! Can't continue the calculations.");
-        const bool use_reads = a.get("use-reads-for-calculating-features", "false") == "true";     // DistanceMatrixBuilderMain.java:162-165
-        check_k(k);
-        int b = a.geti("maximal-bad-frequency", a.geti("maximal-bad-frequence", 1)), l = a.geti("min-seq-len", 100);
-        int b1 = a.geti("min-component-size", 1000), b2 = a.geti("max-component-size", 10000);
-        static const char *STEPS[] = {"kmer-counter-many", "seq-builder-many", "component-cutter", "features-calculator", "dist-matrix-calculator", "heatmap-maker"};
-        for (const string *bound : {&start, &finish})                           // Tool.checkBoundExistence :726-741
-            if (!bound->empty() && std::find_if(std::begin(STEPS), std::end(STEPS), [&](const char *n) { return *bound == n; }) == std::end(STEPS))
-                die("There is no substep with name '%s' in step matrix-builder!", bound->c_str());
-        {   // createOutputDescFiles :178-200
-            g_desc_files = {"output_description.txt", wd + "/output_description.txt"};
-            time_t t = time(nullptr); struct tm tmv; localtime_r(&t, &tmv);
-            char hdr[128]; strftime(hdr, sizeof hdr, "%d-%b-%Y (%a) %H:%M:%S", &tmv);
-            for (auto &d : g_desc_files) {
-                FILE *f = fopen(d.c_str(), "w");
-                if (!f) { logmsg("WARN", "Can't create file %s, skipping", d.c_str()); continue; }
-                fprintf(f, "# Output files' description for run started at %s\n\n%s\n%s\n   Identical files with run log\n\n%s\n%s\n   Identical files with output files' description\n",
-                        hdr, (wd + "/log").c_str(), (wd + "/logs/log_" + e.start_ts).c_str(), g_desc_files[0].c_str(), g_desc_files[1].c_str());
-                fclose(f);
-            }
-        }
-        const string d1 = wd + "/kmer-counter-many", d2 = wd + "/seq-builder-many", d3 = wd + "/component-cutter", d4 = wd + "/features-calculator",
-                     d5 = wd + "/dist-matrix-calculator", d6 = wd + "/heatmap-maker";
-        const string dirs[] = {d1, d2, d3, d4, d5, d6};
-        // --finish <step>: stop after it; the next step's results are outdated then (:512-527)
-        auto finished = [&](int i) {
-            if (finish.empty() || finish != STEPS[i]) return false;
-            if (i + 1 < 6) { unlink((dirs[i + 1] + "/SUCCESS").c_str()); unlink((dirs[i + 1] + "/in.properties").c_str()); }
-            return true;
-        };
-        auto done = [&]() { for (mf_ctx *c : e.ctxs) if (c) mf_ctx_destroy(c); return 0; };
-        vector<string> kmers, seqs, vecs;
-        // 1 kmer-counter-many
-        const string stats_dir = a.get("stats-dir", d1 + "/stats");
-        run_as_step(STEPS[0], d1, {PV("k", k), PV::files("reads", reads), PV("maximal-bad-frequence", b), PV::file("output-dir", d1 + "/kmers"), PV::file("stats-dir", stats_dir)},
-                    start, force,
-                    [&]() { Args sub = a; sub.opt.erase("output-dir"); sub.opt["stats-dir"] = {stats_dir};
-                            kmers = run_kmer_counter_many(e, sub, reads, k, b, d1); return vector<PV>{PV::files("resulting-kmers-files", kmers)}; },
-                    [&](const Props &o) { kmers = props_list(o, "resulting-kmers-files"); });
-        describe(stats_dir, "Directory with kmer frequency statistics (statistics files is in text format for every input reads file)");
-        if (finished(0)) return done();
-        // 2 seq-builder-many
-        const int bp = a.has("bottom-cut-percent") ? a.geti("bottom-cut-percent", 0) : -1;
-        run_as_step(STEPS[1], d2, {PV("k", k), PV::files("k-mers", kmers), PV("maximal-bad-frequency", b), bp >= 0 ? PV("bottom-cut-percent", bp) : PV::null("bottom-cut-percent"),
-                                   PV("sequence-len", l), PV::file("output-dir", d2 + "/sequences")},
-                    start, force,
-                    [&]() { seqs = run_seq_builder_many(e, a, kmers, k, b, bp, l, d2, d2 + "/sequences");
-                            return vector<PV>{PV::files("output-files", seqs)}; },
-                    [&](const Props &o) { seqs = props_list(o, "output-files"); });
-        describe(d2 + "/sequences", "Directory with FASTA files - paths from reads for every library");
-        if (finished(1)) return done();
-        // 3 component-cutter
-        const string comp = d3 + "/components.bin", cstat = d3 + "/components-stat-" + std::to_string(b1) + "-" + std::to_string(b2) + ".txt";
-        run_as_step(STEPS[2], d3, {PV("k", k), PV("min-seq-len", l), PV("min-component-size", b1), PV("max-component-size", b2), PV::files("sequences", seqs), PV::file("components-file", comp)},
-                    start, force,
-                    [&]() { run_component_cutter(e, a, seqs, k, l, b1, b2, d3, comp); return vector<PV>{PV::file("components-file", comp), PV::file("components-stat", cstat)}; },
-                    [&](const Props &) {});
-        describe(cstat, "File with components' statistics (in text format)");
-        describe(comp, "File with extracted components (in binary format)");
-        if (finished(2)) return done();
-        // 4 features-calculator
-        const vector<string> none;
-        run_as_step(STEPS[3], d4, {PV("k", k), PV::file("components-file", comp), PV::files("reads", use_reads ? reads : none), PV::files("kmers", use_reads ? none : kmers),
-                                   a.has("selected") ? PV::files("selected", a.list("selected")) : PV::null("selected"), PV("threshold", 0)},
-                    start, force,
-                    [&]() { vecs = use_reads ? run_features(e, a, comp, reads, {}, k, 0, d4) : run_features(e, a, comp, {}, kmers, k, 0, d4);
-                            return vector<PV>{PV::files("features-files", vecs), PV::file("features-dir", d4 + "/vectors")}; },
-                    [&](const Props &o) { vecs = props_list(o, "features-files"); });
-        describe(d4 + "/vectors", "Directory with features values files for every library (in text format)");
-        if (finished(3)) return done();
-        // 5 dist-matrix-calculator: the matrix in the original order goes to <workDir>/matrices (:132-134)
-        string mpath = wd + "/matrices/dist_matrix_" + e.start_ts + "_original_order.txt";
-        const bool wn = a.get("without-names", "false") == "true";
-        const string fmt = a.get("output-format", "%.4f");
-        run_as_step(STEPS[4], d5, {PV::files("features", vecs), PV::flag("without-names", wn), PV::file("matrix-file", mpath), PV("output-format", fmt)},
-                    start, force,
-                    [&]() { mkdirs(wd + "/matrices"); mpath = run_dist_matrix(e, a, vecs, mpath); return vector<PV>(); },
-                    [&](const Props &) {});
-        describe(mpath, "File with resulted distance matrix between samples keeping original order");
-        if (finished(4)) return done();
-        // 6 heatmap-maker, numeric half: dendrogram order + renumbered matrix (:137-145)
-        string npath = a.get("matrix-file", wd + "/matrices/dist_matrix_$DT.txt");
-        { size_t q = npath.find("$DT"); if (q != string::npos) npath.replace(q, 3, e.start_ts); }
-        const bool wr = a.get("without-renumbering", "false") == "true";
-        run_as_step(STEPS[5], d6, {PV::file("matrix-file", mpath), a.has("colors-file") ? PV::file("colors-file", a.get("colors-file")) : PV::null("colors-file"),
-                                   PV::flag("without-renumbering", wr), PV::file("newMatrix-file", npath),
-                                   PV::file("heatmap-file", tool_inputs(tool, a, wd, e.start_ts)[6].vals[0]), PV::flag("invert-colors", a.get("invert-colors", "false") == "true"),
-                                   PV("output-format", fmt)},
-                    start, force,
-                    [&]() { run_heatmap_maker(e, a, mpath, npath); return vector<PV>{PV::null("heatmap-file"), wr ? PV::null("newMatrix-file-out") : PV::file("newMatrix-file-out", npath)}; },
-                    [&](const Props &) {});
-        if (!wr) describe(npath, "File with resulted distance matrix between samples with new order based on adjacency of the samples");
-        logmsg("INFO", "heatmap image (dist_matrix_<date>_heatmap.png) is not rendered by the HIP path");
-        if (finished(5)) return done();
-    }
+    props_write(inprop, tool_inputs(*t, a, wd, e.start_ts));
+    const vector<PV> outs = t->run(r);
     const double t_work = since_start();
     for (mf_ctx *c : e.ctxs) if (c) mf_ctx_synchronize(c);
-    if (finish.empty()) {                               // (a run cut short by --finish leaves no SUCCESS, :377-379)
+    if (r.finish.empty()) {                             // (a run cut short by --finish leaves no SUCCESS, :377-379)
         props_write(wd + "/out.properties", outs);
         touch(wd + "/SUCCESS");
     }

@@ -1,8 +1,10 @@
 """comp2seq: the Python restatement (tests/comp2seq_ref.py) pinned on hand-worked cases, and the new entry points' declarations."""
 import os
 import struct
+import subprocess
 
 import numpy as np
+import pytest
 
 import comp2seq_ref as R
 
@@ -16,8 +18,16 @@ def test_the_entry_points_are_declared():
         assert f" {name}(" in header, name
         assert name in L.exported_symbols(), name
     assert callable(L.Context.comps_unitigs) and callable(L.Context.comp2seq) and callable(L.Seqs.components)
-    main = open(os.path.join(ROOT, "metafast_amd", "cli", "metafast_main.cpp")).read()
-    assert '"comp2seq\\t' in main and '"kmers-grouped-counter", "comp2seq"}' in main
+
+
+def test_the_driver_lists_and_knows_the_tool(tmp_path):
+    # the stub build of the driver (no GPU): the tool's line is in the -ts listing, and -t comp2seq is a known tool
+    import test_driver_tools_cpu as D
+    cli = D.stub_driver()
+    r = subprocess.run([cli, "-ts"], capture_output=True, text=True, env=D.ENV, cwd=str(tmp_path))
+    assert r.returncode == 0 and "\ncomp2seq\t\tTransforms components in binary format to FASTA sequences (contigs)\n" in r.stdout, r.stdout
+    r = subprocess.run([cli, "-t", "comp2seq", "-w", str(tmp_path / "w")], capture_output=True, text=True, env=D.ENV, cwd=str(tmp_path))
+    assert r.returncode == 1 and "not found" not in r.stderr and r.stderr == "ERROR: Mandatory argument --components-file (-cf) not set\n", r.stderr
 
 
 def test_encoding_and_canonical_form():
