@@ -57,6 +57,34 @@ template <int K> struct skm_word {
     uint32_t cut;         // positions where a run starts
 };
 
+// run starts from the 32 minimizer hashes.  bit j of `same`: the k-mer at j has the minimizer of the one before it.  Built from the top
+// with compare + add-with-carry (two instructions per position instead of compare, select, or)
+template <int K>
+__device__ __forceinline__ void skm_cut_mask(skm_word<K> &S, uint32_t m) {
+    uint32_t acc = 0;
+#pragma unroll
+    for (int j = 31; j >= 1; j--)
+        asm("v_cmp_eq_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(S.mh[j]), "v"(S.mh[j - 1]) : "vcc");
+    const uint32_t same = acc << 1;
+    S.cut = m & ~(same & (m << 1));
+}
+
+// The reverse complement of 16 bases (first base in the top bits): the last base's complement comes first.  An M-mer's reverse
+// complement is then cut out of the reversed words exactly as the M-mer is cut out of the forward ones (funnel shift + shift: two
+// instructions) instead of being rolled base by base (shift, and, subtract, shift-or: four) -- with R[3 - q] = skm_rc16(D[q]) the M-mer
+// that starts at base i of the 64 has its reverse complement at base 64 - M - i of R[0..3].
+__device__ __forceinline__ uint32_t skm_rc16(uint32_t d) {
+    const uint32_t r = __brev(~d);
+    return ((r & 0xAAAAAAAAu) >> 1) | ((r & 0x55555555u) << 1);
+}
+// M bases from base p (0 <= p <= 64 - M) of the 64 in X[0..3], right-aligned
+template <int M>
+__device__ __forceinline__ uint32_t skm_mmer_at(const uint32_t (&X)[4], int p) {
+    const int q = p >> 4, o = p & 15;
+    const uint32_t top = o ? __builtin_amdgcn_alignbit(X[q], q + 1 < 4 ? X[q + 1] : 0u, 32 - 2 * o) : X[q];
+    return top >> (32 - 2 * M);
+}
+
 // the second half of the scan: minimizer hash of each of the word's 32 k-mers from its M-mers' hashes, run starts
 template <int K>
 __device__ __forceinline__ void skm_scan_tail(skm_word<K> &S, uint32_t (&hs)[skm_word<K>::NM], uint32_t m) {
@@ -77,14 +105,7 @@ __device__ __forceinline__ void skm_scan_tail(skm_word<K> &S, uint32_t (&hs)[skm
 #pragma unroll
         for (int j = 0; j < 32; j++) S.mh[j] = min3(hs[j], hs[j + D], hs[j + W - 3]);
     }
-    // bit j: the k-mer at j has the minimizer of the one before it.  Built from the top with compare + add-with-carry (two
-    // instructions per position instead of compare, select, or)
-    uint32_t acc = 0;
-#pragma unroll
-    for (int j = 31; j >= 1; j--)
-        asm("v_cmp_eq_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(S.mh[j]), "v"(S.mh[j - 1]) : "vcc");
-    const uint32_t same = acc << 1;
-    S.cut = m & ~(same & (m << 1));
+    skm_cut_mask<K>(S, m);
 }
 
 template <int K>
@@ -99,13 +120,10 @@ __device__ __forceinline__ void skm_scan_word(skm_word<K> &S, const uint8_t *__r
     S.D[0] = b0 < n_bases ? mf_dec16(c0) : 0u; S.D[1] = in1 ? mf_dec16(c1) : 0u; S.D[2] = in2 ? mf_dec16(c2) : 0u; S.D[3] = in3 ? mf_dec16(c3) : 0u;
     S.valid = m;
     uint32_t hs[NM];
-    uint32_t r = 0;
+    const uint32_t R[4] = {skm_rc16(S.D[3]), skm_rc16(S.D[2]), skm_rc16(S.D[1]), skm_rc16(S.D[0])};
 #pragma unroll
-    for (int i = 0; i < NM; i++) {
-        const int q = i >> 4, o = i & 15;       // bases i .. i+M-1 start in dword q at base offset o
-        const uint32_t top = o ? __builtin_amdgcn_alignbit(S.D[q], S.D[q + 1 < 4 ? q + 1 : 3], 32 - 2 * o) : S.D[q];
-        const uint32_t f = top >> (32 - 2 * M);
-        r = (i == 0) ? mf_mmer_rc(f, M) : ((r >> 2) | ((3u - (f & 3u)) << (2 * M - 2)));
+    for (int i = 0; i < NM; i++) {             // (the last M-mer ends at base NM + M - 2 = K + 29 < 64)
+        const uint32_t f = skm_mmer_at<M>(S.D, i), r = skm_mmer_at<M>(R, 64 - M - i);
         hs[i] = mf_mmer_hash(f < r ? f : r, M);
     }
     skm_scan_tail<K>(S, hs, m);
@@ -131,19 +149,46 @@ __device__ __forceinline__ void skm_scan_word_halo(skm_word<K> &S, const uint8_t
     S.D[0] = b0 < n_bases ? mf_dec16(c0) : 0u; S.D[1] = in1 ? mf_dec16(c1) : 0u;
     S.D[2] = skm_from_next_lane(S.D[0]); S.D[3] = skm_from_next_lane(S.D[1]);
     S.valid = m;
-    uint32_t hs[NM];
-    uint32_t r = 0;
+    // the lane's own 32 M-mers end by base 31 + M - 1 < 48: their reverse complements lie in R[1..3], and R[1] = rc(D[2]) is the next
+    // lane's rc(D[0]); R[0] is not read
+    static_assert(64 - M - 31 >= 16, "reversed words");
+    const uint32_t R3 = skm_rc16(S.D[0]);
+    const uint32_t R[4] = {0u, skm_from_next_lane(R3), skm_rc16(S.D[1]), R3};
+    uint32_t hs[34];
 #pragma unroll
     for (int i = 0; i < 32; i++) {
-        const int q = i >> 4, o = i & 15;       // bases i .. i+M-1 start in dword q at base offset o
-        const uint32_t top = o ? __builtin_amdgcn_alignbit(S.D[q], S.D[q + 1], 32 - 2 * o) : S.D[q];
-        const uint32_t f = top >> (32 - 2 * M);
-        r = (i == 0) ? mf_mmer_rc(f, M) : ((r >> 2) | ((3u - (f & 3u)) << (2 * M - 2)));
+        const uint32_t f = skm_mmer_at<M>(S.D, i), r = skm_mmer_at<M>(R, 64 - M - i);
         hs[i] = mf_mmer_hash(f < r ? f : r, M);
     }
+    // The sliding minimum of skm_scan_tail with the halo taken as late as possible: a minimum over M-mers 32 .. of this word is the
+    // next lane's minimum over its M-mers 0 .., so the next lane's partial minima are moved instead of its hashes (W = 17: 2 + 6 + 8
+    // moves and 3 x 32 minima instead of 16 moves and 118 minima).  Every value moved depends on the next lane's OWN hashes only.
+    constexpr int W = skm_word<K>::W;
+    static_assert(W >= 3 && W <= 18, "window");
+    static_assert(NM <= 64, "halo");
+    auto min3 = [](uint32_t a, uint32_t b, uint32_t c) { const uint32_t m = a < b ? a : b; return m < c ? m : c; };
+    hs[32] = skm_from_next_lane(hs[0]); hs[33] = skm_from_next_lane(hs[1]);
+    uint32_t a[38];
 #pragma unroll
-    for (int i = 32; i < NM; i++) hs[i] = skm_from_next_lane(hs[i - 32]);
-    skm_scan_tail<K>(S, hs, m);
+    for (int i = 0; i < 32; i++) a[i] = min3(hs[i], hs[i + 1], hs[i + 2]);                     // M-mers i .. i+2
+    if (W >= 9) {
+        uint32_t b[32 + 9];
+#pragma unroll
+        for (int i = 32; i < 38; i++) a[i] = skm_from_next_lane(a[i - 32]);
+#pragma unroll
+        for (int i = 0; i < 32; i++) b[i] = min3(a[i], a[i + 3], a[i + 6]);                    // i .. i+8
+#pragma unroll
+        for (int i = 32; i < 32 + W - 9; i++) b[i] = skm_from_next_lane(b[i - 32]);
+#pragma unroll
+        for (int j = 0; j < 32; j++) S.mh[j] = b[j] < b[j + W - 9] ? b[j] : b[j + W - 9];
+    } else {
+        constexpr int D = W - 3 < 3 ? W - 3 : 3;
+#pragma unroll
+        for (int i = 32; i < 32 + W - 3; i++) a[i] = skm_from_next_lane(a[i - 32]);
+#pragma unroll
+        for (int j = 0; j < 32; j++) S.mh[j] = min3(a[j], a[j + D], a[j + W - 3]);
+    }
+    skm_cut_mask<K>(S, m);
 }
 
 // lane-wise m ? b : a as ONE v_cndmask.  Written in C++ (`c ? x[2i+1] : x[2i]`) hipcc turns the select between two
@@ -197,9 +242,13 @@ __device__ __forceinline__ skm_rec skm_make_rec(const uint32_t (&D)[4], uint32_t
         T2 = __builtin_amdgcn_alignbit(E2, E3, 32u - o);
         T3 = __builtin_amdgcn_alignbit(E3, E4, 32u - o);
     }
-    const int kb = 2 * (int)(len + K - 1);                 // bits to keep (<= 100)
-    auto keep = [](uint32_t v, int bits) { return bits >= 32 ? v : (bits <= 0 ? 0u : (v & ~(0xFFFFFFFFu >> bits))); };
-    T0 = keep(T0, kb); T1 = keep(T1, kb - 32); T2 = keep(T2, kb - 64); T3 = keep(T3, kb - 96);
+    // bits to keep: 2 K <= kb <= 100, so T0 stays whole; T0:T1 keep their top min(kb, 64) bits and T2:T3 their top max(kb - 64, 0): two
+    // 64-bit shifts and three ands instead of a compare-and-select pair per dword
+    static_assert(K >= 17 && K <= 32, "the first dword is kept whole");
+    const int kb = 2 * (int)(len + K - 1);
+    const uint64_t m01 = (uint64_t)((int64_t)0x8000000000000000ull >> ((kb < 64 ? kb : 64) - 1));
+    const uint64_t m23 = ~(~0ull >> (kb > 64 ? kb - 64 : 0));
+    T1 &= (uint32_t)m01; T2 &= (uint32_t)(m23 >> 32); T3 &= (uint32_t)m23;
     skm_rec r;
     r.x = ((uint64_t)T0 << 32) | T1;
     r.y = ((uint64_t)T2 << 32) | (uint64_t)(T3 & 0xF0000000u) | ((uint64_t)digits << 6) | (uint64_t)len;
@@ -334,7 +383,13 @@ __device__ __forceinline__ void skm_stage_insert(const skm_stage &L, skm_rec *__
         bool got[4];
 #pragma unroll
         for (int b = 0; b < 4; b++) ca[b] = pending[b] ? ctr0 + 4u * d[b] : dummy_ctr;
-        mf_lds_read4(ca, w);                                                     // peek: is the line open?
+        // peek: is the line open?  The peek is what bounds the reserved half-word.  A reservation on a full line leaves a surplus there
+        // that only the re-opening store wipes; with the peek a record adds to a full line at most once per re-opening (it saw the line
+        // open), so the surplus stays below 4 x 1024.  Reserving blindly, a waiting lane would add once per turn of this loop for as long
+        // as the line is closed -- up to 256 per wave and turn when one digit takes everything (copies of one read), while the closing
+        // wave may be waiting for its chunk (a global atomic, thousands of cycles): 16 waves reach 65536, the carry enters the committed
+        // half-word, and a line is written early or never.  So the peek stays.
+        mf_lds_read4(ca, w);
 #pragma unroll
         for (int b = 0; b < 4; b++) inc[b] = (pending[b] && (w[b] & 0xFFFFu) < (uint32_t)SKM_LINE) ? 1u : 0u;
         mf_lds_add_rtn4(ca, inc, old);                                           // reserve a slot
