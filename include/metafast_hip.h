@@ -206,6 +206,30 @@ int  mf_wcomps_export(const mf_wcomps *c, uint64_t *sizes, int64_t *weights, int
                       uint64_t *kmers_lo);
 /* [mf_features_device] vec[c] = sum of the sample's counts > threshold over the component's k-mers, breadth[c] = found / size */
 int  mf_features_wide_device(mf_ctx *ctx, mf_wcomps *c, mf_wtable *sample, int threshold, int64_t *vec, double *breadth);
+/* ... and its files (mf_wio.hip).  No reference format exists for k > 31; these are the project's own:
+ *   wide .kmers.bin     headerless, 18-byte big-endian records: int64 high word, int64 low word, int16 count (the words of
+ *                       mf_wtable_export); strictly ascending in (high, low); only records with count > threshold
+ *   wide components.bin the layout of mf_comps_write with every member k-mer written as two int64 (high, low)
+ *   .stat.txt, components-stat.txt, .seq.fasta, .vec, .breadth: the k <= 31 files
+ * A headerless file cannot say how wide its records are, so the loaders check every record on the device (the size is a multiple of
+ * the record; every k-mer < 4^k, canonical, strictly above its predecessor; counts positive) and refuse a file that fails by name,
+ * with the number of its first bad record. */
+/* [mf_count_reads] the files' reads counted UNCUT (the histogram of .stat.txt covers what the cut of the writer drops, and a wide table does
+ * not keep it): every distinct k-mer of the read set must fit in HBM, the limit of mf_count_wide_device */
+int  mf_count_reads_wide(mf_ctx *ctx, const char *const *files, int nfiles, int k, int min_read_len, mf_wtable **out);
+/* [mf_table_write_kmers] records with count > threshold, ascending whatever order the count left the table in (it is ordered in place);
+ * stat_txt (may be NULL): the histogram of ALL entries of the table, an error for a table that was cut.  Context option
+ * "wide_write_slab": records encoded in HBM at a time */
+int  mf_wtable_write_kmers(mf_wtable *t, int threshold, const char *kmers_bin, const char *stat_txt, uint64_t *n_good);
+/* [mf_table_load_kmers] records with count <= freq_threshold dropped; one file: one ascending piece, no sort; several files: a k-mer gets the
+ * sum of its counts, saturating at 32767 */
+int  mf_wtable_load_kmers(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_wtable **out);
+/* [mf_comps_write / mf_comps_load] on load the members must be < 4^k and ascending inside a component */
+int  mf_wcomps_write(const mf_wcomps *c, const char *components_bin, const char *stat_txt);
+int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **out);
+/* [mf_features] both files loaded, mf_features_wide_device, .vec / .breadth as for k <= 31 */
+int  mf_features_wide(mf_ctx *ctx, const char *components_bin, const char *kmers_bin, int k, int threshold, const char *vec_path,
+                      const char *breadth_path);
 
 /* ---- A5/A6  .kmers.bin / .stat.txt --------------------------------------------------- */
 /* replaces IOUtils.printKmers (src/io/IOUtils.java:45-71; KmersCounterMain.java:99): 10-byte

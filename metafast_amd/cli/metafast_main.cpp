@@ -72,6 +72,24 @@ extern "C" int mf_reads_stats(const mf_reads *, uint64_t *, uint64_t *) __attrib
 extern "C" int mf_reads_device_view(const mf_reads *, const void **, const void **) __attribute__((weak));
 extern "C" void mf_reads_destroy(mf_reads *) __attribute__((weak));
 
+// (the k = 32 ... 63 path behind --wide-kmers: weak for the same reason)
+extern "C" int mf_count_reads_wide(mf_ctx *, const char *const *, int, int, int, mf_wtable **) __attribute__((weak));
+extern "C" int mf_wtable_write_kmers(mf_wtable *, int, const char *, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_wtable_load_kmers(mf_ctx *, const char *const *, int, int, int, mf_wtable **) __attribute__((weak));
+extern "C" int mf_wtable_stats(const mf_wtable *, uint64_t *, uint64_t *, int *) __attribute__((weak));
+extern "C" int mf_wtable_export(const mf_wtable *, uint64_t *, uint64_t *, uint16_t *, uint64_t, uint64_t *) __attribute__((weak));
+extern "C" void mf_wtable_destroy(mf_wtable *) __attribute__((weak));
+extern "C" int mf_build_unitigs_wide_device(mf_ctx *, mf_wtable *, int, int, mf_seqs **) __attribute__((weak));
+extern "C" int mf_seqs_write_fasta(const mf_seqs *, const char *) __attribute__((weak));
+extern "C" int mf_seqs_stats(const mf_seqs *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" void mf_seqs_destroy(mf_seqs *) __attribute__((weak));
+extern "C" int mf_cut_components_wide_device(mf_ctx *, mf_wtable *, int, int, mf_wcomps **) __attribute__((weak));
+extern "C" int mf_wcomps_write(const mf_wcomps *, const char *, const char *) __attribute__((weak));
+extern "C" int mf_wcomps_load(mf_ctx *, const char *, int, mf_wcomps **) __attribute__((weak));
+extern "C" int mf_wcomps_stats(const mf_wcomps *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" void mf_wcomps_destroy(mf_wcomps *) __attribute__((weak));
+extern "C" int mf_features_wide(mf_ctx *, const char *, const char *, int, int, const char *, const char *) __attribute__((weak));
+
 using std::string;
 using std::vector;
 
@@ -215,6 +233,7 @@ static const OptDef OPTS[] = {
     {"linear", "", false, true}, {"n_comps", "comp", false, false}, {"perc", "", false, false}, {"percent-present", "", false, false},
     {"coverage", "cov", false, true}, {"graph-file", "", false, false},
     {"seq", "", true, false}, {"components", "", true, false}, {"all-components", "a", false, true}, {"min-length", "", false, false},
+    {"wide-kmers", "", false, true},
 };
 static Args parse_args(int argc, char **argv, string *tool_out) {
     // first pass: find the tool (needed to resolve the overloaded short options)
@@ -358,20 +377,38 @@ static void check_k(int k) {                                                 // 
     if (k <= 0) die("The size of k-mer must be at least 1.");
     if (k > 31) die("The size of k-mer must be no more than 31.");
 }
+// --wide-kmers (a launch option of this driver; the reference has none): the tools from files to the matrix take 32 <= k <= 63 on 2k-bit
+// k-mers -- wide .kmers.bin / components.bin files, everything else as for k <= 31.  With k <= 31 the flag changes nothing,
+// and every other tool keeps check_k.  true: this run is wide (k has been checked); false: the caller goes on as ever, check_k first.
+static bool g_wide = false;
+static bool wide_k(int k) {
+    if (!g_wide || k <= 31) return false;
+    if (k > 63) die("The size of k-mer must be no more than 63.");
+    if (!mf_count_reads_wide || !mf_wtable_write_kmers || !mf_wtable_load_kmers || !mf_wcomps_write || !mf_features_wide || !mf_seqs_write_fasta)
+        die("--wide-kmers: this build of the library has no file level for k > 31 (mf_count_reads_wide ...)");
+    return true;
+}
+static void no_wide(bool given, const char *option) {
+    if (given) die("Option --%s is not supported with --wide-kmers and k > 31", option);
+}
 
 // kmer-counter (src/tools/KmersCounterMain.java:65-137)
 static string run_kmer_counter(Env &e, const Args &a, const vector<string> &files, int k, int b, const string &out_dir, const string &stats_dir) {
-    check_k(k);
+    const bool wide = wide_k(k);
+    if (!wide) check_k(k);
     if (files.empty()) die("Mandatory option --reads is not set");
     mf_ctx *ctx = ctx_of(e, a);
     for (auto &f : files) logmsg("INFO", "Loading file %s...", basename_of(f).c_str());
     mf_table *t = nullptr;
+    mf_wtable *wt = nullptr;
     auto fp = cptrs(files);
     // loadReads + printKmers(hm, b, ...) (KmersCounterMain.java:77-99): only the entries with value > b are handed on, so the
     // cut is made inside the counting kernels and the uncut table (> 2^32 entries for a large sample) never exists; the
     // .stat.txt histogram still covers every counted k-mer (the table remembers what the cut dropped)
     uint64_t size = 0;
-    check(mf_count_reads_above(ctx, fp.data(), (int)fp.size(), k, 0, b, &t, &size));
+    // (wide: the count is uncut -- a wide table does not remember what a cut drops, and .stat.txt lists it --, the writer makes the cut)
+    if (wide) { check(mf_count_reads_wide(ctx, fp.data(), (int)fp.size(), k, 0, &wt)); check(mf_wtable_stats(wt, &size, nullptr, nullptr)); }
+    else check(mf_count_reads_above(ctx, fp.data(), (int)fp.size(), k, 0, b, &t, &size));
     mkdirs(out_dir); mkdirs(stats_dir);
     string name;                                                             // getName :122-137
     if (files.size() == 2) {
@@ -382,13 +419,14 @@ static string run_kmer_counter(Env &e, const Args &a, const vector<string> &file
     } else name = library_name(files[0]) + (files.size() > 1 ? "+" : "");
     string out = out_dir + "/" + name + ".kmers.bin", st = stats_dir + "/" + name + ".stat.txt";
     uint64_t good = 0;
-    check(mf_table_write_kmers(t, b, out.c_str(), st.c_str(), &good));
+    if (wide) check(mf_wtable_write_kmers(wt, b, out.c_str(), st.c_str(), &good));
+    else check(mf_table_write_kmers(t, b, out.c_str(), st.c_str(), &good));
     logmsg("INFO", "%s k-mers found, %s (%.1f%%) of them is good (not erroneous)", group_digits(size).c_str(), group_digits(good).c_str(),
            size ? good * 100.0 / size : 0.0);
     if (size == 0) logmsg("WARN", "No k-mers found in reads! Perhaps you reads file is empty or k-mer size is too big");
     else if (good == 0 || good < (uint64_t)(size * 0.03)) logmsg("WARN", "Too few good k-mers were found! Perhaps you should decrease k-mer size or --maximal-bad-frequency value");
     logmsg("INFO", "Good k-mers printed to %s", out.c_str());
-    mf_table_destroy(t);
+    if (wide) mf_wtable_destroy(wt); else mf_table_destroy(t);
     return out;
 }
 // kmer-counter-many (src/tools/KmersCounterForManyFilesMain.java:66-108): sort, pair _r1/_r2, one counter per sample
@@ -414,12 +452,23 @@ static string run_seq_builder(Env &e, const Args &a, const vector<string> &files
     if (files.empty()) die("Mandatory option --k-mers is not set");
     mf_ctx *ctx = ctx_of(e, a);
     mf_table *t = nullptr;
+    mf_wtable *wt = nullptr;
+    const bool wide = wide_k(k);
     auto fp = cptrs(files);
-    check(mf_table_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &t));
+    // (wide: a table loaded from files is ascending, whatever order the count that wrote them left -- the unitigs are a function of the files)
+    if (wide) check(mf_wtable_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &wt));
+    else check(mf_table_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &t));
+    vector<uint16_t> wcnts;                                                  // wide: the counts of the table, for -bp and the distribution file
+    if (wide && (bp >= 0 || write_distribution)) {
+        uint64_t n = 0; check(mf_wtable_export(wt, nullptr, nullptr, nullptr, 0, &n));
+        wcnts.resize(n);
+        if (n) check(mf_wtable_export(wt, nullptr, nullptr, wcnts.data(), n, &n));
+    }
     if (bp >= 0) {                                                           // bottom-cut-percent :103-115
-        uint64_t n = 0; check(mf_table_export(t, -1, nullptr, nullptr, 0, &n));
+        uint64_t n = 0; if (!wide) check(mf_table_export(t, -1, nullptr, nullptr, 0, &n));
         vector<uint64_t> keys(n); vector<uint16_t> cnts(n);
         if (n) check(mf_table_export(t, -1, keys.data(), cnts.data(), n, &n));
+        if (wide) cnts.swap(wcnts);
         vector<uint64_t> stat(1024, 0); uint64_t total = 0;
         for (uint16_t c : cnts) { total += c; stat[c >= 1024 ? 1023 : c]++; }
         uint64_t to_cut = total * (uint64_t)bp / 100, cur = 0;
@@ -432,11 +481,26 @@ static string run_seq_builder(Env &e, const Args &a, const vector<string> &files
     string fasta = out_dir + "/" + base + (files.size() > 1 ? "+" : "") + ".seq.fasta";
     string distr = wd + "/distribution";
     uint64_t nseq = 0;
-    check(mf_build_unitigs(ctx, t, k, b, l, fasta.c_str(), write_distribution ? distr.c_str() : nullptr, &nseq));
+    if (wide) {
+        if (write_distribution) {                                            // stat[min(value, 1023)]++, lines "i stat[i]" (SeqBuilderMain.java:84-98, 170-176)
+            if (bp >= 0) { uint64_t n = 0; check(mf_wtable_export(wt, nullptr, nullptr, nullptr, 0, &n)); wcnts.resize(n); if (n) check(mf_wtable_export(wt, nullptr, nullptr, wcnts.data(), n, &n)); }
+            vector<uint64_t> stat(1024, 0);
+            for (uint16_t c : wcnts) stat[c >= 1024 ? 1023 : c]++;
+            FILE *f = fopen(distr.c_str(), "w");
+            if (!f) die("can't write '%s'", distr.c_str());
+            for (int i = 1; i < 1024; i++) fprintf(f, "%d %llu\n", i, (unsigned long long)stat[i]);
+            fclose(f);
+        }
+        mf_seqs *sq = nullptr;
+        check(mf_build_unitigs_wide_device(ctx, wt, b, l, &sq));
+        check(mf_seqs_write_fasta(sq, fasta.c_str()));
+        check(mf_seqs_stats(sq, &nseq, nullptr));
+        mf_seqs_destroy(sq);
+    } else check(mf_build_unitigs(ctx, t, k, b, l, fasta.c_str(), write_distribution ? distr.c_str() : nullptr, &nseq));
     logmsg("INFO", "%s sequences found", group_digits(nseq).c_str());
     if (nseq == 0) logmsg("WARN", "No sequences were found! Perhaps you should decrease --min-seq-len or --maximal-bad-frequency values");
     logmsg("INFO", "Sequences printed to %s", fasta.c_str());
-    mf_table_destroy(t);
+    if (wide) mf_wtable_destroy(wt); else mf_table_destroy(t);
     return fasta;
 }
 // seq-builder-many (src/tools/SeqBuilderForManyFilesMain.java:82-94): one seq-builder per k-mers file, all in <wd>/sub-builder.  Every one of
@@ -496,6 +560,29 @@ static bool run_component_cutter_sharded(Env &e, const Args &a, const vector<str
 }
 static string run_component_cutter(Env &e, const Args &a, const vector<string> &files, int k, int l, int b1, int b2, const string &wd, const string &comp_file) {
     if (files.empty()) die("Mandatory option --sequences is not set");
+    if (wide_k(k)) {
+        // the wide cutter is replicated: whatever --devices names, this step runs on entry 0 (the per-library steps spread as ever)
+        parse_devices(e, a);
+        if (e.devs.size() > 1) logmsg("DEBUG", "Cutting components on one device context (the cutter for k > 31 is not sharded)");
+        mf_ctx *ctx = ctx_of(e, a);
+        auto fp = cptrs(files);
+        logmsg("DEBUG", "Loading sequences from files...");
+        mf_wtable *wt = nullptr;
+        check(mf_count_reads_wide(ctx, fp.data(), (int)fp.size(), k, l, &wt));
+        uint64_t size = 0; check(mf_wtable_stats(wt, &size, nullptr, nullptr));
+        if (size == 0) die("No sequences were found in input files! The following steps will be useless");
+        logmsg("INFO", "Searching for components...");
+        mkdirs(wd); mkparent(comp_file);
+        mf_wcomps *wc = nullptr;
+        check(mf_cut_components_wide_device(ctx, wt, b1, b2, &wc));
+        check(mf_wcomps_write(wc, comp_file.c_str(), (wd + "/components-stat-" + std::to_string(b1) + "-" + std::to_string(b2) + ".txt").c_str()));
+        uint64_t nc = 0; check(mf_wcomps_stats(wc, &nc, nullptr));
+        logmsg("INFO", "Total %s components were found", group_digits(nc).c_str());
+        if (nc == 0) logmsg("WARN", "No components were extracted! Perhaps you should decrease --min-component-size value");
+        logmsg("INFO", "Components saved to %s", comp_file.c_str());
+        mf_wcomps_destroy(wc); mf_wtable_destroy(wt);
+        return comp_file;
+    }
     {
         mkdirs(wd);
         const string stat = wd + "/components-stat-" + std::to_string(b1) + "-" + std::to_string(b2) + ".txt";
@@ -533,6 +620,12 @@ static vector<string> run_features(Env &e, const Args &a, const string &comp_fil
                                    int k, int thr, const string &wd) {
     if (comp_file.empty()) die("Mandatory option --components-file is not set");
     if (kmers.empty() && reads.empty()) die("No input files: pass reads (-i) or k-mers files (-ka)");
+    const bool wide = wide_k(k);
+    if (wide) {                                                              // (k-mers files only: no selected set, no features from reads)
+        no_wide(!a.list("selected").empty(), "selected");
+        no_wide(a.flag("use-reads-for-calculating-features"), "use-reads-for-calculating-features");
+        no_wide(!reads.empty(), "reads");
+    }
     parse_devices(e, a);
     string out_dir = wd + "/vectors";
     mkdirs(out_dir);
@@ -561,7 +654,8 @@ static vector<string> run_features(Env &e, const Args &a, const string &comp_fil
             const string &kf = kmers[i - reads.size()];
             string base = remove_ext(basename_of(kf), {".kmers.bin"});
             string vec = out_dir + "/" + base + ".vec", br = out_dir + "/" + base + ".breadth";
-            check(mf_features_selected(ctx, comp_file.c_str(), kf.c_str(), k, thr, selected(), vec.c_str(), br.c_str()));
+            if (wide) check(mf_features_wide(ctx, comp_file.c_str(), kf.c_str(), k, thr, vec.c_str(), br.c_str()));
+            else check(mf_features_selected(ctx, comp_file.c_str(), kf.c_str(), k, thr, selected(), vec.c_str(), br.c_str()));
             logmsg("INFO", "Features for file %s printed to %s", basename_of(kf).c_str(), vec.c_str());
             vecs[i] = vec;
         }
@@ -937,7 +1031,7 @@ static vector<PV> tool_kmer_counter(Run &r) {
     return {PV::file("resulting-kmers-file", run_kmer_counter(r.e, r.a, r.a.list("reads"), r.k, r.num("maximal-bad-frequence"), r.str("output-dir"), r.str("stats-dir")))};
 }
 static vector<PV> tool_kmer_counter_many(Run &r) {
-    check_k(r.k);
+    if (!wide_k(r.k)) check_k(r.k);
     return {PV::files("resulting-kmers-files", run_kmer_counter_many(r.e, r.a, r.a.list("reads"), r.k, r.num("maximal-bad-frequence"), r.wd, r.str("output-dir"), r.str("stats-dir")))};
 }
 // seq-builder-many declares no default for -b (it may not be given next to -bp) and hands a null on: seq-builder's own default applies
@@ -1487,7 +1581,8 @@ static vector<PV> tool_matrix_builder(Run &r) {
     logmsg("INFO", "Found %zu libraries to process", reads.size());
     if (reads.empty()) die("No libraries to process!!! Can't continue the calculations.");
     const bool use_reads = a.flag("use-reads-for-calculating-features");                       // DistanceMatrixBuilderMain.java:162-165
-    check_k(k);
+    if (wide_k(k)) { no_wide(!a.list("selected").empty(), "selected"); no_wide(use_reads, "use-reads-for-calculating-features"); }
+    else check_k(k);
     // (-b in either spelling: the counters' --maximal-bad-frequence is taken where --maximal-bad-frequency is not given)
     const int b = a.geti("maximal-bad-frequency", a.geti("maximal-bad-frequence", atoi(r.dflt("maximal-bad-frequency").c_str()))), l = r.num("min-seq-len");
     const int b1 = r.num("min-component-size"), b2 = r.num("max-component-size");
@@ -1733,6 +1828,10 @@ int main(int argc, char **argv) {
             can = can && props_equal(tool_inputs(*t, a, wd, e.start_ts), stored);
         } else can = false;
     }
+    // --wide-kmers goes to in.properties like a parameter where it is in effect (k > 31), so that -c and -s continue a wide workDir
+    g_wide = a.flag("wide-kmers");
+    const bool wide_run = g_wide && t->param("k") && a.geti("k", 0) > 31;
+    auto inputs = [&]() { vector<PV> v = tool_inputs(*t, a, wd, e.start_ts); if (wide_run) v.push_back(PV::flag("wide-kmers", true)); return v; };
     Run r{e, a, *t, wd, a.get("start"), a.get("finish"), force, 0};
     if (!force && r.start.empty() && can) {
         logmsg("INFO", "SUCCESS file found for tool %s - loading results...", tool.c_str());
@@ -1745,7 +1844,7 @@ int main(int argc, char **argv) {
         if (!n.name) break;
         if (!a.has(n.name)) { if (n.sht) die("Mandatory argument --%s (-%s) not set", n.name, n.sht); else die("Mandatory argument --%s not set", n.name); }
     }
-    props_write(inprop, tool_inputs(*t, a, wd, e.start_ts));
+    props_write(inprop, inputs());
     const vector<PV> outs = t->run(r);
     const double t_work = since_start();
     for (mf_ctx *c : e.ctxs) if (c) mf_ctx_synchronize(c);

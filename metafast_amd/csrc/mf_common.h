@@ -113,6 +113,7 @@ struct mf_ctx {
     int64_t opt_wide_skm_unit = 2400;       // ... k-mer occurrences per counting unit (tests lower it: units that overflow the LDS table are counted in passes)
     int64_t opt_wide_big_bucket = 256;   // wide_finish: buckets of more entries than this (<= 256) go through the LDS hash table instead of the walk (tests lower it)
     int64_t opt_wide_distinct = 1280;    // ... buckets of more distinct k-mers than this (<= 1280) are sorted aside (tests lower it)
+    int64_t opt_wide_write_slab = 1 << 25;   // mf_wtable_write_kmers: records encoded in HBM at a time before they stream down to the file (tests: a few hundred)
     int64_t opt_wide_passes = 0;   // mf_count_wide_device: passes over the reads, each for one prefix class of the canonical k-mers (0 = as many as the memory asks for; tests force a number)
     // what the runs leave behind: counters, pools and stream handles
     double t_hipmalloc = 0; uint64_t n_hipmalloc = 0, b_hipmalloc = 0;   // seconds / calls / bytes inside hipMalloc (diagnostics: MF_IO_TIMING)

@@ -180,6 +180,7 @@ static const struct { const char *name; int64_t mf_ctx::*field; int64_t lo = OPT
     {"wide_skm_fine", &mf_ctx::opt_wide_skm_fine}, {"wide_skm_pack", &mf_ctx::opt_wide_skm_pack}, {"wide_skm_merge", &mf_ctx::opt_wide_skm_merge},
     {"wide_skm_lead", &mf_ctx::opt_wide_skm_lead}, {"wide_skm_unit", &mf_ctx::opt_wide_skm_unit},
     {"wide_big_bucket", &mf_ctx::opt_wide_big_bucket, 1, 256}, {"wide_distinct", &mf_ctx::opt_wide_distinct, 1, 1280}, {"wide_passes", &mf_ctx::opt_wide_passes, 0, 65536},
+    {"wide_write_slab", &mf_ctx::opt_wide_write_slab, 1, (int64_t)1 << 30},
 };
 
 extern "C" int mf_ctx_set_option(mf_ctx *ctx, const char *name, int64_t v) {

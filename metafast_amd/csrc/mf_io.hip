@@ -1115,6 +1115,12 @@ static int write_features_files(const std::vector<int64_t> &vec, const std::vect
     return MF_OK;
 }
 
+// (for the wide file level, mf_wio.hip)
+int mf_device_to_file(mf_ctx *ctx, const void *d_src, size_t bytes, int fd, off_t file_off, const char *path) { return device_to_file(ctx, d_src, bytes, fd, file_off, path); }
+int mf_write_features_files(const std::vector<int64_t> &vec, const std::vector<double> &br, const char *vec_path, const char *breadth_path) {
+    return write_features_files(vec, br, vec_path, breadth_path);
+}
+
 // test hook (not part of the ABI; tests/test_inflate_cpu.py): the image of a gzip file -> its content through the whole-buffer decoder alone (mode 1:
 // MF_ERR where it refuses), through zlib alone (0), in the product's order (2), or through the decoder with the several-thread form forced on small
 // inputs (3: pieces of 48 KB; MF_ERR also where that form steps back to one thread).  *out: malloc'd, mf_debug_free

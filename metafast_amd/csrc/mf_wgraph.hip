@@ -179,14 +179,6 @@ extern "C" int mf_build_unitigs_wide_device(mf_ctx *ctx, mf_wtable *t, int freq_
 // ---------------------------------------------------------------------------------------------
 // A10  components
 // ---------------------------------------------------------------------------------------------
-struct mf_wcomps {
-    mf_ctx *ctx = nullptr;
-    int k = 0;
-    uint64_t n = 0, n_kmers = 0;
-    std::vector<uint64_t> sizes; std::vector<int64_t> weights; std::vector<int32_t> thr;
-    // the member k-mers grouped by component (final order), ascending inside a component; comp[j] = component of k-mer j
-    mf_buf<uint64_t> hi, lo; mf_buf<uint32_t> comp;
-};
 __global__ void k_w_gather(const uint64_t *__restrict__ ids, uint64_t n, const uint64_t *__restrict__ thi, const uint64_t *__restrict__ tlo, uint64_t *__restrict__ ohi,
                            uint64_t *__restrict__ olo) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

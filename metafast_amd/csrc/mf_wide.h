@@ -2,6 +2,7 @@
 // mf_wgraph.hip (unitigs, components, features on 128-bit keys).  The reference stops at k = 31 (src/tools/KmersCounterMain.java:66-73).
 #pragma once
 #include <memory>
+#include <sys/types.h>
 #include <vector>
 #include "mf_common.h"
 
@@ -34,6 +35,20 @@ int mf_wtable_flatten(mf_wtable *t);                      // all pieces into one
 int mf_wtable_ensure_index(mf_wtable *t);                 // flatten + index
 // entries of (hi, lo, cnt)[n] with cnt > thr -> a new piece (order kept)
 int mf_wide_compact(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, int thr, mf_wtable::piece &out);
+
+// connected components of 2k-bit k-mers (mf_cut_components_wide_device, mf_wgraph.hip; mf_wcomps_load, mf_wio.hip)
+struct mf_wcomps {
+    mf_ctx *ctx = nullptr;
+    int k = 0;
+    uint64_t n = 0, n_kmers = 0;
+    std::vector<uint64_t> sizes; std::vector<int64_t> weights; std::vector<int32_t> thr;
+    // the member k-mers grouped by component (final order), ascending inside a component; comp[j] = component of k-mer j
+    mf_buf<uint64_t> hi, lo; mf_buf<uint32_t> comp;
+};
+// the file level (mf_wio.hip): the count histogram of a table over all its pieces (32768 bins), and the two writers of mf_io.hip it shares
+int mf_wtable_count_hist(const mf_wtable *t, std::vector<uint64_t> &hist);
+int mf_device_to_file(mf_ctx *ctx, const void *d_src, size_t bytes, int fd, off_t file_off, const char *path);
+int mf_write_features_files(const std::vector<int64_t> &vec, const std::vector<double> &br, const char *vec_path, const char *breadth_path);
 
 #ifdef __HIPCC__
 #define MF_WIDX_EMPTY 0xFFFFFFFFFFFFFFFFull

@@ -50,6 +50,12 @@ _SIGS = {
     "mf_wcomps_stats": (i32, [vp, pu64, pu64]),
     "mf_wcomps_export": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "mf_features_wide_device": (i32, [vp, vp, vp, i32, vp, vp]),
+    "mf_count_reads_wide": (i32, [vp, C.POINTER(cp), i32, i32, i32, pvp]),
+    "mf_wtable_write_kmers": (i32, [vp, i32, cp, cp, pu64]),
+    "mf_wtable_load_kmers": (i32, [vp, C.POINTER(cp), i32, i32, i32, pvp]),
+    "mf_wcomps_write": (i32, [vp, cp, cp]),
+    "mf_wcomps_load": (i32, [vp, cp, i32, pvp]),
+    "mf_features_wide": (i32, [vp, cp, cp, i32, i32, cp, cp]),
     "mf_comm_create_local": (i32, [vp, i32, vp]),
     "mf_comm_rccl_id": (i32, [vp]),
     "mf_comm_create_rccl": (i32, [vp, vp, i32, i32, pvp]),
@@ -412,6 +418,29 @@ class Context:
         br = np.zeros(n, dtype=np.float64)
         _check(lib().mf_features_wide_device(self.h, comps.h, sample.h, threshold, vec.ctypes.data, br.ctypes.data))
         return vec, br
+
+    # ---- the wide path's files (mf_wio.hip; formats: DESIGN 4.4) ----
+    def count_reads_wide(self, files, k, min_read_len=0):
+        """NO-REFERENCE EXTENSION, 32 <= k <= 63: count_reads -> WideTable, uncut (its .stat.txt covers what the writer's cut drops)"""
+        t = C.c_void_p()
+        _check(lib().mf_count_reads_wide(self.h, _cfiles(files), len(files), k, min_read_len, C.byref(t)))
+        return WideTable(self, t)
+
+    def load_kmers_wide(self, files, k, freq_threshold=0):
+        """NO-REFERENCE EXTENSION: wide .kmers.bin files (18-byte records, validated on the device) -> one-piece ascending WideTable;
+        a k-mer of several files gets the saturating sum of its counts"""
+        t = C.c_void_p()
+        _check(lib().mf_wtable_load_kmers(self.h, _cfiles(files), len(files), freq_threshold, k, C.byref(t)))
+        return WideTable(self, t)
+
+    def load_components_wide(self, components_bin, k):
+        c = C.c_void_p()
+        _check(lib().mf_wcomps_load(self.h, os.fsencode(components_bin), k, C.byref(c)))
+        return WideComps(self, c)
+
+    def features_wide_files(self, components_bin, kmers_bin, k, threshold=0, vec_path=None, breadth_path=None):
+        """NO-REFERENCE EXTENSION: features (files) on wide files; .vec / .breadth as for k <= 31"""
+        _check(lib().mf_features_wide(self.h, os.fsencode(components_bin), os.fsencode(kmers_bin), k, threshold, _opt(vec_path), _opt(breadth_path)))
 
     def count_device_above(self, d_bases, d_offsets, n_reads, n_bases, k, threshold, min_read_len=0):
         """count, keeping only the k-mers with count > threshold (what the k-mer counter hands on, IOUtils.printKmers);
@@ -819,9 +848,10 @@ class WideTable:
         self.ctx, self.h = ctx, h
 
     def close(self):
-        if self.h:
-            lib().mf_wtable_destroy(self.h)
-            self.h = None
+        # (a handle that outlives its context -- collected late, out of a reference cycle -- has nothing left to give back: the context took its arena along)
+        if getattr(self, "h", None) and _lib is not None and getattr(self.ctx, "h", None):
+            _lib.mf_wtable_destroy(self.h)
+        self.h = None
 
     __del__ = close
 
@@ -845,6 +875,12 @@ class WideTable:
 
     def drop_index(self):
         _check(lib().mf_wtable_drop_index(self.h))
+
+    def write_kmers(self, threshold, kmers_bin, stat_txt=None):
+        """wide .kmers.bin (records with count > threshold, ascending) + optionally .stat.txt; -> number of records written"""
+        n = C.c_uint64()
+        _check(lib().mf_wtable_write_kmers(self.h, threshold, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
+        return n.value
 
     def lookup(self, kmers):
         """kmers: iterable of Python ints (2k-bit k-mers) -> int32 counts, -1 = absent"""
@@ -1042,9 +1078,10 @@ class WideComps:
         self.ctx, self.h = ctx, h
 
     def close(self):
-        if self.h:
-            lib().mf_wcomps_destroy(self.h)
-            self.h = None
+        # (a handle that outlives its context -- collected late, out of a reference cycle -- has nothing left to give back: the context took its arena along)
+        if getattr(self, "h", None) and _lib is not None and getattr(self.ctx, "h", None):
+            _lib.mf_wcomps_destroy(self.h)
+        self.h = None
 
     __del__ = close
 
@@ -1063,6 +1100,9 @@ class WideComps:
         off = np.zeros(n + 1, dtype=np.uint64); hi = np.zeros(nk, dtype=np.uint64); lo = np.zeros(nk, dtype=np.uint64)
         _check(lib().mf_wcomps_export(self.h, sizes.ctypes.data, weights.ctypes.data, thr.ctypes.data, off.ctypes.data, hi.ctypes.data, lo.ctypes.data))
         return dict(sizes=sizes, weights=weights, thr=thr, offsets=off, hi=hi, lo=lo)
+
+    def write(self, components_bin, stat_txt=None):
+        _check(lib().mf_wcomps_write(self.h, os.fsencode(components_bin), _opt(stat_txt)))
 
 
 class KmersPerSample:
