@@ -230,6 +230,17 @@ int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **
 /* [mf_features] both files loaded, mf_features_wide_device, .vec / .breadth as for k <= 31 */
 int  mf_features_wide(mf_ctx *ctx, const char *components_bin, const char *kmers_bin, int k, int threshold, const char *vec_path,
                       const char *breadth_path);
+/* [mf_comps_unitigs_device / mf_comp2seq] comp2seq on wide components (mf_wcomp2seq.hip): the semantics of the k <= 31 entry points on
+ * 2k-bit k-mers.  split != 0: per component the unitigs (threshold 0, minimal length k) of its canonical k-mers, each weighted with its
+ * multiplicity in the member list, a neighbour counting only inside the SAME component, all components in one pass; split == 0: the
+ * unitigs of the one table of all members (count = multiplicity over all components, capped at 32767).  The components know their k
+ * (mf_wcomps_load takes it).  A member list may hold x and rc(x): that k-mer then has multiplicity 2.  The result is an ordinary mf_seqs
+ * for mf_seqs_components / mf_seqs_export / mf_seqs_write_fasta, in (component, canonical start k-mer, strand) order.  Fewer than
+ * 2^31 - 1 members.  The file form writes mf_comp2seq's layout under out_dir with WIDE .kmers.bin records; nothing is written before
+ * mf_wcomps_load has accepted the file. */
+int  mf_wcomps_unitigs_device(mf_ctx *ctx, mf_wcomps *c, int split, mf_seqs **out);
+int  mf_comp2seq_wide(mf_ctx *ctx, const char *components_bin, int k, int split, const char *out_dir, uint64_t *n_files,
+                      uint64_t *n_seqs);
 
 /* ---- A5/A6  .kmers.bin / .stat.txt --------------------------------------------------- */
 /* replaces IOUtils.printKmers (src/io/IOUtils.java:45-71; KmersCounterMain.java:99): 10-byte

@@ -89,6 +89,7 @@ extern "C" int mf_wcomps_load(mf_ctx *, const char *, int, mf_wcomps **) __attri
 extern "C" int mf_wcomps_stats(const mf_wcomps *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" void mf_wcomps_destroy(mf_wcomps *) __attribute__((weak));
 extern "C" int mf_features_wide(mf_ctx *, const char *, const char *, int, int, const char *, const char *) __attribute__((weak));
+extern "C" int mf_comp2seq_wide(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -386,6 +387,12 @@ static bool wide_k(int k) {
     if (k > 63) die("The size of k-mer must be no more than 63.");
     if (!mf_count_reads_wide || !mf_wtable_write_kmers || !mf_wtable_load_kmers || !mf_wcomps_write || !mf_features_wide || !mf_seqs_write_fasta)
         die("--wide-kmers: this build of the library has no file level for k > 31 (mf_count_reads_wide ...)");
+    return true;
+}
+// view and bin2fasta read wide files on the host and call no library function: wide without a look at the library's symbols
+static bool wide_host_k(int k) {
+    if (!g_wide || k <= 31) return false;
+    if (k > 63) die("The size of k-mer must be no more than 63.");
     return true;
 }
 static void no_wide(bool given, const char *option) {
@@ -830,12 +837,59 @@ static vector<HostComp> read_components(const string &path) {       // Connected
     }
     return cs;
 }
+// ... and of the wide files behind --wide-kmers: 18-byte records, two words per member.  A headerless file of the wrong width is
+// the mistake a user makes here: a size that is no whole number of wide records, or member lists that run past the end, is an error
+static string kmer_string(uint64_t hi, uint64_t lo, int k) {
+    string s((size_t)k, 'A');
+    for (int i = 0; i < k; i++) { const int sh = 2 * (k - 1 - i); s[(size_t)i] = "AGCT"[(sh >= 64 ? hi >> (sh - 64) : lo >> sh) & 3u]; }
+    return s;
+}
+static vector<unsigned char> slurp_wide_kmers(const string &path, int k) {
+    vector<unsigned char> b = slurp(path);
+    if (b.size() % 18) die("Can't read wide k-mers file %s: size %zu is not a multiple of the 18-byte record (k = %d; is this a file of another k?)", path.c_str(), b.size(), k);
+    return b;
+}
+struct WideComp { int64_t weight; vector<std::pair<uint64_t, uint64_t>> kmers; };
+static vector<WideComp> read_components_wide(const string &path, int k) {
+    vector<unsigned char> b = slurp(path);
+    if (b.size() < 4) die("Can't load wide components from %s: %zu bytes is not a components file", path.c_str(), b.size());
+    size_t pos = 4; const uint64_t n = be_read(&b[0], 4);
+    if (4 + 12 * n > b.size()) die("Can't load wide components from %s: %llu components, more than the file holds (k = %d; is this a file of another k?)", path.c_str(), (unsigned long long)n, k);
+    vector<WideComp> cs((size_t)n);
+    for (size_t i = 0; i < cs.size(); i++) {
+        if (pos + 12 > b.size()) die("Can't load wide components from %s: the file ends inside the header of component %zu (k = %d; is this a file of another k?)", path.c_str(), i + 1, k);
+        const uint64_t sz = be_read(&b[pos], 4); cs[i].weight = (int64_t)be_read(&b[pos + 4], 8); pos += 12;
+        if (16 * sz > b.size() - pos) die("Can't load wide components from %s: component %zu has size %llu, more than the file holds (k = %d; is this a file of another k?)", path.c_str(), i + 1, (unsigned long long)sz, k);
+        cs[i].kmers.resize((size_t)sz);
+        for (auto &km : cs[i].kmers) { km.first = be_read(&b[pos], 8); km.second = be_read(&b[pos + 8], 8); pos += 16; }
+    }
+    if (pos != b.size()) die("Can't load wide components from %s: %zu bytes after the last component (k = %d; is this a file of another k?)", path.c_str(), b.size() - pos, k);
+    return cs;
+}
 static FILE *open_out(const string &path) { if (path.empty()) return stdout; FILE *f = fopen(path.c_str(), "w"); if (!f) die("Couldn't open output file"); return f; }
 static void close_out(FILE *f) { if (f != stdout) fclose(f); else fflush(f); }
 static void run_view(const Args &a, int k) {
     const string kf = a.get("kmers-file"), cf = a.get("components-file");
     if (kf.empty() && cf.empty()) { logmsg("WARN", "No input file is selected  --->  no data to display!"); return; }
+    const bool wide = wide_host_k(k);
+    if (wide) no_wide(a.flag("long"), "long");
     FILE *out = open_out(a.get("output-file"));
+    if (wide && !kf.empty()) {
+        vector<unsigned char> b = slurp_wide_kmers(kf, k);
+        fprintf(out, "Kmer\tCount\n");
+        for (size_t p = 0; p < b.size(); p += 18) fprintf(out, "%s\t%lld\n", kmer_string(be_read(&b[p], 8), be_read(&b[p + 8], 8), k).c_str(), (long long)(int16_t)be_read(&b[p + 16], 2));
+    }
+    if (wide && !cf.empty()) {
+        vector<WideComp> cs = read_components_wide(cf, k);
+        logmsg("INFO", "%zu components loaded from %s", cs.size(), cf.c_str());
+        fprintf(out, "%zu components:\n", cs.size());
+        for (size_t i = 0; i < cs.size(); i++) {
+            fprintf(out, "Component %zu, size = %zu kmers, weight = %lld. Kmers:\n", i + 1, cs[i].kmers.size(), (long long)cs[i].weight);
+            for (auto &km : cs[i].kmers) fprintf(out, "%s\n", kmer_string(km.first, km.second, k).c_str());
+            fprintf(out, "\n");
+        }
+    }
+    if (wide) { close_out(out); return; }
     if (!kf.empty()) {
         const int rec = a.flag("long") ? 16 : 10;          // IOUtils.loadLongKmers / loadKmers
         vector<unsigned char> b = slurp(kf);
@@ -859,6 +913,31 @@ static void run_bin2fasta(const Args &a, int k) {
     const string kf = a.get("kmers-file"), cf = a.get("components-file"), prefix = a.get("output-file");
     if (kf.empty() && cf.empty()) { logmsg("WARN", "No input file is selected  --->  no data to display!"); return; }
     if (!prefix.empty()) mkparent(prefix);
+    if (wide_host_k(k)) {
+        if (!kf.empty()) {
+            vector<unsigned char> b = slurp_wide_kmers(kf, k);
+            FILE *out = open_out(prefix.empty() ? "" : prefix + ".fasta");
+            for (size_t p = 0, i = 1; p < b.size(); p += 18, i++) fprintf(out, ">%zu\n%s\n", i, kmer_string(be_read(&b[p], 8), be_read(&b[p + 8], 8), k).c_str());
+            close_out(out);
+        }
+        if (!cf.empty()) {
+            vector<WideComp> cs = read_components_wide(cf, k);
+            logmsg("INFO", "%zu components loaded from %s", cs.size(), cf.c_str());
+            const bool split = a.flag("split");
+            FILE *out = split ? nullptr : open_out(prefix.empty() ? "" : prefix + ".fasta");
+            for (size_t i = 0; i < cs.size(); i++) {
+                if (split) out = open_out(prefix.empty() ? "" : prefix + "_" + std::to_string(i + 1) + ".fasta");
+                size_t j = 1;
+                for (auto &km : cs[i].kmers) {
+                    if (split) fprintf(out, ">%zu\n", j++); else fprintf(out, ">%zu_%zu\n", i + 1, j++);
+                    fprintf(out, "%s\n", kmer_string(km.first, km.second, k).c_str());
+                }
+                if (split) close_out(out);
+            }
+            if (!split) close_out(out);
+        }
+        return;
+    }
     if (!kf.empty()) {
         FILE *out = open_out(prefix.empty() ? "" : prefix + ".fasta");
         vector<unsigned char> b = slurp(kf);
@@ -1440,14 +1519,16 @@ static vector<PV> tool_component_colored(Run &r) {
 static vector<PV> tool_comp2seq(Run &r) {
     // ComponentsToSequences.java:41-76: bin2fasta, kmer-counter-many -b 0, seq-builder-many -b 0 -l k as sub-steps with the work
     // directories kmers_fasta, kmer-counter-many and seq-builder-many -- here one segmented build of all components (mf_comp2seq)
+    // (--wide-kmers and k > 31: the same on a wide components.bin, mf_comp2seq_wide)
     const int k = r.k; const string &wd = r.wd;
-    check_k(k);
+    const bool wide = wide_k(k);
+    if (!wide) check_k(k);
     const bool split = r.a.flag("split");
     const string cf = r.str("components-file");
-    r.entry(mf_comp2seq != nullptr, "mf_comp2seq");
+    if (wide) r.entry(mf_comp2seq_wide != nullptr, "mf_comp2seq_wide"); else r.entry(mf_comp2seq != nullptr, "mf_comp2seq");
     mf_ctx *ctx = r.ctx();
     uint64_t nf = 0, ns = 0;
-    check(mf_comp2seq(ctx, cf.c_str(), k, split ? 1 : 0, wd.c_str(), &nf, &ns));
+    check(wide ? mf_comp2seq_wide(ctx, cf.c_str(), k, split ? 1 : 0, wd.c_str(), &nf, &ns) : mf_comp2seq(ctx, cf.c_str(), k, split ? 1 : 0, wd.c_str(), &nf, &ns));
     if (split) logmsg("INFO", "%s components loaded from %s", group_digits(nf).c_str(), cf.c_str());
     logmsg("INFO", "%s sequences found", group_digits(ns).c_str());
     if (ns == 0) logmsg("WARN", "No sequences were found! Perhaps you should decrease --min-seq-len or --maximal-bad-frequency values");

@@ -2,6 +2,8 @@
 // components, the pair index over them and the per-row flags of k_c2s_flags.  The kernels stay in mf_comp2seq.hip; here are the probe
 // every user of the pair index needs and the host entry points.
 #pragma once
+#include <string>
+#include <vector>
 #include "mf_common.h"
 #include "mf_join.h"
 #include "mf_unitig.h"
@@ -36,3 +38,9 @@ int c2s_build_rows(mf_ctx *ctx, const mf_comps *c, int k, c2s_rows &R);
 // the pair index of the rows (capacity *cap, a power of two); k_c2s_flags over them into A.info / A.ridx / A.lidx / A.pal
 int c2s_pair_index(mf_ctx *ctx, const c2s_rows &R, int k, mf_buf<mf_uslot> &slots, uint64_t *cap);
 int c2s_flags_launch(mf_ctx *ctx, const mf_uslot *slots, uint64_t cap, const c2s_rows &R, const ut_arrays &A);
+// the file form's helpers, shared with the wide tool (mf_wcomp2seq.hip): mkdir -p, a whole file written at once, and Sequence.printSequences as
+// mf_seqs_write_fasta writes it for the sequences [lo, hi) numbered from 1
+int c2s_mkdirs(const std::string &p);
+int c2s_write_file(const std::string &path, const std::string &data);
+void c2s_seq_text(const std::vector<uint8_t> &b, const std::vector<uint64_t> &o, const std::vector<int32_t> &a, const std::vector<int32_t> &mn,
+                  const std::vector<int32_t> &mx, uint64_t lo, uint64_t hi, std::string &out);

@@ -273,7 +273,7 @@ extern "C" int mf_comps_unitigs_device(mf_ctx *ctx, mf_comps *c, int split, mf_s
 }
 
 // ---- the file form ----
-static int c2s_mkdirs(const std::string &p) {
+int c2s_mkdirs(const std::string &p) {
     std::string cur;
     for (size_t i = 0; i <= p.size(); i++) {
         if ((i == p.size() || p[i] == '/') && !cur.empty() && mkdir(cur.c_str(), 0777) != 0 && errno != EEXIST) return mf_set_error("can't create directory %s", cur.c_str());
@@ -281,7 +281,7 @@ static int c2s_mkdirs(const std::string &p) {
     }
     return MF_OK;
 }
-static int c2s_write_file(const std::string &path, const std::string &data) {
+int c2s_write_file(const std::string &path, const std::string &data) {
     FILE *f = fopen(path.c_str(), "w");
     if (!f) return mf_set_error("can't write '%s'", path.c_str());
     const bool bad = data.size() && fwrite(data.data(), 1, data.size(), f) != data.size();
@@ -292,7 +292,7 @@ static void c2s_kmer_text(uint64_t km, int k, std::string &out) {       // Short
     for (int i = 0; i < k; i++) out.push_back("AGCT"[(km >> (2 * (k - 1 - i))) & 3u]);
 }
 // Sequence.printSequences as mf_seqs_write_fasta writes it, for the sequences [lo, hi) numbered from 1
-static void c2s_seq_text(const std::vector<uint8_t> &b, const std::vector<uint64_t> &o, const std::vector<int32_t> &a, const std::vector<int32_t> &mn,
+void c2s_seq_text(const std::vector<uint8_t> &b, const std::vector<uint64_t> &o, const std::vector<int32_t> &a, const std::vector<int32_t> &mn,
                          const std::vector<int32_t> &mx, uint64_t lo, uint64_t hi, std::string &out) {
     char hdr[128];
     for (uint64_t i = lo; i < hi; i++) {

@@ -36,6 +36,9 @@ int mf_wtable_ensure_index(mf_wtable *t);                 // flatten + index
 // entries of (hi, lo, cnt)[n] with cnt > thr -> a new piece (order kept)
 int mf_wide_compact(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, int thr, mf_wtable::piece &out);
 
+// (hi, lo, cnt)[n] in any order -> out: the distinct k-mers ascending with the saturating sum of their counts (mf_wio.hip)
+int mf_wide_merge_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wtable::piece &out);
+
 // connected components of 2k-bit k-mers (mf_cut_components_wide_device, mf_wgraph.hip; mf_wcomps_load, mf_wio.hip)
 struct mf_wcomps {
     mf_ctx *ctx = nullptr;

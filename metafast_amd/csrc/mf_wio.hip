@@ -228,6 +228,40 @@ __global__ void k_wio_sum_runs(const uint64_t *__restrict__ hi, const uint64_t *
     const uint64_t o = idx[i];
     ohi[o] = hi[i]; olo[o] = lo[i]; ocnt[o] = (uint16_t)(s > (uint32_t)MF_MAX_COUNT ? (uint32_t)MF_MAX_COUNT : s);
 }
+// (hi, lo, cnt)[n] in any order -> out: the distinct k-mers ascending, each with the saturating sum of its entries' counts.  Two stable passes
+// -- the low word, then the high word's 2k - 64 bits -- that carry the entry's index, then the saturating sum of every run of equal k-mers
+// (mf_wtable_load_kmers over several files; comp2seq's table of all members, mf_wcomp2seq.hip)
+int mf_wide_merge_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wtable::piece &out) {
+    hipStream_t st = ctx->stream;
+    out.n = 0;
+    if (!n) return MF_OK;
+    const int hb = 2 * k - 64;
+    mf_buf<uint64_t> k0, k1, i0, i1;
+    MF_TRY(k0.alloc(ctx, n)); MF_TRY(k1.alloc(ctx, n)); MF_TRY(i0.alloc(ctx, n)); MF_TRY(i1.alloc(ctx, n));
+    k_wio_iota<<<wio_grid(n), 256, 0, st>>>(i0.p, n);
+    MF_TRY(mf_sort_u64_u64(ctx, lo, i0.p, n, 64, k1.p, i1.p));                             // (lo', idx') in (k1, i1)
+    if (hb) {
+        k_wio_gather64<<<wio_grid(n), 256, 0, st>>>(i1.p, hi, n, k0.p);                    // hi' in k0
+        MF_TRY(mf_sort_u64_u64(ctx, k0.p, i1.p, n, hb, k1.p, i0.p));                       // (hi'', idx'') in (k1, i0)
+    } else i0.swap(i1);                                                                    // (k = 32: every high word is 0)
+    mf_buf<uint64_t> slo; mf_buf<uint16_t> scnt;
+    MF_TRY(slo.alloc(ctx, n)); MF_TRY(scnt.alloc(ctx, n));
+    k_wio_gather_pair<<<wio_grid(n), 256, 0, st>>>(i0.p, lo, cnt, n, slo.p, scnt.p);
+    const uint64_t *shi = k1.p;
+    if (!hb) { MF_HIP(hipMemsetAsync(k1.p, 0, n * 8, st)); }
+    mf_buf<uint32_t> flag; mf_buf<uint64_t> idx, tot;
+    MF_TRY(flag.alloc(ctx, n)); MF_TRY(idx.alloc(ctx, n + 1)); MF_TRY(tot.alloc(ctx, 1));
+    k_wio_heads<<<wio_grid(n), 256, 0, st>>>(shi, slo.p, n, flag.p);
+    MF_TRY(mf_scan<1>(ctx, flag.p, idx.p, n, tot.p));
+    uint64_t nd = 0;
+    MF_HIP(hipMemcpyAsync(&nd, tot.p, 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipStreamSynchronize(st));
+    MF_TRY(out.hi.alloc(ctx, nd)); MF_TRY(out.lo.alloc(ctx, nd)); MF_TRY(out.cnt.alloc(ctx, nd));
+    k_wio_sum_runs<<<wio_grid(n), 256, 0, st>>>(shi, slo.p, scnt.p, flag.p, idx.p, n, out.hi.p, out.lo.p, out.cnt.p);
+    MF_HIP(hipStreamSynchronize(st));
+    out.n = nd;
+    return MF_OK;
+}
 static const char *wbad_text(uint32_t rule) {
     switch (rule) {
         case WBAD_RANGE: return "the k-mer is not below 4^k";
@@ -282,36 +316,10 @@ extern "C" int mf_wtable_load_kmers(mf_ctx *ctx, const char *const *files, int n
         MF_TRY(mf_wide_compact(ctx, piece->hi.p, piece->lo.p, piece->cnt.p, total, freq_threshold, *kept));
         piece = std::move(kept);
     }
-    // several files (seq-builder): ascending order over all of them by two stable passes -- the low word, then the high word's 2k - 64 bits --
-    // that carry the entry's index, then the saturating sum of every run of equal k-mers
+    // several files (seq-builder): ascending order over all of them, the counts of equal k-mers added up
     if (nfiles > 1 && piece->n) {
-        const uint64_t n = piece->n;
-        const int hb = 2 * k - 64;
-        mf_buf<uint64_t> k0, k1, i0, i1;
-        MF_TRY(k0.alloc(ctx, n)); MF_TRY(k1.alloc(ctx, n)); MF_TRY(i0.alloc(ctx, n)); MF_TRY(i1.alloc(ctx, n));
-        k_wio_iota<<<wio_grid(n), 256, 0, st>>>(i0.p, n);
-        MF_TRY(mf_sort_u64_u64(ctx, piece->lo.p, i0.p, n, 64, k1.p, i1.p));               // (lo', idx') in (k1, i1)
-        if (hb) {
-            k_wio_gather64<<<wio_grid(n), 256, 0, st>>>(i1.p, piece->hi.p, n, k0.p);       // hi' in k0
-            MF_TRY(mf_sort_u64_u64(ctx, k0.p, i1.p, n, hb, k1.p, i0.p));                   // (hi'', idx'') in (k1, i0)
-        } else i0.swap(i1);                                                                // (k = 32: every high word is 0)
-        mf_buf<uint64_t> slo; mf_buf<uint16_t> scnt;
-        MF_TRY(slo.alloc(ctx, n)); MF_TRY(scnt.alloc(ctx, n));
-        k_wio_gather_pair<<<wio_grid(n), 256, 0, st>>>(i0.p, piece->lo.p, piece->cnt.p, n, slo.p, scnt.p);
-        const uint64_t *shi = k1.p;
-        if (!hb) { MF_HIP(hipMemsetAsync(k1.p, 0, n * 8, st)); }
-        mf_buf<uint32_t> flag; mf_buf<uint64_t> idx, tot;
-        MF_TRY(flag.alloc(ctx, n)); MF_TRY(idx.alloc(ctx, n + 1)); MF_TRY(tot.alloc(ctx, 1));
-        k_wio_heads<<<wio_grid(n), 256, 0, st>>>(shi, slo.p, n, flag.p);
-        MF_TRY(mf_scan<1>(ctx, flag.p, idx.p, n, tot.p));
-        uint64_t nd = 0;
-        MF_HIP(hipMemcpyAsync(&nd, tot.p, 8, hipMemcpyDeviceToHost, st));
-        MF_HIP(hipStreamSynchronize(st));
         auto sum = std::make_unique<mf_wtable::piece>();
-        MF_TRY(sum->hi.alloc(ctx, nd)); MF_TRY(sum->lo.alloc(ctx, nd)); MF_TRY(sum->cnt.alloc(ctx, nd));
-        k_wio_sum_runs<<<wio_grid(n), 256, 0, st>>>(shi, slo.p, scnt.p, flag.p, idx.p, n, sum->hi.p, sum->lo.p, sum->cnt.p);
-        MF_HIP(hipStreamSynchronize(st));
-        sum->n = nd;
+        MF_TRY(mf_wide_merge_runs(ctx, k, piece->hi.p, piece->lo.p, piece->cnt.p, piece->n, *sum));
         piece = std::move(sum);
     }
     auto t = std::make_unique<mf_wtable>();

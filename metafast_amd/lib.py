@@ -56,6 +56,8 @@ _SIGS = {
     "mf_wcomps_write": (i32, [vp, cp, cp]),
     "mf_wcomps_load": (i32, [vp, cp, i32, pvp]),
     "mf_features_wide": (i32, [vp, cp, cp, i32, i32, cp, cp]),
+    "mf_wcomps_unitigs_device": (i32, [vp, vp, i32, pvp]),
+    "mf_comp2seq_wide": (i32, [vp, cp, i32, i32, cp, pu64, pu64]),
     "mf_comm_create_local": (i32, [vp, i32, vp]),
     "mf_comm_rccl_id": (i32, [vp]),
     "mf_comm_create_rccl": (i32, [vp, vp, i32, i32, pvp]),
@@ -505,6 +507,19 @@ class Context:
         """File form: kmers_fasta/, kmer-counter-many/{kmers,stats}/, seq-builder-many/sequences/ under out_dir -> (file sets, sequences)"""
         nf, ns = C.c_uint64(), C.c_uint64()
         _check(lib().mf_comp2seq(self.h, os.fsencode(components_bin), k, 1 if split else 0, os.fsencode(out_dir), C.byref(nf), C.byref(ns)))
+        return nf.value, ns.value
+
+    def wcomps_unitigs(self, wcomps, split=True):
+        """NO-REFERENCE EXTENSION, 32 <= k <= 63 (mf_wcomp2seq.hip): comps_unitigs on WideComps (they know their k) -> Seqs;
+        Seqs.components() gives the component index of every sequence in export order (all 0 without split)"""
+        s = C.c_void_p()
+        _check(lib().mf_wcomps_unitigs_device(self.h, wcomps.h, 1 if split else 0, C.byref(s)))
+        return Seqs(self, s)
+
+    def comp2seq_wide(self, components_bin, k, out_dir, split=False):
+        """NO-REFERENCE EXTENSION: comp2seq's file form on a wide components.bin (wide .kmers.bin records) -> (file sets, sequences)"""
+        nf, ns = C.c_uint64(), C.c_uint64()
+        _check(lib().mf_comp2seq_wide(self.h, os.fsencode(components_bin), k, 1 if split else 0, os.fsencode(out_dir), C.byref(nf), C.byref(ns)))
         return nf.value, ns.value
 
     # ---- comp2graph ----
