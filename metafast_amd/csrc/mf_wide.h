@@ -29,7 +29,9 @@ struct mf_windex_view { const unsigned long long *slots; uint64_t mask; const ui
 // the count on the record path (mf_wskm.hip): 0 = *t filled, 1 = not an input for it (the caller counts the old way), < 0 = error
 int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_read_len, int threshold,
                       const uint32_t *vmask, uint64_t n_words, mf_wtable *t);
-int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *src_lo, const uint16_t *src_cnt, uint64_t nk, mf_wtable::piece *pc);
+// route (may be nullptr; for the tests, mf_debug_wide_order): [0] the entries that stood in runs of more than WO_RUN equal leading bits (0 where the leading-bits
+// route was not tried), [1] 1 = the leading-bits route was kept, 0 = all bits of everything were sorted -- nothing is launched or copied for it
+int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *src_lo, const uint16_t *src_cnt, uint64_t nk, mf_wtable::piece *pc, uint64_t *route = nullptr);
 int mf_wtable_ensure_ascending(mf_wtable *t);             // (drops an index built over the other order)
 int mf_wtable_flatten(mf_wtable *t);                      // all pieces into one (no-op for <= 1 piece)
 int mf_wtable_ensure_index(mf_wtable *t);                 // flatten + index

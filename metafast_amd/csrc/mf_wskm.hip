@@ -470,8 +470,9 @@ __global__ void k_wskm_scatter_side(const uint32_t *__restrict__ pos, const uint
 }
 
 // nk distinct k-mers (src_hi, src_lo, src_cnt) in any order -> *pc: ascending (high, low)
-int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *src_lo, const uint16_t *src_cnt, uint64_t nk, mf_wtable::piece *pc) {
+int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *src_lo, const uint16_t *src_cnt, uint64_t nk, mf_wtable::piece *pc, uint64_t *route) {
     hipStream_t st = ctx->stream;
+    if (route) route[0] = route[1] = 0;
     MF_TRY(pc->hi.alloc(ctx, nk)); MF_TRY(pc->lo.alloc(ctx, nk)); MF_TRY(pc->cnt.alloc(ctx, nk));
     if (nk) {
         mf_ktimer tm(ctx, "k_wskm_order");
@@ -516,6 +517,7 @@ int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *sr
             MF_HIP(hipMemcpyAsync(&ns, side_n.p, 4, hipMemcpyDeviceToHost, st));
             MF_HIP(hipStreamSynchronize(st));
             l1.reset(); j1.reset();
+            if (route) route[0] = ns;
             if ((uint64_t)ns <= scap) {
                 placed = true;
                 if (ns) {
@@ -531,9 +533,30 @@ int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *sr
                 if (ctx->opt_verbose) fprintf(stderr, "[mf] count_wide (records): %u of %llu kept k-mers stand in runs of more than %d with the same leading 16 bases (all their bits are sorted)\n", ns, (unsigned long long)nk, WO_RUN);
             }
         }
+        if (route) route[1] = placed ? 1 : 0;
         if (!placed) MF_TRY(full_order(src_hi, src_lo, src_cnt, nk, pc->hi.p, pc->lo.p, pc->cnt.p));
     }
     pc->n = nk;
+    return MF_OK;
+}
+
+// What mf_debug_wskm_records (the end of this file) takes out of a count: every stage's output as the next stage finds it.  ctx->wskm_snap is null in
+// production: nothing below is launched, allocated, copied or waited for then.
+struct mf_wskm_snap {
+    bool entered = false;                  // mf_count_wide_skm ran
+    const char *back = nullptr;            // ... and handed the input back (return 1): why
+    int pbits = 0, scan_attempts = 0;
+    bool packed = false;                   // k_wskm_pack ran: k_wskm_count read `pack` one after the other, not `rec` through `order`
+    uint64_t n_occ = 0, n_rec = 0, n_units = 0, first_room = 0;
+    std::vector<uint32_t> rec, part, order, pack;      // rec / pack: 8 words per record
+    std::vector<uint64_t> poff, uoff, hi, lo;          // poff [2^pbits + 1], uoff [n_units + 1]; hi / lo / cnt: the count's output in unit order
+    std::vector<uint16_t> cnt;
+    unsigned long long counters[4] = {0, 0, 0, 0};
+};
+#define WS_SNAP_MAX_OCC (1ull << 24)
+template <typename T> static int ws_snap_copy(mf_ctx *ctx, std::vector<T> &dst, const void *src, size_t n) {
+    dst.resize(n);
+    if (n) { MF_HIP(hipMemcpyAsync(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream)); MF_HIP(hipStreamSynchronize(ctx->stream)); }
     return MF_OK;
 }
 
@@ -541,16 +564,21 @@ int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *sr
 int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_read_len, int threshold,
                       const uint32_t *vmask, uint64_t n_words, mf_wtable *t) {
     hipStream_t st = ctx->stream;
+    mf_wskm_snap *snap = ctx->wskm_snap;                 // (tests: mf_debug_wskm_records)
+    if (snap) snap->entered = true;
+    auto back = [&](const char *why) { if (snap) snap->back = why; return 1; };
     mf_buf<unsigned long long> ctr; MF_TRY(ctr.alloc(ctx, 8));
     MF_HIP(hipMemsetAsync(ctr.p, 0, 64, st));
     k_wskm_nocc<<<wsgrid(n_reads), 256, 0, st>>>(d_offsets, n_reads, k, min_read_len, &ctr.p[4]);
     unsigned long long n_occ = 0;
     MF_HIP(hipMemcpyAsync(&n_occ, &ctr.p[4], 8, hipMemcpyDeviceToHost, st));
     MF_HIP(hipStreamSynchronize(st));
-    if (n_occ < (uint64_t)std::max<int64_t>(1, ctx->opt_wide_skm_min)) return 1;
+    if (n_occ < (uint64_t)std::max<int64_t>(1, ctx->opt_wide_skm_min)) return back("fewer k-mer occurrences than option wide_skm_min");
+    if (snap && n_occ > WS_SNAP_MAX_OCC)
+        return mf_set_error("mf_debug_wskm_records: %llu k-mer occurrences (every stage is copied to the host: %llu at most)", n_occ, (unsigned long long)WS_SNAP_MAX_OCC);
     // (the kept entries are ordered with 32-bit entry numbers: an UNCUT table of a sample this large -- 4.1e9 distinct 63-mers at 200 M reads -- goes
     // the old way, which leaves it in per-pass pieces; with the cut of the k-mer counter, count > b, a twentieth is kept)
-    if (threshold < 1 && n_occ >= 3000000000ull) return 1;
+    if (threshold < 1 && n_occ >= 3000000000ull) return back("an uncut table of 3e9 occurrences or more");
     const uint64_t n_tiles = (n_words * 32 + WS_TILE - 1) / WS_TILE;
     // partitions: units of about 4000 k-mer occurrences (a unit whose distinct k-mers do not fit the LDS table is counted in passes)
     int pbits = 0;
@@ -562,8 +590,10 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
     mf_buf<wskm_rec> recs; mf_buf<uint32_t> part;
     unsigned long long n_rec = 0;
     const unsigned sgrid = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 4);
+    if (snap) { snap->n_occ = n_occ; snap->pbits = pbits; snap->first_room = cap; }
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (recs.alloc(ctx, cap) != MF_OK || part.alloc(ctx, cap) != MF_OK) { (void)hipGetLastError(); return 1; }
+        if (recs.alloc(ctx, cap) != MF_OK || part.alloc(ctx, cap) != MF_OK) { (void)hipGetLastError(); return back("no memory for the records"); }
+        if (snap) snap->scan_attempts = attempt + 1;
         MF_HIP(hipMemsetAsync(&ctr.p[5], 0, 8, st));
         {
             mf_ktimer tm(ctx, "k_wskm_scan");
@@ -576,7 +606,8 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
         recs.reset(); part.reset();
         cap = n_rec + 64;                                                        // (the cursor went on counting: the exact number)
     }
-    if (n_rec >= (1ull << 32)) return 1;                                         // (the pair sort takes 2^32 entries; the old way cuts its passes by class)
+    if (n_rec >= (1ull << 32)) return back("2^32 records or more");              // (the pair sort takes 2^32 entries; the old way cuts its passes by class)
+    if (snap) { snap->n_rec = n_rec; MF_TRY(ws_snap_copy(ctx, snap->rec, recs.p, (size_t)n_rec * 8)); MF_TRY(ws_snap_copy(ctx, snap->part, part.p, (size_t)n_rec)); }
     t->n_occ = n_occ;
     if (!n_rec) { t->n = 0; t->n_all = 0; t->cut_thr = threshold >= 1 ? threshold : 0; return MF_OK; }
     // by partition
@@ -585,13 +616,14 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
     mf_buf<uint32_t> order; mf_buf<uint64_t> uoff;
     {
         mf_buf<uint32_t> idx, part_s;
-        if (idx.alloc(ctx, n_rec) != MF_OK || part_s.alloc(ctx, n_rec) != MF_OK || order.alloc(ctx, n_rec) != MF_OK) { (void)hipGetLastError(); return 1; }
+        if (idx.alloc(ctx, n_rec) != MF_OK || part_s.alloc(ctx, n_rec) != MF_OK || order.alloc(ctx, n_rec) != MF_OK) { (void)hipGetLastError(); return back("no memory for the records' order"); }
         mf_buf<uint64_t> poff;
         MF_TRY(poff.alloc(ctx, (size_t)n_parts + 1));
         k_wskm_iota<<<wsgrid(n_rec), 256, 0, st>>>(idx.p, n_rec);
         if (pbits) MF_TRY(mf_sort_u32_pairs(ctx, part.p, idx.p, n_rec, pbits, part_s.p, order.p));
         else { MF_HIP(hipMemcpyAsync(order.p, idx.p, n_rec * 4, hipMemcpyDeviceToDevice, st)); MF_HIP(hipMemcpyAsync(part_s.p, part.p, n_rec * 4, hipMemcpyDeviceToDevice, st)); }
         k_wskm_offsets<<<(n_parts + 1 + 255) / 256, 256, 0, st>>>(part_s.p, n_rec, n_parts, poff.p);
+        if (snap) { MF_TRY(ws_snap_copy(ctx, snap->order, order.p, (size_t)n_rec)); MF_TRY(ws_snap_copy(ctx, snap->poff, poff.p, (size_t)n_parts + 1)); }
         if (ctx->opt_wide_skm_merge && pbits) {
             // (records per unit: the unit's k-mer occurrences / the k-mers a record holds)
             const uint64_t G = std::max<uint64_t>(8, (uint64_t)((double)std::max<int64_t>(ctx->opt_wide_skm_unit, 64) * (double)n_rec / (double)n_occ));
@@ -603,6 +635,7 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
             }
         }
         if (!uoff.p) uoff.swap(poff);
+        if (snap) { snap->n_units = n_units; MF_TRY(ws_snap_copy(ctx, snap->uoff, uoff.p, (size_t)n_units + 1)); }
         if (ctx->opt_verbose >= 2) {                      // the units' sizes in records: how heavy the heavy ones are
             std::vector<uint64_t> h((size_t)n_units + 1);
             MF_HIP(hipMemcpyAsync(h.data(), uoff.p, ((size_t)n_units + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -629,6 +662,7 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
                 k_wskm_pack<<<(unsigned)((n_rec + 1023) / 1024), 1024, 0, st>>>(recs.p, order.p, n_rec, ctx->opt_wide_skm_pack == 1 ? 1u : 0u, packed.p);
             }
             MF_HIP(hipStreamSynchronize(st));
+            if (snap) { snap->packed = true; MF_TRY(ws_snap_copy(ctx, snap->pack, packed.p, (size_t)n_rec * 8)); }
             recs.swap(packed); packed.reset(); order.reset();
         } else (void)hipGetLastError();
     }
@@ -640,7 +674,7 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
     const size_t wc_lds = (size_t)WC_SLOTS * 20 + (size_t)1024 * 32 + (size_t)1025 * 4;
     MF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_wskm_count), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wc_lds));
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (ohi.alloc(ctx, ocap) != MF_OK || olo.alloc(ctx, ocap) != MF_OK || ocnt.alloc(ctx, ocap) != MF_OK) { (void)hipGetLastError(); return 1; }
+        if (ohi.alloc(ctx, ocap) != MF_OK || olo.alloc(ctx, ocap) != MF_OK || ocnt.alloc(ctx, ocap) != MF_OK) { (void)hipGetLastError(); return back("no memory for the kept entries"); }
         MF_HIP(hipMemsetAsync(ctr.p, 0, 32, st));
         {
             mf_ktimer tm(ctx, "k_wskm_count");
@@ -658,7 +692,11 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
     const uint64_t nk = res[0];
     if (ctx->opt_verbose) fprintf(stderr, "[mf] count_wide (records): %llu k-mers in %llu records (%.1f per record), %u units, %llu counted in several passes; %llu distinct, %llu kept\n", n_occ, n_rec,
                                   (double)n_occ / (double)n_rec, n_units, res[2], res[1], (unsigned long long)nk);
-    if (nk >= (1ull << 32)) { t->n_occ = 0; return 1; }                         // (more kept k-mers than entry numbers: the old way)
+    if (nk >= (1ull << 32)) { t->n_occ = 0; return back("2^32 kept k-mers or more"); }      // (more kept k-mers than entry numbers: the old way)
+    if (snap) {
+        for (int i = 0; i < 4; i++) snap->counters[i] = res[i];
+        MF_TRY(ws_snap_copy(ctx, snap->hi, ohi.p, (size_t)nk)); MF_TRY(ws_snap_copy(ctx, snap->lo, olo.p, (size_t)nk)); MF_TRY(ws_snap_copy(ctx, snap->cnt, ocnt.p, (size_t)nk));
+    }
     // The table stays in the order of the counting units (option wide_skm_lazy_order, the default) until somebody needs it ascending -- an export, the
     // pieces' views, the component cutter (mf_wtable_ensure_ascending): unitigs and features find k-mers through the index and compare k-mers, not places,
     // and ordering 7.5e8 kept entries is 0.2 s of the 200 M-read sample's 1.4 s.
@@ -675,5 +713,84 @@ int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_off
     if (nk) t->pieces.push_back(std::move(pc));
     t->n = nk; t->n_all = res[1];
     t->cut_thr = threshold >= 1 ? threshold : 0;
+    return MF_OK;
+}
+
+// =============================================================================================
+// Debugging aids of tests/test_wskm_stages_gpu.py (not part of the C-ABI).
+//   mf_debug_wskm_records  the call is mf_count_wide_device_above's own (the mask kernels of mf_wide.hip, then mf_count_wide_skm with the context's options)
+//                          with ctx->wskm_snap set, which makes mf_count_wide_skm copy every stage's output to the host on its way.  A call that does not
+//                          reach the record path (option wide_skm), an input the path hands back, and one of more than 2^24 occurrences are errors.
+//                          -> *out: the snapshot (mf_debug_wskm_free)
+//   mf_debug_wskm_info     info[0..13) = pbits, occurrences, records, units, partitions, k_wskm_pack ran (0 / 1), scans made (1 / 2), the first scan's record
+//                          room, counters[0..4) of k_wskm_count, the entries it wrote
+//   mf_debug_wskm_copy     rec [8 records] + part [records] as k_wskm_scan wrote them, order [records], poff [partitions + 1], uoff [units + 1], pack [8 records]
+//                          (k_wskm_pack's output, if it ran), hi / lo / cnt [entries] as k_wskm_count wrote them (unit order, nothing ordered); null: not wanted
+//   mf_debug_wide_order    n distinct entries from the host, in any order, through mf_wide_order -> ascending; route[0] = the entries set aside, route[1] = the
+//                          leading-bits route was kept (1) or all bits of everything were sorted (0)
+// =============================================================================================
+extern "C" void mf_debug_wskm_free(mf_wskm_snap *s) { delete s; }
+extern "C" int mf_debug_wskm_records(mf_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_len, int threshold,
+                                     mf_wskm_snap **out) {
+    if (!ctx || !out) return mf_set_error("mf_debug_wskm_records: NULL argument");
+    *out = nullptr;
+    std::unique_ptr<mf_wskm_snap> S(new mf_wskm_snap());
+    mf_wtable *t = nullptr;
+    ctx->wskm_snap = S.get();
+    const int rc = mf_count_wide_device_above(ctx, d_bases, d_offsets, n_reads, n_bases, k, min_len, threshold, &t, nullptr);
+    ctx->wskm_snap = nullptr;
+    if (rc < 0) return rc;
+    if (t) mf_wtable_destroy(t);
+    if (!S->entered) return mf_set_error("mf_debug_wskm_records: option wide_skm = %d, min_len = %d: the call does not reach the record path", (int)ctx->opt_wide_skm, min_len);
+    if (S->back) return mf_set_error("mf_debug_wskm_records: the record path handed the input back (%s)", S->back);
+    *out = S.release();
+    return MF_OK;
+}
+extern "C" int mf_debug_wskm_info(const mf_wskm_snap *s, uint64_t *info) {
+    if (!s || !info) return mf_set_error("mf_debug_wskm_info: NULL argument");
+    const uint64_t v[13] = {(uint64_t)s->pbits, s->n_occ, s->n_rec, s->n_units, s->poff.empty() ? 0 : s->poff.size() - 1, (uint64_t)s->packed, (uint64_t)s->scan_attempts, s->first_room,
+                            s->counters[0], s->counters[1], s->counters[2], s->counters[3], s->hi.size()};
+    std::copy(v, v + 13, info);
+    return MF_OK;
+}
+extern "C" int mf_debug_wskm_copy(const mf_wskm_snap *s, uint32_t *rec, uint32_t *part, uint32_t *order, uint64_t *poff, uint64_t *uoff, uint32_t *pack, uint64_t *hi, uint64_t *lo,
+                                  uint16_t *cnt) {
+    if (!s) return mf_set_error("mf_debug_wskm_copy: NULL argument");
+    if (rec) std::copy(s->rec.begin(), s->rec.end(), rec);
+    if (part) std::copy(s->part.begin(), s->part.end(), part);
+    if (order) std::copy(s->order.begin(), s->order.end(), order);
+    if (poff) std::copy(s->poff.begin(), s->poff.end(), poff);
+    if (uoff) std::copy(s->uoff.begin(), s->uoff.end(), uoff);
+    if (pack) std::copy(s->pack.begin(), s->pack.end(), pack);
+    if (hi) std::copy(s->hi.begin(), s->hi.end(), hi);
+    if (lo) std::copy(s->lo.begin(), s->lo.end(), lo);
+    if (cnt) std::copy(s->cnt.begin(), s->cnt.end(), cnt);
+    return MF_OK;
+}
+extern "C" int mf_debug_wide_order(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, uint64_t *hi_out, uint64_t *lo_out, uint16_t *cnt_out,
+                                   uint64_t *n_aside, int *placed) {
+    if (!ctx || (n && (!hi || !lo || !cnt || !hi_out || !lo_out || !cnt_out))) return mf_set_error("mf_debug_wide_order: NULL argument");
+    if (k < 32 || k > 63) return mf_set_error("mf_debug_wide_order: k = %d (32 .. 63)", k);
+    if (n >= (1ull << 32)) return mf_set_error("mf_debug_wide_order: %llu entries (fewer than 2^32 are supported)", (unsigned long long)n);
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    mf_buf<uint64_t> dhi, dlo; mf_buf<uint16_t> dcnt;
+    MF_TRY(dhi.alloc(ctx, n)); MF_TRY(dlo.alloc(ctx, n)); MF_TRY(dcnt.alloc(ctx, n));
+    if (n) {
+        MF_HIP(hipMemcpyAsync(dhi.p, hi, n * 8, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(dlo.p, lo, n * 8, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(dcnt.p, cnt, n * 2, hipMemcpyHostToDevice, st));
+    }
+    mf_wtable::piece pc;
+    uint64_t route[2] = {0, 0};
+    MF_TRY(mf_wide_order(ctx, k, dhi.p, dlo.p, dcnt.p, n, &pc, route));
+    if (n) {
+        MF_HIP(hipMemcpyAsync(hi_out, pc.hi.p, n * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(lo_out, pc.lo.p, n * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(cnt_out, pc.cnt.p, n * 2, hipMemcpyDeviceToHost, st));
+    }
+    MF_HIP(hipStreamSynchronize(st));
+    if (n_aside) *n_aside = route[0];
+    if (placed) *placed = (int)route[1];
     return MF_OK;
 }

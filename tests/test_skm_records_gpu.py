@@ -21,8 +21,8 @@ counter.  Every comparison is bit-exact.  Every case asserts the plan it is abou
 and the multiset of whole records of every partition against the reference: the exact form wherever level 1 has exact ranges or the scatter
 is not the FAST one, the one-pass form (runs go on across word borders, skm_ref.Scan.one_pass) otherwise.
 
-Left out: the RECORDS of level 1 in front of a split (only its directory is looked at); the streamed level 1 (mf_stream.hip); the 32-byte
-records of the wide path (mf_wskm.hip)."""
+Left out: the RECORDS of level 1 in front of a split (only its directory is looked at); the streamed level 1 (mf_stream.hip).  The 32-byte
+records of the wide path (mf_wskm.hip) have tests/test_wskm_stages_gpu.py."""
 import ctypes as C
 
 import numpy as np

@@ -1,6 +1,7 @@
 """NO-REFERENCE EXTENSION: `metafast.sh --wide-kmers -k K` (32 <= K <= 63) from FASTA files to the distance matrix, against
 oracle.run_pipeline_wide on the same reads and the numpy restatement of the wide file formats (tests/wide_files_ref.py)."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -176,7 +177,9 @@ def test_the_flag_changes_nothing_up_to_k31_and_is_needed_above(tmp_path):
     _run([*common, "-w", tmp_path / "without"], tmp_path)
     a, b = _data_files(str(tmp_path / "with")), _data_files(str(tmp_path / "without"))
     assert a == b and len(a) >= 18
-    strip = lambda p: open(p).read().replace(str(tmp_path / "without"), "W").replace(str(tmp_path / "with"), "W")
+    # (the two runs start one after the other: a file name that carries a run's start time, yyyy.MM.dd_HH.mm.ss, differs whenever a second ticks between them)
+    stamp = re.compile(r"\d{4}\.\d\d\.\d\d_\d\d\.\d\d\.\d\d")
+    strip = lambda p: stamp.sub("TS", open(p).read().replace(str(tmp_path / "without"), "W").replace(str(tmp_path / "with"), "W"))
     for sub in ("", "kmer-counter-many", "seq-builder-many", "component-cutter", "features-calculator"):
         assert strip(tmp_path / "with" / sub / "in.properties") == strip(tmp_path / "without" / sub / "in.properties"), sub
     # without the flag k = 32 dies with the reference's message, for the builder and for a single tool
