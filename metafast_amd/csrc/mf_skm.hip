@@ -309,10 +309,10 @@ __global__ __launch_bounds__(1024) void k_skm_hist(const uint8_t *__restrict__ b
 // reserve a slot, write it, commit; the 4th committer's line is written to HBM by four lanes with one store instruction
 // =============================================================================================
 struct skm_stage {
-    skm_rec *line;     // [nd][4] + 64 dummy slots (one per lane)
+    skm_rec *line;     // [nd][4]
     uint64_t *cur;     // [nd] next record index of this workgroup's range of digit d
     uint64_t *q_pos;   // [16 waves][SKM_QCAP]
-    uint32_t *ctr;     // [nd] low 16 = reserved, high 16 = committed; + 64 dummy counters
+    uint32_t *ctr;     // [nd] low 16 = reserved, high 16 = committed
     uint32_t *q_d;     // [16 waves][SKM_QCAP]
     int nd;
 };
@@ -320,24 +320,59 @@ __device__ __forceinline__ skm_stage skm_stage_carve(unsigned char *smem, int nd
     skm_stage L;
     L.nd = nd;
     L.line = reinterpret_cast<skm_rec *>(smem);
-    L.cur = reinterpret_cast<uint64_t *>(L.line + (size_t)nd * SKM_LINE + 64);
+    L.cur = reinterpret_cast<uint64_t *>(L.line + (size_t)nd * SKM_LINE);
     L.q_pos = L.cur + nd;
     L.ctr = reinterpret_cast<uint32_t *>(L.q_pos + 16 * SKM_QCAP);
-    L.q_d = L.ctr + nd + 64;
+    L.q_d = L.ctr + nd;
     return L;
 }
 __host__ __device__ static inline size_t skm_stage_bytes(int nd) {
-    return ((size_t)nd * SKM_LINE + 64) * 16 + (size_t)nd * 8 + 16 * SKM_QCAP * 8 + ((size_t)nd + 64) * 4 + 16 * SKM_QCAP * 4;
+    return (size_t)nd * SKM_LINE * 16 + (size_t)nd * 8 + 16 * SKM_QCAP * 8 + (size_t)nd * 4 + 16 * SKM_QCAP * 4;
 }
-// four 16-byte stores, then four returning adds (the commits); LDS operations of one wave execute in order
-__device__ __forceinline__ void skm_lds_write4_add_rtn4(const uint32_t (&wa)[4], const skm_v4 (&wv)[4], const uint32_t (&a)[4],
-                                                        const uint32_t (&inc)[4], uint32_t (&old)[4]) {
-    asm volatile("ds_write_b128 %4, %8\n\tds_write_b128 %5, %9\n\tds_write_b128 %6, %10\n\tds_write_b128 %7, %11\n\t"
-                 "ds_add_rtn_u32 %0, %12, %16\n\tds_add_rtn_u32 %1, %13, %17\n\tds_add_rtn_u32 %2, %14, %18\n\t"
-                 "ds_add_rtn_u32 %3, %15, %19\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&v"(old[0]), "=&v"(old[1]), "=&v"(old[2]), "=&v"(old[3])
-                 : "v"(wa[0]), "v"(wa[1]), "v"(wa[2]), "v"(wa[3]), "v"(wv[0]), "v"(wv[1]), "v"(wv[2]), "v"(wv[3]),
-                   "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(inc[0]), "v"(inc[1]), "v"(inc[2]), "v"(inc[3])
+// The four-wide LDS steps of the staging protocol, each operation under a lane mask of its own: exec is set from the mask (a ballot, so
+// a subset of the lanes that are active here) in front of the operation and put back behind the last one, and lanes outside the mask
+// touch no LDS -- they used to run the whole protocol against a counter and a slot of their own.  An operation whose mask is empty is
+// issued with exec = 0 and does nothing.  A result register keeps its old contents in the lanes outside its mask: the caller reads it
+// under the same condition only.  (Inline asm for the reason given in mf_count_dev.h: written as `if`s these become a branch and a
+// wait per operation.)
+__device__ __forceinline__ void skm_lds_read4_if(const unsigned long long (&m)[4], const uint32_t (&a)[4], uint32_t (&v)[4]) {
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %4, exec\n\t"
+                 "s_mov_b64 exec, %5\n\tds_read_b32 %0, %9\n\t"
+                 "s_mov_b64 exec, %6\n\tds_read_b32 %1, %10\n\t"
+                 "s_mov_b64 exec, %7\n\tds_read_b32 %2, %11\n\t"
+                 "s_mov_b64 exec, %8\n\tds_read_b32 %3, %12\n\t"
+                 "s_mov_b64 exec, %4\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&s"(sv)
+                 : "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3])
+                 : "memory");
+}
+__device__ __forceinline__ void skm_lds_add_rtn4_if(const unsigned long long (&m)[4], const uint32_t (&a)[4], uint32_t inc, uint32_t (&old)[4]) {
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %4, exec\n\t"
+                 "s_mov_b64 exec, %5\n\tds_add_rtn_u32 %0, %9, %13\n\t"
+                 "s_mov_b64 exec, %6\n\tds_add_rtn_u32 %1, %10, %13\n\t"
+                 "s_mov_b64 exec, %7\n\tds_add_rtn_u32 %2, %11, %13\n\t"
+                 "s_mov_b64 exec, %8\n\tds_add_rtn_u32 %3, %12, %13\n\t"
+                 "s_mov_b64 exec, %4\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(old[0]), "=&v"(old[1]), "=&v"(old[2]), "=&v"(old[3]), "=&s"(sv)
+                 : "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(inc)
+                 : "memory");
+}
+// a 16-byte store and the returning add that commits it, pair by pair.  LDS operations of one wave execute in order and both halves of
+// a pair run under the same mask, so every lane's store is in front of its own commit -- all a commit vouches for is its own slot
+__device__ __forceinline__ void skm_lds_write4_add_rtn4_if(const unsigned long long (&m)[4], const uint32_t (&wa)[4], const skm_v4 (&wv)[4],
+                                                           const uint32_t (&a)[4], uint32_t inc, uint32_t (&old)[4]) {
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %4, exec\n\t"
+                 "s_mov_b64 exec, %5\n\tds_write_b128 %9, %13\n\tds_add_rtn_u32 %0, %17, %21\n\t"
+                 "s_mov_b64 exec, %6\n\tds_write_b128 %10, %14\n\tds_add_rtn_u32 %1, %18, %21\n\t"
+                 "s_mov_b64 exec, %7\n\tds_write_b128 %11, %15\n\tds_add_rtn_u32 %2, %19, %21\n\t"
+                 "s_mov_b64 exec, %8\n\tds_write_b128 %12, %16\n\tds_add_rtn_u32 %3, %20, %21\n\t"
+                 "s_mov_b64 exec, %4\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(old[0]), "=&v"(old[1]), "=&v"(old[2]), "=&v"(old[3]), "=&s"(sv)
+                 : "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]), "v"(wa[0]), "v"(wa[1]), "v"(wa[2]), "v"(wa[3]),
+                   "v"(wv[0]), "v"(wv[1]), "v"(wv[2]), "v"(wv[3]), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(inc)
                  : "memory");
 }
 // DYN (one-pass level-1 scatter): a workgroup does not know its share of a digit in advance; it reserves the digit's region
@@ -368,47 +403,57 @@ __device__ __forceinline__ uint64_t skm_take_line(const skm_stage &L, uint32_t d
 template <bool DYN = false>
 __device__ __forceinline__ void skm_stage_insert(const skm_stage &L, skm_rec *__restrict__ out, const uint32_t (&d)[4],
                                                  const skm_rec (&rec)[4], bool (&pending)[4], const skm_dyn &Dy = skm_dyn()) {
+    // (d and rec of a lane that is not pending are never looked at: every LDS step below runs under the mask of the lanes it is for)
     const uint32_t ctr0 = mf_lds_addr(L.ctr), line0 = mf_lds_addr(L.line);
-    const uint32_t dummy_ctr = ctr0 + 4u * ((uint32_t)L.nd + (uint32_t)mf_lane());
-    const uint32_t dummy_slot = line0 + 16u * ((uint32_t)L.nd * SKM_LINE + (uint32_t)mf_lane());
     skm_v4 wv[4];
+    uint32_t ca[4], la[4];
 #pragma unroll
-    for (int b = 0; b < 4; b++) { wv[b].x = (uint32_t)rec[b].x; wv[b].y = (uint32_t)(rec[b].x >> 32); wv[b].z = (uint32_t)rec[b].y; wv[b].w = (uint32_t)(rec[b].y >> 32); }
+    for (int b = 0; b < 4; b++) {
+        wv[b].x = (uint32_t)rec[b].x; wv[b].y = (uint32_t)(rec[b].x >> 32); wv[b].z = (uint32_t)rec[b].y; wv[b].w = (uint32_t)(rec[b].y >> 32);
+        ca[b] = ctr0 + 4u * d[b];
+        la[b] = line0 + 16u * SKM_LINE * d[b];
+    }
     for (;;) {
-        bool any = false;
+        unsigned long long P[4], R[4], G[4];
 #pragma unroll
-        for (int b = 0; b < 4; b++) any |= pending[b];
-        if (__ballot(any) == 0ull) break;
-        uint32_t ca[4], w[4], inc[4], old[4], old2[4], wa[4];
+        for (int b = 0; b < 4; b++) P[b] = __ballot(pending[b]);
+        if ((P[0] | P[1] | P[2] | P[3]) == 0ull) break;
+        uint32_t w[4], old[4], old2[4], wa[4];
         bool got[4];
-#pragma unroll
-        for (int b = 0; b < 4; b++) ca[b] = pending[b] ? ctr0 + 4u * d[b] : dummy_ctr;
         // peek: is the line open?  The peek is what bounds the reserved half-word.  A reservation on a full line leaves a surplus there
         // that only the re-opening store wipes; with the peek a record adds to a full line at most once per re-opening (it saw the line
         // open), so the surplus stays below 4 x 1024.  Reserving blindly, a waiting lane would add once per turn of this loop for as long
         // as the line is closed -- up to 256 per wave and turn when one digit takes everything (copies of one read), while the closing
         // wave may be waiting for its chunk (a global atomic, thousands of cycles): 16 waves reach 65536, the carry enters the committed
         // half-word, and a line is written early or never.  So the peek stays.
-        mf_lds_read4(ca, w);
+        // Only pending lanes peek, only lanes that saw their line open reserve, and only lanes that got a slot write and commit.
+        skm_lds_read4_if(P, ca, w);
 #pragma unroll
-        for (int b = 0; b < 4; b++) inc[b] = (pending[b] && (w[b] & 0xFFFFu) < (uint32_t)SKM_LINE) ? 1u : 0u;
-        mf_lds_add_rtn4(ca, inc, old);                                           // reserve a slot
+        for (int b = 0; b < 4; b++) { got[b] = pending[b] && (w[b] & 0xFFFFu) < (uint32_t)SKM_LINE; R[b] = __ballot(got[b]); }
+        skm_lds_add_rtn4_if(R, ca, 1u, old);                                     // reserve a slot
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-            got[b] = inc[b] && (old[b] & 0xFFFFu) < (uint32_t)SKM_LINE;
-            wa[b] = got[b] ? line0 + 16u * (d[b] * SKM_LINE + (old[b] & 0xFFFFu)) : dummy_slot;
-            ca[b] = got[b] ? ctr0 + 4u * d[b] : dummy_ctr;
-            inc[b] = got[b] ? 0x10000u : 0u;
+            got[b] = got[b] && (old[b] & 0xFFFFu) < (uint32_t)SKM_LINE;
+            wa[b] = la[b] + 16u * (old[b] & (uint32_t)(SKM_LINE - 1));           // (got: the reserved half-word was below SKM_LINE)
+            G[b] = __ballot(got[b]);
         }
-        skm_lds_write4_add_rtn4(wa, wv, ca, inc, old2);                          // write the slot, commit
+        skm_lds_write4_add_rtn4_if(G, wa, wv, ca, 0x10000u, old2);               // write the slot, commit
         uint64_t *qpos = L.q_pos + (threadIdx.x >> 6) * SKM_QCAP;
         uint32_t *qd = L.q_d + (threadIdx.x >> 6) * SKM_QCAP;
         const uint64_t lt_mask = (1ull << mf_lane()) - 1ull;
+        bool fl4[4], anyfl = false;
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-            const bool fl = got[b] && (old2[b] >> 16) == (uint32_t)(SKM_LINE - 1);   // last committer of its line
-            const unsigned long long F = __ballot(fl);
+            fl4[b] = got[b] && (old2[b] >> 16) == (uint32_t)(SKM_LINE - 1);      // last committer of its line
+            anyfl |= fl4[b];
             if (got[b]) pending[b] = false;
+        }
+        // one ballot for the four flush blocks: a turn in which no line closed (the tail of a batch, a narrow slice) tests nothing else
+        if (__ballot(anyfl) == 0ull) continue;                  // (nothing above leaves an LDS operation in flight)
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const bool fl = fl4[b];
+            const unsigned long long F = __ballot(fl);
             if (F == 0ull) continue;
             const uint32_t n = (uint32_t)__popcll(F), qi = (uint32_t)__popcll(F & lt_mask);
             uint64_t mypos = 0;
@@ -441,7 +486,13 @@ __device__ __forceinline__ void skm_stage_flush_all(const skm_stage &L, skm_rec 
         const uint32_t c = L.ctr[d] >> 16;
         if (c) {
             const uint64_t pos = skm_take_line<DYN>(L, (uint32_t)d, Dy);
-            for (uint32_t s = 0; s < (uint32_t)SKM_LINE; s++) out[pos + s] = s < c ? L.line[d * SKM_LINE + s] : SENT;
+            // (the slot is read, then replaced: `s < c ? line : SENT` selects between two ADDRESSES and puts SENT on the stack -- 16 of
+            // the kernels' bytes of scratch)
+            for (uint32_t s = 0; s < (uint32_t)SKM_LINE; s++) {
+                skm_rec v = L.line[d * SKM_LINE + s];
+                if (s >= c) v = SENT;
+                out[pos + s] = v;
+            }
             L.ctr[d] = 0;
         }
         if (DYN) {
@@ -470,8 +521,8 @@ __global__ void k_skm_close_chunks(const unsigned long long *__restrict__ save, 
 // meant a second, nearly empty iteration for the whole wave (r02: ~580 of the kernel's 2120 instructions per word), and every
 // run slot paid a 41-instruction select tree for the run's minimizer hash (a register array cannot be indexed per lane).  Now:
 // every lane parks its word (bases, run starts, valid starts: 24 bytes) and writes one 8-byte descriptor per run -- the loop
-// is over the 32 POSITIONS, so the hash is a fixed register, and lanes without a run at that position write to a dummy
-// slot --; then lane l takes the runs l, l + 64, l + 128, l + 192 of the list: one four-wide iteration per 256 runs (237 on
+// is over the 32 POSITIONS, so the hash is a fixed register, and only the lanes with a run at that position write
+// (skm_runlist8) --; then lane l takes the runs l, l + 64, l + 128, l + 192 of the list: one four-wide iteration per 256 runs (237 on
 // average per batch).  Rare batches (a run longer than RMAX that must be cut, more runs than the list holds) take the per-lane loop.
 // RUNS GO ON ACROSS WORD BOUNDARIES here: a word used to start a new run whatever its first k-mer's minimizer -- a quarter of
 // all records began at a word boundary.  Now a lane whose first k-mer continues the previous lane's last run (same minimizer
@@ -479,7 +530,34 @@ __global__ void k_skm_close_chunks(const unsigned long long *__restrict__ save, 
 // k-mers; the rest of the head becomes a run of its own), and the lane that owns the run builds the record from its own 64
 // bases + the next lane's (parked) -- 1.75e9 -> ~1.35e9 records at 100 M reads: less to write, to split and to unpack.
 #define SKM_LCAP 384               // run descriptors per wave and batch
-#define SKM_FAST_WAVE_BYTES (64 * 16 + 64 * 8 + (SKM_LCAP + 1) * 8)
+#define SKM_FAST_WAVE_BYTES (64 * 16 + 64 * 8 + SKM_LCAP * 8)
+// Eight positions J0 .. J0 + 7 of the run list.  `c` holds the run starts not yet dealt with, bit-reversed (the next position in the top
+// bit); `at` is the lane's next free descriptor.  A position costs three VALU, one SALU and the LDS write: c + c shifts the position's
+// bit out as the carry of all 64 lanes (an SGPR pair, eight of them up front), exec is set from that pair, and the tag (lane << 5 | position), the
+// (hash, tag) write and the step of `at` run under it -- 12 % of the lanes on average, none of them at a position where no lane of the
+// wave starts a run (exec = 0: the three instructions do nothing).  It used to be six VALU and a write per position with a dummy
+// slot for the other 88 %.
+template <int J0>
+__device__ __forceinline__ void skm_runlist8(uint32_t &c, uint32_t &at, uint32_t lane, uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3,
+                                             uint32_t h4, uint32_t h5, uint32_t h6, uint32_t h7) {
+    uint32_t t;
+    unsigned long long sv, m0, m1, m2, m3, m4, m5, m6, m7;
+#define SKM_RL_STEP(M, H, J) "s_mov_b64 exec, %[" M "]\n\tv_lshl_or_b32 %[t], %[lane], 5, %[" J "]\n\tds_write2_b32 %[at], %[" H "], %[t] offset1:1\n\tv_add_u32 %[at], 8, %[at]\n\t"
+    asm volatile("v_add_co_u32 %[c], %[m0], %[c], %[c]\n\tv_add_co_u32 %[c], %[m1], %[c], %[c]\n\t"
+                 "v_add_co_u32 %[c], %[m2], %[c], %[c]\n\tv_add_co_u32 %[c], %[m3], %[c], %[c]\n\t"
+                 "v_add_co_u32 %[c], %[m4], %[c], %[c]\n\tv_add_co_u32 %[c], %[m5], %[c], %[c]\n\t"
+                 "v_add_co_u32 %[c], %[m6], %[c], %[c]\n\tv_add_co_u32 %[c], %[m7], %[c], %[c]\n\t"
+                 "s_mov_b64 %[sv], exec\n\t"
+                 SKM_RL_STEP("m0", "h0", "j0") SKM_RL_STEP("m1", "h1", "j1") SKM_RL_STEP("m2", "h2", "j2") SKM_RL_STEP("m3", "h3", "j3")
+                 SKM_RL_STEP("m4", "h4", "j4") SKM_RL_STEP("m5", "h5", "j5") SKM_RL_STEP("m6", "h6", "j6") SKM_RL_STEP("m7", "h7", "j7")
+                 "s_mov_b64 exec, %[sv]"
+                 : [c] "+v"(c), [at] "+v"(at), [t] "=&v"(t), [sv] "=&s"(sv), [m0] "=&s"(m0), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3),
+                   [m4] "=&s"(m4), [m5] "=&s"(m5), [m6] "=&s"(m6), [m7] "=&s"(m7)
+                 : [lane] "v"(lane), [h0] "v"(h0), [h1] "v"(h1), [h2] "v"(h2), [h3] "v"(h3), [h4] "v"(h4), [h5] "v"(h5), [h6] "v"(h6), [h7] "v"(h7),
+                   [j0] "i"(J0), [j1] "i"(J0 + 1), [j2] "i"(J0 + 2), [j3] "i"(J0 + 3), [j4] "i"(J0 + 4), [j5] "i"(J0 + 5), [j6] "i"(J0 + 6), [j7] "i"(J0 + 7)
+                 : "memory");
+#undef SKM_RL_STEP
+}
 template <int K, bool DYN, bool FAST>
 __global__ __launch_bounds__(1024) void k_skm_scatter(const uint8_t *__restrict__ bases, uint64_t n_bases, const uint32_t *__restrict__ vmask,
                                                       uint64_t n_words, uint64_t words_per_block, int bits1,
@@ -493,21 +571,27 @@ __global__ __launch_bounds__(1024) void k_skm_scatter(const uint8_t *__restrict_
         L.cur[i] = DYN ? (Dy.save ? (uint64_t)Dy.save[(size_t)blockIdx.x * nd + i] : SKM_NONE) : blockstart[(size_t)i * G + blockIdx.x];
         L.ctr[i] = 0;
     }
-    if (threadIdx.x < 64) L.ctr[nd + threadIdx.x] = 0;
     __syncthreads();
     // FAST: this wave's parking area and run list, behind the staging area
     const uint32_t lane = (uint32_t)mf_lane();
     unsigned char *wbase = smem + ((skm_stage_bytes(nd) + 15) & ~(size_t)15) + (size_t)(threadIdx.x >> 6) * SKM_FAST_WAVE_BYTES;
     uint4 *pd = reinterpret_cast<uint4 *>(wbase);                               // [64] the words' bases
     uint2 *pc = reinterpret_cast<uint2 *>(wbase + 64 * 16);                     // [64] (positions where a run stops, k-mers of the word's head that belong to the previous lane's run)
-    uint2 *rl = reinterpret_cast<uint2 *>(wbase + 64 * 16 + 64 * 8);            // [SKM_LCAP + 1] (minimizer hash, lane << 5 | position); the last one: dummy
+    uint2 *rl = reinterpret_cast<uint2 *>(wbase + 64 * 16 + 64 * 8);            // [SKM_LCAP] (minimizer hash, lane << 5 | position)
     const uint64_t wlo = (uint64_t)blockIdx.x * words_per_block;
     const uint64_t whi = wlo + words_per_block < n_words ? wlo + words_per_block : n_words;
     // a wave takes 63 words per batch: lane 63 only provides lane 62's halo (skm_scan_word_halo), the word it scans is lane 0's
     // of the wave's next batch
-    const uint64_t wstep = (uint64_t)(blockDim.x >> 6) * 63u;
+    // (the step and the wave's share as provably wave-uniform values: the loop is then counted in scalar registers.  As 64-bit
+    // per-lane values both were spilled to scratch and reloaded every batch)
+    const uint64_t wstep = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6)) * 63u;
+    const uint64_t wave0 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 63u;
     for (uint64_t wb = wlo; wb < whi; wb += wstep) {          // wave-uniform: all lanes reach skm_stage_insert together
-        const uint64_t w = wb + (uint64_t)(threadIdx.x >> 6) * 63u + lane;
+        // the wave's first word of this batch, kept scalar: as (wave0 + lane) + wb the per-lane half lives across the loop -- in scratch
+        uint32_t wlo32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wb + wave0));
+        uint32_t whi32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((wb + wave0) >> 32));
+        asm("" : "+s"(wlo32), "+s"(whi32));
+        const uint64_t w = (((uint64_t)whi32 << 32) | wlo32) + lane;
         const uint32_t m = (lane < 63u && w < whi) ? vmask[w] : 0u;
         if (__ballot(m != 0u) == 0ull) continue;
         skm_word<K> S;
@@ -544,17 +628,12 @@ __global__ __launch_bounds__(1024) void k_skm_scatter(const uint8_t *__restrict_
             pd[lane] = make_uint4(S.D[0], S.D[1], S.D[2], S.D[3]);
             pc[lane] = make_uint2(cutf | ~S.valid, ext);                 // (positions where a run stops, k-mers handed to the previous lane's run)
             {
-                const uint32_t l0 = mf_lds_addr(rl), dummy = l0 + 8u * (uint32_t)SKM_LCAP;
-                uint32_t at = l0 + 8u * roff;
-                const uint32_t tagl = lane << 5;
-#pragma unroll
-                for (int j = 0; j < 32; j++) {
-                    const uint32_t bit = (cutf >> j) & 1u;
-                    const uint32_t addr = bit ? at : dummy;
-                    const uint32_t v1 = tagl | (uint32_t)j;
-                    asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" :: "v"(addr), "v"(S.mh[j]), "v"(v1) : "memory");
-                    at += bit << 3;
-                }
+                // (a lane's descriptors are rl[roff .. roff + popc(cutf)): inside the list, NR <= SKM_LCAP here)
+                uint32_t at = mf_lds_addr(rl) + 8u * roff, c = __brev(cutf);
+                skm_runlist8<0>(c, at, lane, S.mh[0], S.mh[1], S.mh[2], S.mh[3], S.mh[4], S.mh[5], S.mh[6], S.mh[7]);
+                skm_runlist8<8>(c, at, lane, S.mh[8], S.mh[9], S.mh[10], S.mh[11], S.mh[12], S.mh[13], S.mh[14], S.mh[15]);
+                skm_runlist8<16>(c, at, lane, S.mh[16], S.mh[17], S.mh[18], S.mh[19], S.mh[20], S.mh[21], S.mh[22], S.mh[23]);
+                skm_runlist8<24>(c, at, lane, S.mh[24], S.mh[25], S.mh[26], S.mh[27], S.mh[28], S.mh[29], S.mh[30], S.mh[31]);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
@@ -575,7 +654,7 @@ __global__ __launch_bounds__(1024) void k_skm_scatter(const uint8_t *__restrict_
                     uint32_t digits;
                     skm_route(de.x, bits1, d[b], digits);
                     rec[b] = skm_make_rec<K>(DD, s0, len, digits, Dn.z);
-                    if (!pend[b] || d[b] < dlo || d[b] >= dhi) { pend[b] = false; d[b] = 0; rec[b] = make_ulonglong2(~0ull, ~0ull); }
+                    if (d[b] < dlo || d[b] >= dhi) pend[b] = false;                                       // (another slice's record)
                 }
                 skm_stage_insert<DYN>(L, out, d, rec, pend, Dy);
             }
@@ -697,7 +776,6 @@ __global__ __launch_bounds__(1024) void k_skm_split(const skm_rec *__restrict__ 
         }
         __syncthreads();
         for (int i = threadIdx.x; i < nd; i += blockDim.x) L.ctr[i] = 0;
-        if (threadIdx.x < 64) L.ctr[nd + threadIdx.x] = 0;
         __syncthreads();
         // wave-uniform loop bounds: every lane reaches skm_stage_insert
         for (uint32_t jb = 0; jb < len; jb += 4 * blockDim.x) {
