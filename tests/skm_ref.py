@@ -1,4 +1,4 @@
-"""The super-k-mer records of the counting path (metafast_amd/csrc/mf_skm.hip: S1 k_skm_hist, S2 k_skm_scatter, S3 k_skm_split) restated in
+"""The super-k-mer records of the counting path (metafast_amd/csrc/mf_skm_scatter.h: S1 k_skm_hist, S2 k_skm_scatter; mf_skm_split.h: S3 k_skm_split) restated in
 plain numpy for tests/test_skm_records_gpu.py.  The rule is stated from the reads, position by position; nothing here is shared with the
 kernels' way of getting there (rolling reverse complements, a three-input sliding minimum, halo words from the next lane, run lists in LDS).
 tests/test_skm_ref_cpu.py pins this file to the oracle's table and to tests/nbr_ref.py.

@@ -1,4 +1,4 @@
-"""The reverse complements of the minimizer scan, taken word by word (metafast_amd/csrc/mf_skm.hip: skm_rc16, skm_mmer_at), restated on the host
+"""The reverse complements of the minimizer scan, taken word by word (metafast_amd/csrc/mf_skm_scan.h: skm_rc16, skm_mmer_at), restated on the host
 and compared with the reverse complement of the M-mer itself (mf_mmer_rc, restated as nbr_ref.revcomp).
 
 The scan holds 64 bases in four dwords D[0..3], first base in the top bits of D[0].  It reverse-complements each dword once, R[3 - q] =

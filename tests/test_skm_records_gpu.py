@@ -1,4 +1,4 @@
-"""The super-k-mer scan, scatter and split (metafast_amd/csrc/mf_skm.hip: k_skm_hist, k_skm_scatter, k_skm_split) record by record against
+"""The super-k-mer scan, scatter and split (metafast_amd/csrc/mf_skm_scan.h, mf_skm_scatter.h, mf_skm_split.h: k_skm_hist, k_skm_scatter, k_skm_split) record by record against
 tests/skm_ref.py.
 
 mf_debug_skm_records (mf_skm.hip; bound here with ctypes, not part of the C-ABI) runs what mf_count_device runs with the context's options and

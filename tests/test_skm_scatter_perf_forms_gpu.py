@@ -1,4 +1,4 @@
-"""k_skm_scatter / k_skm_hist (metafast_amd/csrc/mf_skm.hip) at the edges of the cheaper scan: reverse complements cut out of reversed words, the
+"""k_skm_scatter / k_skm_hist (metafast_amd/csrc/mf_skm_scatter.h) at the edges of the cheaper scan: reverse complements cut out of reversed words, the
 sliding minimum's partial results handed over by the next lane, record tails cleared with 64-bit masks.  Every partition's record multiset
 against tests/skm_ref.py, with the checks and the hook of tests/test_skm_records_gpu.py, bit-exact.
 

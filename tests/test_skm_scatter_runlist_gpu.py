@@ -1,4 +1,4 @@
-"""k_skm_scatter (metafast_amd/csrc/mf_skm.hip) where its run list and its staging protocol work under lane masks: a descriptor is written
+"""k_skm_scatter (metafast_amd/csrc/mf_skm_scatter.h) where its run list and its staging protocol work under lane masks: a descriptor is written
 only by the lanes that start a run at a position (skm_runlist8), and only pending lanes peek, reserve, write and commit in
 skm_stage_insert.  Every partition's record multiset and the directory invariants against tests/skm_ref.py, with the checks and the hook
 of tests/test_skm_records_gpu.py, bit-exact, in the exact and in the one-pass form.
