@@ -241,6 +241,19 @@ int  mf_features_wide(mf_ctx *ctx, const char *components_bin, const char *kmers
 int  mf_wcomps_unitigs_device(mf_ctx *ctx, mf_wcomps *c, int split, mf_seqs **out);
 int  mf_comp2seq_wide(mf_ctx *ctx, const char *components_bin, int k, int split, const char *out_dir, uint64_t *n_files,
                       uint64_t *n_seqs);
+/* [mf_comps_graph_device / mf_comp2graph] comp2graph on wide components (mf_wcomp2graph.hip): the semantics of the k <= 31 entry points
+ * on 2k-bit k-mers, rule for rule -- names <n>_i<c>, paths ascending by (canonical start k-mer, strand as walked) then isolated cycles, the
+ * printed strand never above its reverse complement in string order, L lines ascending by (from, sign, to, sign), a palindromic k-mer
+ * (even k) as two S lines with its links counted twice, a hairpin ending its segment with a link to itself; a member list that holds x
+ * and rc(x) gives one row, drawn once.  Values: no samples -- every member 1; coverage == 0 -- the number of tables that hold the k-mer
+ * with a count > 0; coverage != 0 -- the summed count, bounded at 32767.  A sample table of another k or another context is an error.
+ * The result is an ordinary mf_gfa, declared below, for mf_gfa_text / mf_gfa_stats / mf_gfa_destroy.  Fewer than 2^31 - 1 members,
+ * 2^31 - 1 segments, 2^32 - 1 components.  The file form keeps one wide .kmers.bin resident at a time (coverage: one load of all files);
+ * nothing is written before mf_wcomps_load has accepted the file and the text is complete. */
+struct mf_gfa;
+int  mf_wcomps_graph_device(mf_ctx *ctx, mf_wcomps *c, mf_wtable *const *samples, int n_samples, int coverage, struct mf_gfa **out);
+int  mf_comp2graph_wide(mf_ctx *ctx, const char *components_bin, int k, const char *const *kmers_files, int n_files, int coverage,
+                        const char *out_gfa, uint64_t *n_components, uint64_t *n_segments, uint64_t *n_links);
 
 /* ---- A5/A6  .kmers.bin / .stat.txt --------------------------------------------------- */
 /* replaces IOUtils.printKmers (src/io/IOUtils.java:45-71; KmersCounterMain.java:99): 10-byte

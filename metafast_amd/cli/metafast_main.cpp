@@ -90,6 +90,7 @@ extern "C" int mf_wcomps_stats(const mf_wcomps *, uint64_t *, uint64_t *) __attr
 extern "C" void mf_wcomps_destroy(mf_wcomps *) __attribute__((weak));
 extern "C" int mf_features_wide(mf_ctx *, const char *, const char *, int, int, const char *, const char *) __attribute__((weak));
 extern "C" int mf_comp2seq_wide(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_comp2graph_wide(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -390,6 +391,7 @@ static bool wide_k(int k) {
     return true;
 }
 // view and bin2fasta read wide files on the host and call no library function: wide without a look at the library's symbols
+// (comp2graph calls ONE entry point, on wide files somebody else wrote, and reports it by name itself)
 static bool wide_host_k(int k) {
     if (!g_wide || k <= 31) return false;
     if (k > 63) die("The size of k-mer must be no more than 63.");
@@ -1540,16 +1542,18 @@ static vector<PV> tool_comp2seq(Run &r) {
 static vector<PV> tool_comp2graph(Run &r) {
     // ComponentsToGraph.java:70-130: one Comp2Graph per component on a thread pool, a HashMap of strings and a quadratic merge loop
     // each -- here the graphs of all components in one pass, the text formatted on the device (mf_comp2graph)
+    // (--wide-kmers and k > 31: the same on a wide components.bin and wide .kmers.bin files, mf_comp2graph_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const string cf = r.str("components-file"), gf = r.str("graph-file");
     const vector<string> files = r.a.list("k-mers");
     const bool cov = r.a.flag("coverage");                                // (without -i: accepted and ignored, as in the reference)
-    r.entry(mf_comp2graph != nullptr, "mf_comp2graph");
+    if (wide) r.entry(mf_comp2graph_wide != nullptr, "mf_comp2graph_wide"); else r.entry(mf_comp2graph != nullptr, "mf_comp2graph");
     mf_ctx *ctx = r.ctx();
     auto fp = cptrs(files);
     uint64_t nc = 0, ns = 0, nl = 0;
-    check(mf_comp2graph(ctx, cf.c_str(), k, files.empty() ? nullptr : fp.data(), (int)files.size(), cov ? 1 : 0, gf.c_str(), &nc, &ns, &nl));
+    check((wide ? mf_comp2graph_wide : mf_comp2graph)(ctx, cf.c_str(), k, files.empty() ? nullptr : fp.data(), (int)files.size(), cov ? 1 : 0, gf.c_str(), &nc, &ns, &nl));
     logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
     logmsg("INFO", "Graph components saved to GFA format!");
     return {PV::file("graph-file", gf)};

@@ -9,7 +9,7 @@ import sys
 
 NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_cp_|k_specific|k_uk_")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
-# column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip; one thread per run of positions, per
+# column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip, mf_wcomp2graph.hip; one thread per run of positions, per
 # run, per record, or one wave per record: mf_comppaths.hip)
 NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_|k_cp_")
 # the translation units that hold those kernels: the guard must SEE them there (a renamed kernel, or a remark format that changed,
@@ -18,6 +18,9 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
           "mf_kps": ["k_kps_index", "k_kps_gather", "k_kps_header", "k_kps_widths", "k_kps_format"],
           "mf_comp2graph": ["k_c2g_links", "k_c2g_double", "k_c2g_ends", "k_c2g_assign", "k_c2g_segments", "k_c2g_links_of", "k_c2g_write_s",
                             "k_c2g_write_bases", "k_c2g_write_l", "k_c2g_values"],
+          # (the same steps on 2k-bit k-mers: mf_c2g.h's kernels, the three k-mer reading ones instantiated over 128-bit keys)
+          "mf_wcomp2graph": ["k_c2g_links", "k_c2g_double", "k_c2g_ends", "k_c2g_assign", "k_c2g_segments", "k_c2g_links_of", "k_c2g_write_s",
+                             "k_c2g_write_bases", "k_c2g_write_l", "k_c2g_wvalues"],
           # (k_s2c_lds: waves that share a workgroup's LDS table between wave-level barriers, two workgroups per CU)
           "mf_seq2comp": ["k_s2c_sizes", "k_s2c_lds", "k_s2c_pairs", "k_s2c_heads", "k_s2c_seg_heads", "k_s2c_seg_sizes", "k_s2c_compact", "k_s2c_place",
                           "k_s2c_shift"],

@@ -22,17 +22,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include "mf_common.h"
-#include "mf_wide.h"
-#include "mf_c2s.h"
-
-#define WC2S_EMPTY 0xFFFFFFFFFFFFFFFFull
-
-static inline unsigned wc2s_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 0x7FFFFFFFull); }
-
-// rows sorted by (component, hi, lo)
-struct wc2s_rows { mf_buf<uint64_t> hi, lo; mf_buf<uint32_t> comp; mf_buf<uint16_t> cnt; uint64_t n = 0; };
-struct wc2s_index { const unsigned long long *slots; uint64_t mask; const uint64_t *hi, *lo; const uint32_t *comp; };
+#include "mf_wc2s.h"
 
 // members -> canonical k-mers; a member that does not fit 2k bits raises bit 0 of *flags
 __global__ __launch_bounds__(256) void k_wc2s_canon(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, uint64_t n, int k, uint64_t *__restrict__ ohi,
@@ -81,10 +71,7 @@ __global__ __launch_bounds__(256) void k_wc2s_counts(const uint32_t *__restrict_
     rcnt[r] = (uint16_t)(len > (uint64_t)MF_MAX_COUNT ? (uint64_t)MF_MAX_COUNT : len);
 }
 
-// ---- the wide pair index: home slot = low bits of the hash, tag = its high 32 bits
-__device__ __forceinline__ uint64_t wc2s_hash(uint64_t hi, uint64_t lo, uint32_t comp) {
-    return mf_hash64((lo * 0x9E3779B97F4A7C15ull ^ hi) + (uint64_t)comp * 0xC2B2AE3D27D4EB4Full);
-}
+// ---- the wide pair index (wc2s_hash, wc2s_find: mf_wc2s.h)
 // the rows' (k-mer, component) pairs are all different: a row takes the first empty slot of its probe sequence
 __global__ __launch_bounds__(256) void k_wc2s_index_insert(unsigned long long *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ rhi,
                                                            const uint64_t *__restrict__ rlo, const uint32_t *__restrict__ rcomp, uint64_t n_rows) {
@@ -96,22 +83,6 @@ __global__ __launch_bounds__(256) void k_wc2s_index_insert(unsigned long long *_
     for (;;) {                                               // (load <= 0.5: an empty slot is always there)
         if (slots[s] == WC2S_EMPTY && atomicCAS(&slots[s], WC2S_EMPTY, ent) == WC2S_EMPTY) break;
         s = (s + 1) & mask;
-    }
-}
-// the row of (k-mer, component) or C2S_NONE
-__device__ __forceinline__ uint32_t wc2s_find(const wc2s_index &ix, mf_u128 key, uint32_t comp) {
-    const uint64_t hi = (uint64_t)(key >> 64), lo = (uint64_t)key;
-    const uint64_t h = wc2s_hash(hi, lo, comp);
-    const uint32_t tag = (uint32_t)(h >> 32);
-    uint64_t s = h & ix.mask;
-    for (;;) {
-        const unsigned long long v = ix.slots[s];
-        if (v == WC2S_EMPTY) return C2S_NONE;
-        if ((uint32_t)(v >> 32) == tag) {
-            const uint32_t p = (uint32_t)v;
-            if (ix.lo[p] == lo && ix.hi[p] == hi && ix.comp[p] == comp) return p;
-        }
-        s = (s + 1) & ix.mask;
     }
 }
 // U1 restricted to a component: k_w_ut_flags (mf_wgraph.hip) per ROW, every neighbour looked up in the row's own component.  One reverse
@@ -160,7 +131,7 @@ __global__ __launch_bounds__(256) void k_wc2s_flags(wc2s_index ix, ut_arrays A) 
 // ---------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------
-static int wc2s_check_k(const char *who, int k) {
+int wc2s_check_k(const char *who, int k) {
     if (k < 32 || k > 63) return mf_set_error("%s: 32 <= k <= 63 (k <= 31: the entry point without 'wide')", who);
     return MF_OK;
 }
@@ -171,12 +142,12 @@ static int wc2s_member_flags(mf_ctx *ctx, const unsigned int *d_flags, int k) {
     if (f & 1u) return mf_set_error("comp2seq: a component holds a k-mer that does not fit %d bases", k);
     return MF_OK;
 }
-static int wc2s_member_count(const mf_wcomps *c) {
-    if (c->n_kmers >= 0x7FFFFFFFull) return mf_set_error("comp2seq: %llu component k-mers (fewer than 2^31 - 1 are supported)", (unsigned long long)c->n_kmers);
+int wc2s_member_count(const char *who, const mf_wcomps *c) {
+    if (c->n_kmers >= 0x7FFFFFFFull) return mf_set_error("%s: %llu component k-mers (fewer than 2^31 - 1 are supported)", who, (unsigned long long)c->n_kmers);
     return MF_OK;
 }
 // the rows of all components, built from the member lists
-static int wc2s_build_rows(mf_ctx *ctx, const mf_wcomps *c, wc2s_rows &R) {
+int wc2s_build_rows(mf_ctx *ctx, const mf_wcomps *c, wc2s_rows &R) {
     hipStream_t st = ctx->stream;
     const uint64_t n = c->n_kmers;
     const int k = c->k, hb = 2 * k - 64;
@@ -225,26 +196,32 @@ static int wc2s_build_rows(mf_ctx *ctx, const mf_wcomps *c, wc2s_rows &R) {
     R.n = nr;
     return MF_OK;
 }
+int wc2s_pair_index(mf_ctx *ctx, const wc2s_rows &R, mf_buf<unsigned long long> &slots, wc2s_index *ix) {
+    *ix = wc2s_index{};
+    if (!R.n) return MF_OK;
+    uint64_t cap = 1024; while (cap < 2 * R.n) cap <<= 1;                        // load <= 0.5, as the index of a wide table (mf_wtable_ensure_index)
+    MF_TRY(slots.alloc(ctx, cap));
+    MF_HIP(hipMemsetAsync(slots.p, 0xFF, cap * 8, ctx->stream));
+    mf_ktimer tm(ctx, "k_wc2s_index_insert");
+    k_wc2s_index_insert<<<wc2s_grid(R.n), 256, 0, ctx->stream>>>(slots.p, cap - 1, R.hi.p, R.lo.p, R.comp.p, R.n);
+    *ix = wc2s_index{slots.p, cap - 1, R.hi.p, R.lo.p, R.comp.p};
+    return MF_OK;
+}
+int wc2s_flags_launch(mf_ctx *ctx, const wc2s_index &ix, const ut_arrays &A) {
+    if (!A.n) return MF_OK;
+    mf_ktimer tm(ctx, "k_wc2s_flags");
+    k_wc2s_flags<<<wc2s_grid(A.n), 256, 0, ctx->stream>>>(ix, A);
+    return MF_OK;
+}
 // the segmented build over the rows: pair index, restricted U1, U2 .. U5
 static int wc2s_unitigs_of_rows(mf_ctx *ctx, const wc2s_rows &R, uint64_t n_comps, int k, mf_seqs **out) {
-    hipStream_t st = ctx->stream;
     const uint64_t nr = R.n;
     mf_buf<unsigned long long> slots;
     wc2s_index ix{};
-    if (nr) {
-        uint64_t cap = 1024; while (cap < 2 * nr) cap <<= 1;                     // load <= 0.5, as the index of a wide table (mf_wtable_ensure_index)
-        MF_TRY(slots.alloc(ctx, cap));
-        MF_HIP(hipMemsetAsync(slots.p, 0xFF, cap * 8, st));
-        mf_ktimer tm(ctx, "k_wc2s_index_insert");
-        k_wc2s_index_insert<<<wc2s_grid(nr), 256, 0, st>>>(slots.p, cap - 1, R.hi.p, R.lo.p, R.comp.p, nr);
-        ix = wc2s_index{slots.p, cap - 1, R.hi.p, R.lo.p, R.comp.p};
-    }
+    MF_TRY(wc2s_pair_index(ctx, R, slots, &ix));
     mf_seqs *S = nullptr;
-    MF_TRY(mf_ut_build(ctx, R.lo.p, R.hi.p, R.cnt.p, nr, k, 0, nullptr, k, [&](const ut_arrays &A) -> int {
-        mf_ktimer tm(ctx, "k_wc2s_flags");
-        k_wc2s_flags<<<wc2s_grid(A.n), 256, 0, st>>>(ix, A);
-        return MF_OK;
-    }, &S, nullptr, R.comp.p));
+    MF_TRY(mf_ut_build(ctx, R.lo.p, R.hi.p, R.cnt.p, nr, k, 0, nullptr, k, [&](const ut_arrays &A) -> int { return wc2s_flags_launch(ctx, ix, A); }, &S, nullptr,
+                       R.comp.p));
     if (!S->d_comp) {                                        // (no rows: no sequences, but sequences of components all the same)
         void *p = nullptr;
         if (mf_alloc(ctx, 4, &p) < 0) { mf_seqs_destroy(S); return MF_ERR; }
@@ -300,7 +277,7 @@ extern "C" int mf_wcomps_unitigs_device(mf_ctx *ctx, mf_wcomps *c, int split, mf
     *out = nullptr;
     if (c->ctx != ctx) return mf_set_error("mf_wcomps_unitigs_device: the components belong to another context");
     MF_TRY(wc2s_check_k("mf_wcomps_unitigs_device", c->k));
-    MF_TRY(wc2s_member_count(c));
+    MF_TRY(wc2s_member_count("comp2seq", c));
     MF_HIP(hipSetDevice(ctx->device));
     if (split) {
         wc2s_rows R;
@@ -347,7 +324,7 @@ extern "C" int mf_comp2seq_wide(mf_ctx *ctx, const char *components_bin, int k, 
     mf_wcomps *c = nullptr;
     MF_TRY(mf_wcomps_load(ctx, components_bin, k, &c));      // (a file of another width or another k stops here, before anything is written)
     std::unique_ptr<mf_wcomps, void (*)(mf_wcomps *)> gc(c, mf_wcomps_destroy);
-    MF_TRY(wc2s_member_count(c));
+    MF_TRY(wc2s_member_count("comp2seq", c));
     MF_HIP(hipSetDevice(ctx->device));
     const std::string od(out_dir);
     const std::string d_fa = od + "/kmers_fasta", d_km = od + "/kmer-counter-many/kmers", d_st = od + "/kmer-counter-many/stats", d_sq = od + "/seq-builder-many/sequences";

@@ -52,12 +52,6 @@ int mf_wtable_ensure_index(mf_wtable *t) {
     k_windex_build<<<ggrid(t->n), 256, 0, ctx->stream>>>(t->index.p, t->index_mask, pc.hi.p, pc.lo.p, t->n, t->k);
     return MF_OK;
 }
-static mf_windex_view wview(const mf_wtable *t) {
-    mf_windex_view v{};
-    v.k = t->k;
-    if (t->n) { auto &pc = *t->pieces[0]; v.slots = t->index.p; v.mask = t->index_mask; v.hi = pc.hi.p; v.lo = pc.lo.p; v.cnt = pc.cnt.p; v.n = t->n; }
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // the eight neighbours of a vertex: idx[2 nuc] = x[1..] + nuc (right), idx[2 nuc + 1] = nuc + x[..k-2] (left), as mf_nbr.h; bit i of
@@ -168,7 +162,7 @@ extern "C" int mf_build_unitigs_wide_device(mf_ctx *ctx, mf_wtable *t, int freq_
         own.reset(f); g = f;
     }
     if (g->n && g->n < 0x7FFFFFFFull) MF_TRY(mf_wtable_ensure_index(g));
-    const mf_windex_view ix = wview(g);
+    const mf_windex_view ix = mf_wtable_view(g);
     // (an empty table: no high words to point at -- mf_ut_build returns its empty result before it looks)
     return mf_ut_build(ctx, ix.lo, ix.hi, ix.cnt, g->n, g->k, 0, nullptr, min_len, [&](const ut_arrays &A) -> int {
         k_w_ut_flags<<<ggrid(A.n), 256, 0, ctx->stream>>>(ix, A);
@@ -203,7 +197,7 @@ extern "C" int mf_cut_components_wide_device(mf_ctx *ctx, mf_wtable *t, int b1, 
     if (t->n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
     MF_TRY(mf_wtable_ensure_ascending(t));                // (vertex ids stand for k-mers here: members come out as ids, ties go to the smallest id)
     if (t->n) MF_TRY(mf_wtable_ensure_index(t));
-    const mf_windex_view ix = wview(t);
+    const mf_windex_view ix = mf_wtable_view(t);
     mf_comps *inner = nullptr;
     // (d_keys = nullptr: the members come out as vertex ids, ties between components are broken by the smallest id = the smallest k-mer)
     MF_TRY(mf_cc_build(ctx, t->n, 16, ix.cnt, nullptr, b1, b2, [&](uint32_t *nbr) -> int {
@@ -286,7 +280,7 @@ extern "C" int mf_features_wide_device(mf_ctx *ctx, mf_wcomps *c, mf_wtable *sam
     if (sample->n && c->n_kmers) {
         MF_TRY(mf_wtable_ensure_index(sample));
         mf_ktimer tm(ctx, "k_features");
-        k_w_features<<<ggrid(c->n_kmers), 256, 0, st>>>(wview(sample), c->hi.p, c->lo.p, c->comp.p, c->n_kmers, threshold, dvec.p, dfound.p);
+        k_w_features<<<ggrid(c->n_kmers), 256, 0, st>>>(mf_wtable_view(sample), c->hi.p, c->lo.p, c->comp.p, c->n_kmers, threshold, dvec.p, dfound.p);
     }
     std::vector<unsigned int> hf(nc);
     MF_HIP(hipMemcpyAsync(vec, dvec.p, nc * 8, hipMemcpyDeviceToHost, st));
@@ -318,7 +312,7 @@ extern "C" int mf_wtable_lookup(mf_wtable *t, const uint64_t *keys_hi, const uin
     MF_TRY(dh.alloc(ctx, n)); MF_TRY(dl.alloc(ctx, n)); MF_TRY(dv.alloc(ctx, n));
     MF_HIP(hipMemcpyAsync(dh.p, keys_hi, n * 8, hipMemcpyHostToDevice, st));
     MF_HIP(hipMemcpyAsync(dl.p, keys_lo, n * 8, hipMemcpyHostToDevice, st));
-    k_w_lookup<<<ggrid(n), 256, 0, st>>>(wview(t), dh.p, dl.p, n, dv.p);
+    k_w_lookup<<<ggrid(n), 256, 0, st>>>(mf_wtable_view(t), dh.p, dl.p, n, dv.p);
     MF_HIP(hipMemcpyAsync(values, dv.p, n * 4, hipMemcpyDeviceToHost, st));
     MF_HIP(hipStreamSynchronize(st));
     return MF_OK;

@@ -25,6 +25,13 @@ struct mf_wtable {
     mf_buf<unsigned long long> index; uint64_t index_mask = 0;
 };
 struct mf_windex_view { const unsigned long long *slots; uint64_t mask; const uint64_t *hi, *lo; const uint16_t *cnt; uint64_t n; int k; };
+// the view of an indexed table (after mf_wtable_ensure_index)
+static inline mf_windex_view mf_wtable_view(const mf_wtable *t) {
+    mf_windex_view v{};
+    v.k = t->k;
+    if (t->n) { auto &pc = *t->pieces[0]; v.slots = t->index.p; v.mask = t->index_mask; v.hi = pc.hi.p; v.lo = pc.lo.p; v.cnt = pc.cnt.p; v.n = t->n; }
+    return v;
+}
 
 // the count on the record path (mf_wskm.hip): 0 = *t filled, 1 = not an input for it (the caller counts the old way), < 0 = error
 int mf_count_wide_skm(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_read_len, int threshold,

@@ -58,6 +58,8 @@ _SIGS = {
     "mf_features_wide": (i32, [vp, cp, cp, i32, i32, cp, cp]),
     "mf_wcomps_unitigs_device": (i32, [vp, vp, i32, pvp]),
     "mf_comp2seq_wide": (i32, [vp, cp, i32, i32, cp, pu64, pu64]),
+    "mf_wcomps_graph_device": (i32, [vp, vp, vp, i32, i32, pvp]),
+    "mf_comp2graph_wide": (i32, [vp, cp, i32, C.POINTER(cp), i32, i32, cp, pu64, pu64, pu64]),
     "mf_comm_create_local": (i32, [vp, i32, vp]),
     "mf_comm_rccl_id": (i32, [vp]),
     "mf_comm_create_rccl": (i32, [vp, vp, i32, i32, pvp]),
@@ -533,6 +535,9 @@ class Context:
         h = (C.c_void_p * max(len(samples), 1))(*[t.h for t in samples])
         g = C.c_void_p()
         _check(lib().mf_comps_graph_device(self.h, comps.h, h, len(samples), 1 if coverage else 0, C.byref(g)))
+        return self._gfa_out(g)
+
+    def _gfa_out(self, g):
         try:
             ns, nl, ncy, nb = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
             _check(lib().mf_gfa_stats(g, C.byref(ns), C.byref(nl), C.byref(ncy), C.byref(nb)))
@@ -548,6 +553,24 @@ class Context:
         nc, ns, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(lib().mf_comp2graph(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files), 1 if coverage else 0,
                                    os.fsencode(out_gfa), C.byref(nc), C.byref(ns), C.byref(nl)))
+        return nc.value, ns.value, nl.value
+
+    def wcomps_graph(self, wcomps, samples=None, coverage=False):
+        """NO-REFERENCE EXTENSION, 32 <= k <= 63 (mf_wcomp2graph.hip): comps_graph on WideComps (they know their k) -> (text, stats);
+        samples: WideTables of the same k"""
+        samples = list(samples or [])
+        h = (C.c_void_p * max(len(samples), 1))(*[t.h for t in samples])
+        g = C.c_void_p()
+        _check(lib().mf_wcomps_graph_device(self.h, wcomps.h, h, len(samples), 1 if coverage else 0, C.byref(g)))
+        return self._gfa_out(g)
+
+    def comp2graph_wide(self, components_bin, k, out_gfa, kmers_files=(), coverage=False):
+        """NO-REFERENCE EXTENSION: comp2graph's file form on a wide components.bin and wide .kmers.bin files -> out_gfa; returns
+        (components, segments, links)"""
+        files = list(kmers_files)
+        nc, ns, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().mf_comp2graph_wide(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files), 1 if coverage else 0,
+                                        os.fsencode(out_gfa), C.byref(nc), C.byref(ns), C.byref(nl)))
         return nc.value, ns.value, nl.value
 
     # ---- seq2comp ----
