@@ -138,6 +138,7 @@ struct mf_ctx {
     // counters a host can read (mf_ctx_stat): counting runs that started their slices over because a buffer found no place (mf_skm.hip);
     // read files the device parser took / handed to the host readers (mf_dparse.hip)
     uint64_t n_slice_restarts = 0, n_dparse_files = 0, n_dparse_stepped_back = 0, n_wide_big = 0, n_wide_hashed = 0, n_ut_doubled = 0, n_pilots = 0, n_gz_device = 0, n_s2c_batches = 0;
+    uint64_t n_table_regrown = 0;  // calls of skm_grow_table (mf_skm.hip) that had entries to copy: the dense table of a run grown a second, third ... time
     // timers
     std::vector<mf_timer_rec> pending;
     std::vector<hipEvent_t> event_pool;

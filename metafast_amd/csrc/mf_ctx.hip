@@ -217,6 +217,7 @@ extern "C" int64_t mf_ctx_stat(mf_ctx *ctx, const char *name) {
     if (s == "slice_restarts") return (int64_t)ctx->n_slice_restarts;
     if (s == "gz_files_inflated_into_hbm") return (int64_t)ctx->n_gz_device;
     if (s == "pilot_runs") return (int64_t)ctx->n_pilots;
+    if (s == "skm_table_regrown") return (int64_t)ctx->n_table_regrown;
     if (s == "unitig_doublings") return (int64_t)ctx->n_ut_doubled;
     if (s == "wide_big_entries") return (int64_t)ctx->n_wide_big;
     if (s == "wide_hashed_entries") return (int64_t)ctx->n_wide_hashed;

@@ -522,6 +522,7 @@ static int skm_grow_table(mf_ctx *ctx, skm_acc &A, uint64_t need, uint64_t done_
     mf_buf<uint64_t> nk; mf_buf<uint16_t> nc;
     if (nk.alloc(ctx, want) != MF_OK || nc.alloc(ctx, want) != MF_OK) return MF_SKM_NOMEM;
     if (A.dused) {
+        ctx->n_table_regrown++;                                 // (mf_ctx_stat "skm_table_regrown")
         MF_HIP(hipMemcpyAsync(nk.p, A.dk.p, A.dused * 8, hipMemcpyDeviceToDevice, st));
         MF_HIP(hipMemcpyAsync(nc.p, A.dc.p, A.dused * 2, hipMemcpyDeviceToDevice, st));
         MF_HIP(hipStreamSynchronize(st));
@@ -1101,5 +1102,196 @@ extern "C" int mf_debug_skm_copy(const mf_skm_snap *s, int slice, uint64_t *rec,
     if (pocc) std::copy(x.pocc.begin(), x.pocc.end(), pocc);
     if (l1_pstart) std::copy(x.l1_pstart.begin(), x.l1_pstart.end(), l1_pstart);
     if (l1_plen) std::copy(x.l1_plen.begin(), x.l1_plen.end(), l1_plen);
+    return MF_OK;
+}
+
+// =============================================================================================
+// Debugging aid of tests/test_skm_count_units_gpu.py (not part of the C-ABI; host code only, no kernel of its own): S4 on records the test supplies.
+// The record buffer and the directory come from the host, the launches are skm_count_batches' own (k_skm_count<K> with C2_LDS dynamic LDS through
+// skm_set_lds, the units split into batches by the same rule, a scan of the batch's dcount, k_gather_split for 2 table partitions per unit and
+// k_gather_split_n otherwise), and everything the stage writes goes back to the host.
+//   mf_debug_skm_count       rec[2 n_rec] (x, y of every record), pstart / plen [np]; k 20 .. 31; thr -1 .. C2_LH - 1; dedupe: the option's raw value; dyn 1: as
+//                            skm_count_batches launches it (a unit counter, drop_hist when thr >= 0), 0: as skm_pilot does (neither); grid 1 .. 2 CUs; n_batches >= 1;
+//                            room[np] or null: entries a unit's slice of the lists takes (null: its occurrences / (thr + 1), k_skm_cap); split_bits < 0: no gather,
+//                            else 0 .. 4 table partitions bits per unit, from bit `bit` of the partition hash.
+//                            A directory that is not well formed is refused before anything is allocated or launched: regions ascending, disjoint, inside the buffer,
+//                            plen a multiple of 4; a record with n = 63 is all ones; any other has 1 <= n <= RMAX and zero bits behind its last base.
+//                            The lists are allocated at the units' occurrences (>= the sum of `room`) and filled with 0xA5 before every batch: what a unit
+//                            writes beyond its room stays inside them and shows.  A batch that raises `overflow` is the last one, and nothing is gathered.
+//   mf_debug_skm_count_info  info[0..10) = np, length of the lists, overflow, n_all, n_redo (summed over the batches), gathered (0 / 1), entries of dk / dc, length of
+//                            dfine, batches launched, CUs of the device
+//   mf_debug_skm_count_copy  dcount [np] (0xFFFFFFFF: never written), toff [np + 1], tkeys / tcnt [length of the lists]: unit p's slice starts at toff[p]
+//                            (a batch's lists as the batch left them; behind the last unit, up to the end of the allocation, the last batch's), drop_hist [C2_LH]
+//                            (dyn = 1 and thr >= 0, else zeros), dk / dc, dfine [(np << split_bits) + 1]; null: not wanted
+// =============================================================================================
+struct mf_skm_count_dbg {
+    std::vector<uint32_t> dcount; std::vector<uint64_t> toff, tkeys, drop_hist, dk, dfine; std::vector<uint16_t> tcnt, dc;
+    uint64_t overflow = 0, n_all = 0, n_redo = 0, gathered = 0, launches = 0, n_cu = 0;
+};
+// the directory and the records of its regions, as k_skm_count takes them for granted; occ[p]: the k-mers of unit p
+static int skm_debug_check_units(const uint64_t *rec, uint64_t n_rec, const uint64_t *pstart, const uint32_t *plen, uint32_t np, int k, std::vector<uint32_t> &occ) {
+    const uint32_t rmax = (uint32_t)std::min(MF_SKM_BASES - (k - 1), 20);
+    uint64_t end = 0;
+    occ.assign(np, 0);
+    for (uint32_t p = 0; p < np; p++) {
+        if (plen[p] % 4u) return mf_set_error("mf_debug_skm_count: plen[%u] = %u is not a multiple of 4", p, plen[p]);
+        if (pstart[p] < end) return mf_set_error("mf_debug_skm_count: region %u starts at %llu, inside or in front of the region before it (which ends at %llu)", p, (unsigned long long)pstart[p], (unsigned long long)end);
+        if (pstart[p] > n_rec || plen[p] > n_rec - pstart[p]) return mf_set_error("mf_debug_skm_count: region %u = [%llu, + %u) leaves the buffer of %llu records", p, (unsigned long long)pstart[p], plen[p], (unsigned long long)n_rec);
+        end = pstart[p] + plen[p];
+        uint64_t o = 0;
+        for (uint64_t j = pstart[p]; j < end; j++) {
+            const uint64_t x = rec[2 * j], y = rec[2 * j + 1];
+            const uint32_t n = (uint32_t)y & 63u;
+            if (x == ~0ull && y == ~0ull) continue;
+            if (n < 1u || n > rmax) return mf_set_error("mf_debug_skm_count: record %llu of region %u has n = %u (1 .. %u, or an all-ones sentinel)", (unsigned long long)j, p, n, rmax);
+            const int nb = (int)n + k - 1;                                       // bases: 0 .. 31 in x, 32 .. 49 in the top 36 bits of y
+            const uint64_t jx = nb >= 32 ? 0ull : x & ((1ull << (64 - 2 * nb)) - 1ull);
+            const uint64_t jy = (nb <= 32 ? y : y & ((1ull << (64 - 2 * (nb - 32))) - 1ull)) & ~((1ull << 28) - 1ull);
+            if (jx || jy) return mf_set_error("mf_debug_skm_count: record %llu of region %u has bits set behind its last base (%d bases)", (unsigned long long)j, p, nb);
+            o += n;
+        }
+        if (o > 0xFFFFFFFFull) return mf_set_error("mf_debug_skm_count: region %u holds %llu k-mers", p, (unsigned long long)o);
+        occ[p] = (uint32_t)o;
+    }
+    return MF_OK;
+}
+template <int K>
+static int skm_debug_count(mf_ctx *ctx, const uint64_t *rec, uint64_t n_rec, const uint64_t *pstart, const uint32_t *plen, uint32_t np, int thr, uint32_t dedupe, int dyn,
+                           unsigned grid, uint32_t nbatch, const std::vector<uint64_t> &h_toff, uint64_t t_alloc, int S, int bit, mf_skm_count_dbg &D) {
+    hipStream_t st = ctx->stream;
+    MF_TRY(skm_set_lds(k_skm_count<K>, C2_LDS));
+    mf_buf<skm_rec> buf; MF_TRY(buf.alloc(ctx, n_rec + 4));
+    mf_buf<uint64_t> ps, toff, coff, tkeys, dk, dfine; mf_buf<uint32_t> pl, dcount; mf_buf<uint16_t> tcnt, dc; mf_buf<unsigned long long> scal, dhist, c2p;
+    MF_TRY(ps.alloc(ctx, np)); MF_TRY(pl.alloc(ctx, np)); MF_TRY(toff.alloc(ctx, (size_t)np + 1)); MF_TRY(coff.alloc(ctx, (size_t)np + 1)); MF_TRY(dcount.alloc(ctx, np));
+    MF_TRY(tkeys.alloc(ctx, t_alloc)); MF_TRY(tcnt.alloc(ctx, t_alloc));
+    MF_TRY(scal.alloc(ctx, 16)); MF_TRY(c2p.alloc(ctx, 16)); MF_TRY(dhist.alloc(ctx, (size_t)MF_MAX_COUNT + 1));
+    const uint64_t d_alloc = h_toff[np];                                          // (no overflow: dcount[p] <= the room of p)
+    if (S >= 0) { MF_TRY(dk.alloc(ctx, d_alloc)); MF_TRY(dc.alloc(ctx, d_alloc)); MF_TRY(dfine.alloc(ctx, ((size_t)np << S) + 1)); }
+    MF_HIP(hipMemsetAsync(buf.p, 0xFF, (n_rec + 4) * sizeof(skm_rec), st));        // padding = sentinels
+    if (n_rec) MF_HIP(hipMemcpyAsync(buf.p, rec, n_rec * sizeof(skm_rec), hipMemcpyHostToDevice, st));
+    MF_HIP(hipMemcpyAsync(ps.p, pstart, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    MF_HIP(hipMemcpyAsync(pl.p, plen, (size_t)np * 4, hipMemcpyHostToDevice, st));
+    MF_HIP(hipMemcpyAsync(toff.p, h_toff.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice, st));
+    MF_HIP(hipMemsetAsync(dcount.p, 0xFF, (size_t)np * 4, st));
+    MF_HIP(hipMemsetAsync(scal.p, 0, 16 * 8, st)); MF_HIP(hipMemsetAsync(c2p.p, 0, 16 * 8, st)); MF_HIP(hipMemsetAsync(dhist.p, 0, dhist.bytes(), st));
+    if (S >= 0) MF_HIP(hipMemsetAsync(dfine.p, 0xFF, dfine.bytes(), st));
+    // the batches of skm_count_batches
+    const uint32_t PB = (np + nbatch - 1) / nbatch;
+    std::vector<uint64_t> tb(nbatch + 1);
+    for (uint32_t b = 0; b <= nbatch; b++) tb[b] = h_toff[std::min<uint64_t>((uint64_t)b * PB, np)];
+    uint64_t tmax = 0;
+    for (uint32_t b = 0; b < nbatch; b++) tmax = std::max(tmax, tb[b + 1] - tb[b]);
+    D.tkeys.assign(t_alloc, 0xA5A5A5A5A5A5A5A5ull); D.tcnt.assign(t_alloc, (uint16_t)0xA5A5);
+    uint64_t dused = 0;
+    for (uint32_t b = 0; b < nbatch; b++) {
+        const uint32_t p0 = (uint32_t)std::min<uint64_t>((uint64_t)b * PB, np), p1 = (uint32_t)std::min<uint64_t>((uint64_t)(b + 1) * PB, np);
+        if (p0 == p1) continue;
+        MF_HIP(hipMemsetAsync(tkeys.p, 0xA5, t_alloc * 8, st)); MF_HIP(hipMemsetAsync(tcnt.p, 0xA5, t_alloc * 2, st));
+        MF_HIP(hipMemsetAsync(&scal.p[8], 0, 16, st));                           // ([8] units redone, [9] the unit counter)
+        {
+            const unsigned g = std::min<unsigned>(grid, p1 - p0);
+            mf_ktimer t(ctx, "k_skm_count");
+            k_skm_count<K><<<g, SKM_CT, C2_LDS, st>>>(buf.p, ps.p, pl.p, p1, toff.p, tkeys.p, tcnt.p, dcount.p, (unsigned int *)&scal.p[2], p0, (uint64_t)tb[b], thr, &scal.p[7],
+                                                      (unsigned int *)&scal.p[8], dyn && thr >= 0 ? dhist.p : nullptr, c2p.p, (uint64_t)tmax, dedupe, dyn ? (unsigned int *)&scal.p[9] : nullptr);
+        }
+        D.launches++;
+        MF_TRY(mf_scan<1>(ctx, dcount.p + p0, coff.p + p0, p1 - p0, (uint64_t *)&scal.p[3]));
+        unsigned long long res[2], nr = 0;
+        MF_HIP(hipMemcpyAsync(res, &scal.p[2], 16, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(&nr, &scal.p[8], 8, hipMemcpyDeviceToHost, st));
+        // this batch's lists: its units' slices, and (the last batch) what lies behind them
+        const uint64_t span = p1 == np ? t_alloc - tb[b] : tb[b + 1] - tb[b];
+        if (span) {
+            MF_HIP(hipMemcpyAsync(D.tkeys.data() + tb[b], tkeys.p, span * 8, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipMemcpyAsync(D.tcnt.data() + tb[b], tcnt.p, span * 2, hipMemcpyDeviceToHost, st));
+        }
+        MF_HIP(hipStreamSynchronize(st));
+        MF_HIP(hipGetLastError());
+        D.n_redo += nr & 0xFFFFFFFFull;
+        if (res[0]) { D.overflow = res[0] & 0xFFFFFFFFull; break; }
+        if (S < 0) continue;
+        const uint64_t d_b = res[1];
+        if (dused + d_b > d_alloc) return mf_set_error("mf_debug_skm_count: batch %u keeps %llu entries, its units' rooms add up to less", b, (unsigned long long)d_b);
+        {
+            const unsigned g = (unsigned)std::min<uint64_t>(((uint64_t)(p1 - p0) + 3) / 4, (uint64_t)ctx->n_cu * 32);
+            mf_ktimer t(ctx, "k_gather");
+            if (S == 1)
+                k_gather_split<K><<<g, 256, 0, st>>>(tkeys.p, tcnt.p, toff.p, dcount.p, coff.p, p1, dk.p + dused, dc.p + dused, p0, (uint64_t)tb[b], dfine.p, dused, bit);
+            else
+                k_gather_split_n<K><<<g, 256, 0, st>>>(tkeys.p, tcnt.p, toff.p, dcount.p, coff.p, p1, dk.p + dused, dc.p + dused, p0, (uint64_t)tb[b], dfine.p, dused, bit, S);
+        }
+        dused += d_b;
+        if (p1 == np) D.gathered = 1;
+    }
+    D.dcount.resize(np); D.drop_hist.assign(C2_LH, 0);
+    unsigned long long na = 0;
+    MF_HIP(hipMemcpyAsync(D.dcount.data(), dcount.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipMemcpyAsync(D.drop_hist.data(), dhist.p, (size_t)C2_LH * 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipMemcpyAsync(&na, &scal.p[7], 8, hipMemcpyDeviceToHost, st));
+    if (D.gathered) {
+        D.dk.resize(dused); D.dc.resize(dused); D.dfine.resize(((size_t)np << S) + 1);
+        if (dused) { MF_HIP(hipMemcpyAsync(D.dk.data(), dk.p, dused * 8, hipMemcpyDeviceToHost, st)); MF_HIP(hipMemcpyAsync(D.dc.data(), dc.p, dused * 2, hipMemcpyDeviceToHost, st)); }
+        MF_HIP(hipMemcpyAsync(D.dfine.data(), dfine.p, D.dfine.size() * 8, hipMemcpyDeviceToHost, st));
+    }
+    MF_HIP(hipStreamSynchronize(st));
+    MF_HIP(hipGetLastError());
+    D.n_all = na;
+    return MF_OK;
+}
+extern "C" void mf_debug_skm_count_free(mf_skm_count_dbg *d) { delete d; }
+extern "C" int mf_debug_skm_count(mf_ctx *ctx, const uint64_t *rec, uint64_t n_rec, const uint64_t *pstart, const uint32_t *plen, uint32_t np, int k, int thr, int dedupe, int dyn,
+                                  int grid, int n_batches, const uint32_t *room, int split_bits, int bit, mf_skm_count_dbg **out) {
+    if (!ctx || !out || !pstart || !plen || (n_rec && !rec)) return mf_set_error("mf_debug_skm_count: NULL argument");
+    *out = nullptr;
+    if (k < MF_SKM_MIN_K || k > 31) return mf_set_error("mf_debug_skm_count: k = %d (%d .. 31)", k, MF_SKM_MIN_K);
+    if (thr < -1 || thr >= C2_LH) return mf_set_error("mf_debug_skm_count: thr = %d (-1 .. %d: a higher cut is made after the kernel)", thr, C2_LH - 1);
+    if (dedupe < 0 || (dyn != 0 && dyn != 1)) return mf_set_error("mf_debug_skm_count: dedupe = %d, dyn = %d", dedupe, dyn);
+    if (grid < 1 || grid > ctx->n_cu * C2_WG_PER_CU) return mf_set_error("mf_debug_skm_count: grid = %d (1 .. %d)", grid, ctx->n_cu * C2_WG_PER_CU);
+    if (n_batches < 1) return mf_set_error("mf_debug_skm_count: n_batches = %d", n_batches);
+    if (np < 1 || np > (1u << 20) || n_rec > (1ull << 24)) return mf_set_error("mf_debug_skm_count: %u units, %llu records (1 .. 2^20 units, at most 2^24 records)", np, (unsigned long long)n_rec);
+    if (split_bits > 4 || (split_bits >= 0 && (bit < 0 || bit > 31 || bit + split_bits > 32))) return mf_set_error("mf_debug_skm_count: split_bits = %d from bit %d", split_bits, bit);
+    std::vector<uint32_t> occ;
+    MF_TRY(skm_debug_check_units(rec, n_rec, pstart, plen, np, k, occ));
+    std::vector<uint64_t> toff((size_t)np + 1, 0);
+    uint64_t t_alloc = 0;                                     // (a unit that ran past its room would still end in front of its slice's start + its occurrences)
+    for (uint32_t p = 0; p < np; p++) {
+        const uint32_t r = room ? room[p] : occ[p] / (thr >= 0 ? (uint32_t)thr + 1u : 1u);
+        toff[p + 1] = toff[p] + r; t_alloc += std::max(r, occ[p]);
+    }
+    std::unique_ptr<mf_skm_count_dbg> D(new mf_skm_count_dbg());
+    D->toff = toff; D->n_cu = (uint64_t)ctx->n_cu;
+    const uint32_t nbatch = (uint32_t)std::min<int64_t>(n_batches, np);
+    int rc = MF_ERR;
+    switch (k) {
+#define SKM_CASE(KK) case KK: rc = skm_debug_count<KK>(ctx, rec, n_rec, pstart, plen, np, thr, (uint32_t)dedupe, dyn, (unsigned)grid, nbatch, toff, t_alloc, split_bits, bit, *D); break;
+#ifndef MF_SKM_ONLY_K31
+        SKM_CASE(20) SKM_CASE(21) SKM_CASE(22) SKM_CASE(23) SKM_CASE(24) SKM_CASE(25)
+        SKM_CASE(26) SKM_CASE(27) SKM_CASE(28) SKM_CASE(29) SKM_CASE(30)
+#endif
+        SKM_CASE(31)
+#undef SKM_CASE
+        default: return mf_set_error("mf_debug_skm_count: k = %d is not compiled in", k);
+    }
+    if (rc < 0) return rc;
+    *out = D.release();
+    return MF_OK;
+}
+extern "C" int mf_debug_skm_count_info(const mf_skm_count_dbg *d, uint64_t *info) {
+    if (!d || !info) return mf_set_error("mf_debug_skm_count_info: NULL argument");
+    const uint64_t v[10] = {d->dcount.size(), d->tkeys.size(), d->overflow, d->n_all, d->n_redo, d->gathered, d->dk.size(), d->dfine.size(), d->launches, d->n_cu};
+    for (int i = 0; i < 10; i++) info[i] = v[i];
+    return MF_OK;
+}
+extern "C" int mf_debug_skm_count_copy(const mf_skm_count_dbg *d, uint32_t *dcount, uint64_t *toff, uint64_t *tkeys, uint16_t *tcnt, uint64_t *drop_hist, uint64_t *dk, uint16_t *dc,
+                                       uint64_t *dfine) {
+    if (!d) return mf_set_error("mf_debug_skm_count_copy: NULL argument");
+    if (dcount) std::copy(d->dcount.begin(), d->dcount.end(), dcount);
+    if (toff) std::copy(d->toff.begin(), d->toff.end(), toff);
+    if (tkeys) std::copy(d->tkeys.begin(), d->tkeys.end(), tkeys);
+    if (tcnt) std::copy(d->tcnt.begin(), d->tcnt.end(), tcnt);
+    if (drop_hist) std::copy(d->drop_hist.begin(), d->drop_hist.end(), drop_hist);
+    if (dk) std::copy(d->dk.begin(), d->dk.end(), dk);
+    if (dc) std::copy(d->dc.begin(), d->dc.end(), dc);
+    if (dfine) std::copy(d->dfine.begin(), d->dfine.end(), dfine);
     return MF_OK;
 }

@@ -318,7 +318,8 @@ class Context:
         _check(lib().mf_ctx_reset_timers(self.h))
 
     def stat(self, name):
-        """counters and gauges of the context: slice_restarts, device_parsed_files, device_parser_stepped_back, hipmalloc_calls, ..."""
+        """counters and gauges of the context: slice_restarts, device_parsed_files, device_parser_stepped_back, hipmalloc_calls,
+        skm_table_regrown (the dense table of a super-k-mer count grown again with entries to copy), ..."""
         v = lib().mf_ctx_stat(self.h, name.encode())
         if v < 0:
             raise MetafastError(lib().mf_last_error().decode(errors="replace"))

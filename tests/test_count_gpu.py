@@ -498,3 +498,47 @@ def test_option_names_and_ranges(gpu_ctx):
         for name, v in OPTION_DEFAULTS.items():
             gpu_ctx.set_option(name, v)
         _reset(gpu_ctx)          # (the shared context as the other tests of this module leave it)
+
+
+def _regrow_reads(k, bits1, B, n_batches, per_third, depth):
+    """reads of exactly k bases (one k-mer, one record, one partition each, assigned with skm_ref for the plan [bits1, B - bits1]): the reads of
+    the first batch's partitions are few distinct ones `depth` times each, the others all distinct; about `per_third` occurrences per batch"""
+    import skm_ref as S
+    rng = np.random.default_rng(1120)
+    n = 4 * per_third
+    b = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=(n, k))]
+    sc = S.Scan(b.reshape(-1), np.arange(n + 1, dtype=np.uint64) * np.uint64(k), k)
+    part = S.partition_of(sc.mh[np.arange(n) * k], bits1, B)
+    per_batch = ((1 << B) + n_batches - 1) // n_batches                             # skm_count_batches: PB partitions per batch
+    low = np.flatnonzero(part < per_batch)[:per_third // depth]
+    high = np.flatnonzero(part >= per_batch)[:(n_batches - 1) * per_third]
+    assert len(low) == per_third // depth and len(high) == (n_batches - 1) * per_third
+    rows = np.concatenate([np.repeat(low, depth), high])
+    reads = b[rows[rng.permutation(len(rows))]]
+    return reads.reshape(-1).copy(), np.arange(len(rows) + 1, dtype=np.uint64) * np.uint64(k), np.bincount(part[rows] // per_batch, minlength=n_batches)
+
+
+def test_skm_dense_table_grows_twice(gpu_ctx, oracle):
+    """skm_grow_table beyond its first call (the table grown from nothing): the first of three batches keeps a fortieth of its occurrences, so
+    the table is sized for little more than that; the second batch, all distinct, does not fit (grown with entries to copy: once), and the
+    estimate made then -- about half of what is to come, plus the slack of 4096 entries -- is too small for the third batch, all distinct
+    again and well over 10,000 k-mers (twice).  Reached with skm_batches = 3 on the plan 5 + 5 bits."""
+    _reset(gpu_ctx)
+    k, n_batches = 31, 3
+    b, o, per_batch = _regrow_reads(k, 5, 10, n_batches, 32000, 40)
+    assert per_batch[0] == 32000 and per_batch.sum() == 96000 and abs(per_batch[1] - 32000) < 1000      # occurrences per batch: about even
+    try:
+        for name, v in (("l1_bits", 5), ("l2_bits", 5), ("skm_dyn", 0), ("skm_batches", n_batches)):
+            gpu_ctx.set_option(name, v)
+        before = gpu_ctx.stat("skm_table_regrown")
+        t = _check(gpu_ctx, oracle, b, o, k)
+        grown = gpu_ctx.stat("skm_table_regrown") - before
+        assert len(t) == 800 + 2 * 32000 and t.records()[1] == 16                   # (the super-k-mer path, not its fallback)
+        assert grown >= 2, grown
+        # a count in one batch never copies: the table is sized once
+        gpu_ctx.set_option("skm_batches", 1)
+        before = gpu_ctx.stat("skm_table_regrown")
+        _check(gpu_ctx, oracle, b, o, k)
+        assert gpu_ctx.stat("skm_table_regrown") == before
+    finally:
+        _reset(gpu_ctx)
