@@ -686,6 +686,17 @@ int mf_dparse_gz(mf_ctx *ctx, const char *path, const void *packed, size_t packe
 // mem != nullptr: the file's content is in host memory already (mem_n bytes: a compressed file the host has inflated); path names it in messages
 static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size_t mem_n, int fmt, mf_buf<uint8_t> &bases, mf_buf<uint64_t> &offsets, uint64_t *n_reads, uint64_t *n_bases,
                          mf_buf<uint8_t> *filled = nullptr, int filled_qoff = 64);
+// what the passes hand to each other, and what the host has read back on the way
+struct dp_work {
+    mf_buf<unsigned int> flags; mf_buf<uint64_t> totals;
+    mf_buf<uint64_t> rec_a, rec_place; mf_buf<uint8_t> rec_b;      // FASTA: rec_seq [n_rec + 1], flag bytes; FASTQ: ls [n_lines + 1], drop [n_rec]
+    mf_buf<unsigned long long> blk_r, blk_b;
+    mf_buf<dp_fa_prefix> pre; mf_buf<unsigned long long> chunk_nl;
+    uint64_t n_rec = 0, n_lines = 0;
+    unsigned int anomaly = 0;                                       // the anomaly word as the host read it last
+    size_t slack = 64; bool canary = false;                         // room behind the bases; tests (mf_debug_dparse): more of it, and 0xA5 everywhere before pass 3
+};
+static int dparse_kernels(mf_ctx *ctx, const uint8_t *raw, size_t n, int fmt, int qoff, mf_buf<uint8_t> &bases, mf_buf<uint64_t> &offsets, uint64_t *n_reads, uint64_t *n_bases, dp_work &W);
 int mf_dparse_file(mf_ctx *ctx, const char *path, int fmt, mf_buf<uint8_t> &bases, mf_buf<uint64_t> &offsets, uint64_t *n_reads, uint64_t *n_bases) {
     return dparse_source(ctx, path, nullptr, 0, fmt, bases, offsets, n_reads, n_bases);
 }
@@ -725,7 +736,6 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
         if (qoff < 0) { shut(); return 1; }           // (whatever it is: the host parser says it in the reference's words)
     }
     MF_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     const uint64_t nc = (n + DP_CHUNK - 1) / DP_CHUNK;
     mf_buf<uint8_t> raw;
     if (filled) raw.swap(*filled);
@@ -736,23 +746,38 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
         if (rc != 0) return rc;
     }
     const double t1 = now();
-    mf_buf<unsigned int> flags; MF_TRY(flags.alloc(ctx, 4));
-    mf_buf<uint64_t> totals; MF_TRY(totals.alloc(ctx, 4));
+    dp_work W;
+    const int rc = dparse_kernels(ctx, raw.p, n, fmt, qoff, bases, offsets, n_reads, n_bases, W);
+    if (rc != 0) return rc;
+    static const bool env = getenv("MF_IO_TIMING") != nullptr;
+    if (env) fprintf(stderr, "[mf] device parser (%s, %.2f GB): read + H2D %.3f s, kernels %.3f s; %llu records, %llu reads kept\n", fmt == 1 ? "FASTA" : "FASTQ", n / 1e9,
+                     t1 - t0, now() - t1, (unsigned long long)W.n_rec, (unsigned long long)*n_reads);
+    return 0;
+}
+// the kernels: n bytes of text at raw (whole chunks + 64 bytes of room; whatever stands behind the n bytes is never looked at) -> (bases, offsets).
+// 0 = done, 1 = not a text the device parser is sure about (W.anomaly: why), < 0 = error.  Everything the passes hand to each other is W's and lives
+// as long as it (dparse_source drops it at once; mf_debug_dparse, the end of this file, reads it first).
+static int dparse_kernels(mf_ctx *ctx, const uint8_t *raw, size_t n, int fmt, int qoff, mf_buf<uint8_t> &bases, mf_buf<uint64_t> &offsets, uint64_t *n_reads, uint64_t *n_bases, dp_work &W) {
+    hipStream_t st = ctx->stream;
+    const uint64_t nc = (n + DP_CHUNK - 1) / DP_CHUNK;
+    mf_buf<unsigned int> &flags = W.flags; MF_TRY(flags.alloc(ctx, 4));
+    mf_buf<uint64_t> &totals = W.totals; MF_TRY(totals.alloc(ctx, 4));
     MF_HIP(hipMemsetAsync(flags.p, 0, 16, st));
     uint64_t h_tot[4] = {0, 0, 0, 0}; unsigned int h_flags[4] = {0, 0, 0, 0};
     auto anomaly = [&]() -> int {                   // (synchronises)
         if (hipMemcpyAsync(h_flags, flags.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+        W.anomaly = h_flags[0];
         return (int)h_flags[0];
     };
-    mf_buf<uint64_t> rec_a, rec_place; mf_buf<uint8_t> rec_b;
-    mf_buf<unsigned long long> blk_r, blk_b;
-    uint64_t n_rec = 0;
-    mf_buf<dp_fa_prefix> pre; mf_buf<unsigned long long> chunk_nl;
+    mf_buf<uint64_t> &rec_a = W.rec_a, &rec_place = W.rec_place; mf_buf<uint8_t> &rec_b = W.rec_b;
+    mf_buf<unsigned long long> &blk_r = W.blk_r, &blk_b = W.blk_b;
+    uint64_t &n_rec = W.n_rec;
+    mf_buf<dp_fa_prefix> &pre = W.pre; mf_buf<unsigned long long> &chunk_nl = W.chunk_nl;
     if (fmt == 1) {
         mf_buf<dp_fa_chunk> chunks; MF_TRY(chunks.alloc(ctx, nc)); MF_TRY(pre.alloc(ctx, nc));
         {
             mf_ktimer tm(ctx, "k_dparse");
-            k_dp_fa_count<<<(unsigned)nc, DP_T, 0, st>>>(raw.p, n, chunks.p, flags.p);
+            k_dp_fa_count<<<(unsigned)nc, DP_T, 0, st>>>(raw, n, chunks.p, flags.p);
             k_dp_fa_scan<<<1, 1024, 0, st>>>(chunks.p, nc, pre.p, totals.p);
         }
         MF_HIP(hipMemcpyAsync(h_tot, totals.p, 16, hipMemcpyDeviceToHost, st));
@@ -767,7 +792,7 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
         {
             mf_ktimer tm(ctx, "k_dparse");
             k_dp_set_u64<<<1, 1, 0, st>>>(rec_a.p + n_rec, h_tot[1]);
-            k_dp_fa_records<<<(unsigned)nc, DP_T, 0, st>>>(raw.p, n, pre.p, rec_a.p, reinterpret_cast<unsigned int *>(rec_b.p));
+            k_dp_fa_records<<<(unsigned)nc, DP_T, 0, st>>>(raw, n, pre.p, rec_a.p, reinterpret_cast<unsigned int *>(rec_b.p));
         }
     } else {
         MF_TRY(chunk_nl.alloc(ctx, nc + 1));
@@ -775,16 +800,16 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
         MF_HIP(hipMemsetAsync(dummy.p, 0, (nc + 1) * 8, st));
         {
             mf_ktimer tm(ctx, "k_dparse");
-            k_dp_fq_count<<<(unsigned)nc, DP_T, 0, st>>>(raw.p, n, chunk_nl.p, flags.p);
+            k_dp_fq_count<<<(unsigned)nc, DP_T, 0, st>>>(raw, n, chunk_nl.p, flags.p);
             k_dp_scan2<<<1, 1024, 0, st>>>(chunk_nl.p, dummy.p, nc, totals.p);
         }
         MF_HIP(hipMemcpyAsync(h_tot, totals.p, 16, hipMemcpyDeviceToHost, st));
         uint8_t last = 0;
-        MF_HIP(hipMemcpyAsync(&last, raw.p + (n - 1), 1, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(&last, raw + (n - 1), 1, hipMemcpyDeviceToHost, st));
         const int a = anomaly();
         if (a < 0) return mf_set_error("device parser: %s", hipGetErrorString(hipGetLastError()));
         if (a) return 1;
-        const uint64_t n_lines = h_tot[0] + (last != '\n' ? 1 : 0);
+        const uint64_t n_lines = W.n_lines = h_tot[0] + (last != '\n' ? 1 : 0);
         if (n_lines % 4) return 1;                      // ("Unexpected end of file. File is corrupted/Format mismatch.": the host parser says it)
         n_rec = n_lines / 4;
         if (n_rec == 0) return 1;
@@ -793,7 +818,7 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
         {
             mf_ktimer tm(ctx, "k_dparse");
             k_dp_set_u64<<<1, 1, 0, st>>>(rec_a.p + n_lines, last != '\n' ? (uint64_t)n + 1 : (uint64_t)n);
-            k_dp_fq_lines<<<(unsigned)nc, DP_T, 0, st>>>(raw.p, n, chunk_nl.p, (uint32_t)qoff, rec_a.p, rec_b.p, flags.p);
+            k_dp_fq_lines<<<(unsigned)nc, DP_T, 0, st>>>(raw, n, chunk_nl.p, (uint32_t)qoff, rec_a.p, rec_b.p, flags.p);
         }
     }
     // records: keep / drop, places
@@ -801,8 +826,8 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
     MF_TRY(blk_r.alloc(ctx, nb)); MF_TRY(blk_b.alloc(ctx, nb)); MF_TRY(rec_place.alloc(ctx, n_rec + 1));
     {
         mf_ktimer tm(ctx, "k_dparse");
-        if (fmt == 1) k_dp_rec_count<1><<<(unsigned)nb, DP_T, 0, st>>>(raw.p, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, flags.p);
-        else k_dp_rec_count<2><<<(unsigned)nb, DP_T, 0, st>>>(raw.p, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, flags.p);
+        if (fmt == 1) k_dp_rec_count<1><<<(unsigned)nb, DP_T, 0, st>>>(raw, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, flags.p);
+        else k_dp_rec_count<2><<<(unsigned)nb, DP_T, 0, st>>>(raw, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, flags.p);
         k_dp_scan2<<<1, 1024, 0, st>>>(blk_r.p, blk_b.p, nb, totals.p);
     }
     MF_HIP(hipMemcpyAsync(h_tot, totals.p, 16, hipMemcpyDeviceToHost, st));
@@ -812,24 +837,95 @@ static int dparse_source(mf_ctx *ctx, const char *path, const uint8_t *mem, size
         if (a) return 1;
     }
     const uint64_t nr = h_tot[0], nbases = h_tot[1];
-    MF_TRY(bases.alloc(ctx, nbases + 64)); MF_TRY(offsets.alloc(ctx, nr + 1));
+    MF_TRY(bases.alloc(ctx, nbases + W.slack)); MF_TRY(offsets.alloc(ctx, nr + 1));
+    if (W.canary) MF_HIP(hipMemsetAsync(bases.p, 0xA5, nbases + W.slack, st));       // (tests: a byte written outside [0, nbases), or not written inside, shows)
     {
         mf_ktimer tm(ctx, "k_dparse_emit");                        // (only a file the device parser has accepted gets here)
         MF_HIP(hipMemsetAsync(rec_place.p + n_rec, 0xFF, 8, st));
         k_dp_set_u64<<<1, 1, 0, st>>>(offsets.p + nr, nbases);
         if (fmt == 1) {
-            k_dp_rec_place<1><<<(unsigned)nb, DP_T, 0, st>>>(raw.p, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, rec_place.p, offsets.p);
-            k_dp_fa_emit<<<(unsigned)nc, DP_T, 0, st>>>(raw.p, n, pre.p, rec_place.p, bases.p);
+            k_dp_rec_place<1><<<(unsigned)nb, DP_T, 0, st>>>(raw, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, rec_place.p, offsets.p);
+            k_dp_fa_emit<<<(unsigned)nc, DP_T, 0, st>>>(raw, n, pre.p, rec_place.p, bases.p);
         } else {
-            k_dp_rec_place<2><<<(unsigned)nb, DP_T, 0, st>>>(raw.p, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, rec_place.p, offsets.p);
-            k_dp_fq_emit<<<(unsigned)nc, DP_T, 0, st>>>(raw.p, n, chunk_nl.p, rec_a.p, rec_place.p, bases.p);
+            k_dp_rec_place<2><<<(unsigned)nb, DP_T, 0, st>>>(raw, rec_a.p, rec_b.p, n_rec, blk_r.p, blk_b.p, rec_place.p, offsets.p);
+            k_dp_fq_emit<<<(unsigned)nc, DP_T, 0, st>>>(raw, n, chunk_nl.p, rec_a.p, rec_place.p, bases.p);
         }
     }
     MF_HIP(hipGetLastError());
     MF_HIP(hipStreamSynchronize(st));
     *n_reads = nr; *n_bases = nbases;
-    static const bool env = getenv("MF_IO_TIMING") != nullptr;
-    if (env) fprintf(stderr, "[mf] device parser (%s, %.2f GB): read + H2D %.3f s, kernels %.3f s; %llu records, %llu reads kept\n", fmt == 1 ? "FASTA" : "FASTQ", n / 1e9,
-                     t1 - t0, now() - t1, (unsigned long long)n_rec, (unsigned long long)nr);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// test hook (bound with ctypes by tests/test_dparse_units_gpu.py, not part of the C-ABI)
+// ---------------------------------------------------------------------------------------------
+//   mf_debug_dparse       n bytes of text from the host into a buffer of whole chunks + 64 bytes that holds fill_byte everywhere else (what stands behind the
+//                         text in the streamed count's and the .gz way's buffers is old text, not zeros), then dparse_kernels as dparse_source runs it, with
+//                         qoff from the caller (as mf_dparse_device) and 256 bytes of 0xA5 behind the bases (and under them, before pass 3)
+//                         -> *out (mf_debug_dparse_free); the return value is < 0 for an error only: the parser's 0 / 1 is info[0]
+//   mf_debug_dparse_info  info[0..8) = return code (0 taken, 1 stepped back), the anomaly word as the host read it last, n_rec, n_lines (FASTQ), reads kept,
+//                         bases kept, what there is to copy (0: nothing, 1: the record arrays, 2: everything), 0
+//   mf_debug_dparse_copy  rec_a: FASTA rec_seq [n_rec + 1], FASTQ ls [n_lines + 1]; rec_b: FASTA flag bytes [n_rec], FASTQ drop [n_rec]; rec_place [n_rec + 1]
+//                         (the last one: the sentinel), offsets [reads + 1], bases [bases + 256]; a null pointer: not wanted
+struct mf_dparse_dbg {
+    int rc = 0, have = 0; unsigned int anomaly = 0;
+    uint64_t n_rec = 0, n_lines = 0, n_reads = 0, n_bases = 0;
+    std::vector<uint64_t> rec_a, rec_place, offsets;
+    std::vector<uint8_t> rec_b, bases;
+};
+extern "C" void mf_debug_dparse_free(mf_dparse_dbg *d) { delete d; }
+static int dparse_debug_run(mf_ctx *ctx, const void *text, uint64_t n, int fmt, int qoff, int fill_byte, mf_dparse_dbg *D) {
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t nc = (n + DP_CHUNK - 1) / DP_CHUNK;
+    mf_buf<uint8_t> raw; MF_TRY(raw.alloc(ctx, nc * DP_CHUNK + 64));
+    MF_HIP(hipMemsetAsync(raw.p, fill_byte, nc * DP_CHUNK + 64, st));
+    MF_HIP(hipMemcpyAsync(raw.p, text, n, hipMemcpyHostToDevice, st));
+    dp_work W; W.slack = 256; W.canary = true;
+    mf_buf<uint8_t> bases; mf_buf<uint64_t> offsets;
+    const int rc = dparse_kernels(ctx, raw.p, n, fmt, qoff, bases, offsets, &D->n_reads, &D->n_bases, W);
+    if (rc < 0) return rc;
+    D->rc = rc; D->anomaly = W.anomaly; D->n_rec = W.n_rec; D->n_lines = W.n_lines;
+    D->have = rc == 0 ? 2 : (W.rec_a.p && W.rec_b.p && W.n_rec ? 1 : 0);
+    if (D->have >= 1) {
+        D->rec_a.resize((fmt == 1 ? W.n_rec : W.n_lines) + 1); D->rec_b.resize(W.n_rec);
+        MF_HIP(hipMemcpyAsync(D->rec_a.data(), W.rec_a.p, D->rec_a.size() * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(D->rec_b.data(), W.rec_b.p, D->rec_b.size(), hipMemcpyDeviceToHost, st));
+    }
+    if (D->have == 2) {
+        D->rec_place.resize(W.n_rec + 1); D->offsets.resize(D->n_reads + 1); D->bases.resize(D->n_bases + 256);
+        MF_HIP(hipMemcpyAsync(D->rec_place.data(), W.rec_place.p, D->rec_place.size() * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(D->offsets.data(), offsets.p, D->offsets.size() * 8, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(D->bases.data(), bases.p, D->bases.size(), hipMemcpyDeviceToHost, st));
+    }
+    MF_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int mf_debug_dparse(mf_ctx *ctx, const void *text, uint64_t n, int fmt, int qoff, int fill_byte, mf_dparse_dbg **out) {
+    if (!ctx || !text || !out) return mf_set_error("mf_debug_dparse: NULL argument");
+    *out = nullptr;
+    if (fmt != 1 && fmt != 2) return mf_set_error("mf_debug_dparse: fmt = %d (1 FASTA, 2 FASTQ)", fmt);
+    if (n < 1 || n > ((uint64_t)1 << 30)) return mf_set_error("mf_debug_dparse: %llu bytes of text (1 .. 2^30)", (unsigned long long)n);
+    if (qoff < 0 || qoff > 126 || fill_byte < 0 || fill_byte > 255) return mf_set_error("mf_debug_dparse: qoff = %d, fill_byte = %d", qoff, fill_byte);
+    mf_dparse_dbg *D = new mf_dparse_dbg;
+    const int rc = dparse_debug_run(ctx, text, n, fmt, qoff, fill_byte, D);
+    if (rc != 0) { delete D; return rc; }
+    *out = D;
+    return 0;
+}
+extern "C" int mf_debug_dparse_info(const mf_dparse_dbg *d, uint64_t *info) {
+    if (!d || !info) return mf_set_error("mf_debug_dparse_info: NULL argument");
+    const uint64_t v[8] = {(uint64_t)d->rc, d->anomaly, d->n_rec, d->n_lines, d->n_reads, d->n_bases, (uint64_t)d->have, 0};
+    memcpy(info, v, sizeof v);
+    return 0;
+}
+extern "C" int mf_debug_dparse_copy(const mf_dparse_dbg *d, uint64_t *rec_a, uint8_t *rec_b, uint64_t *rec_place, uint64_t *offsets, uint8_t *bases) {
+    if (!d) return mf_set_error("mf_debug_dparse_copy: NULL argument");
+    if (rec_a && !d->rec_a.empty()) memcpy(rec_a, d->rec_a.data(), d->rec_a.size() * 8);
+    if (rec_b && !d->rec_b.empty()) memcpy(rec_b, d->rec_b.data(), d->rec_b.size());
+    if (rec_place && !d->rec_place.empty()) memcpy(rec_place, d->rec_place.data(), d->rec_place.size() * 8);
+    if (offsets && !d->offsets.empty()) memcpy(offsets, d->offsets.data(), d->offsets.size() * 8);
+    if (bases && !d->bases.empty()) memcpy(bases, d->bases.data(), d->bases.size());
     return 0;
 }

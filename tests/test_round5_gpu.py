@@ -480,6 +480,33 @@ def test_device_parser_steps_back(gpu_ctx, oracle, tmp_path):
         gpu_ctx.set_option("device_parse_min_bytes", 1 << 20)
 
 
+def test_device_parser_steps_back_for_the_expected_reason(gpu_ctx):
+    """the texts of test_device_parser_steps_back through mf_debug_dparse (tests/test_dparse_units_gpu.py): the anomaly word is the one
+    tests/dparse_ref.py expects at the stage the host returns at, and it holds the bit each text is made for -- a step back for another
+    reason would look the same from outside"""
+    import dparse_ref as R
+    from test_dparse_units_gpu import check, run_debug
+    rng = np.random.default_rng(22)
+    good_fa = _fa_text(rng, 300, 0)
+    good_fq = _fq_text(rng, 300)
+    texts = {"lone_cr.fa": (good_fa.replace(b"\n>read_7 ", b"\r>read_7 ", 1), R.A_LONE_CR), "lone_cr_in_header.fa": (good_fa.replace(b"read_9 some", b"read_9\rACGT", 1), R.A_LONE_CR),
+             "empty_lines.fq": (good_fq.replace(b"\n@r20\n", b"\n\n@r20\n", 1), R.A_EMPTY_LINE), "leading_empty.fq": (b"\n" + good_fq, R.A_EMPTY_LINE),
+             "crlf_empty.fq": (good_fq.replace(b"\n@r30\n", b"\n\r\n@r30\n", 1), R.A_EMPTY_LINE),
+             "bad_char.fa": (good_fa.replace(b"\nA", b"\nJ", 1), R.A_BAD_CHAR), "bad_char.fq": (good_fq.replace(b"\nA", b"\n#", 1), R.A_BAD_CHAR),
+             "truncated.fq": (good_fq[: len(good_fq) // 2], 0),                   # (lines that are no multiple of four: no bit, or whatever the cut leaves -- the reference says which)
+             "lengths.fq": (good_fq.replace(b"\n+\n", b"\n+\nI", 1), R.A_LENGTHS), "structure.fq": (good_fq.replace(b"\n@r5\n", b"\nr5\n", 1), R.A_STRUCTURE),
+             "bad_qual.fq": (good_fq[:-2] + b"\x1f\n", R.A_BAD_QUAL)}
+    for name, (text, bit) in texts.items():
+        fmt = 1 if name.endswith(".fa") else 2
+        qoff = R.sniff_qoff(text) if fmt == 2 else 64
+        ref = R.parse(text, fmt, qoff)
+        assert ref.rc == 1 and ref.anomaly & bit == bit, (name, ref.names())
+        for fill in (ord("A"), ord("\r")):
+            out = run_debug(gpu_ctx, text, fmt, qoff, fill)
+            check(out, ref, name, bit=bit)
+            assert out["rc"] == 1, name
+
+
 @pytest.mark.parametrize("k", [21, 23, 25])
 def test_low_complexity_reads_with_the_short_minimizer(gpu_ctx, oracle, k):
     """k <= 25 takes 13-mers as minimizers (mf_skm_m), with their own hash seed: homopolymer and microsatellite stretches between random flanks --
