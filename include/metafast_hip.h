@@ -254,8 +254,20 @@ struct mf_gfa;
 int  mf_wcomps_graph_device(mf_ctx *ctx, mf_wcomps *c, mf_wtable *const *samples, int n_samples, int coverage, struct mf_gfa **out);
 int  mf_comp2graph_wide(mf_ctx *ctx, const char *components_bin, int k, const char *const *kmers_files, int n_files, int coverage,
                         const char *out_gfa, uint64_t *n_components, uint64_t *n_segments, uint64_t *n_links);
+/* [mf_comps_from_sequences_device / mf_seq2comp] seq2comp on 2k-bit k-mers (mf_wseq2comp.hip): the semantics of the k <= 31 entry points
+ * word for word -- one component per sequence in sequence order, members the distinct canonical k-mers, size their number, weight
+ * max(0, L - k + 1), thr 0, a sequence shorter than k an empty component -- with the members ASCENDING in (hi, lo) inside every component
+ * on the device, as every mf_wcomps has them.  32 <= k <= 63; the limits and their messages are the narrow tool's (n_seqs, members and the
+ * k-mers of one sequence below 2^32 - 1; offsets that go backwards or do not end at n_bases are errors).  Sequences of up to
+ * mf_ctx_stat("ws2c_lds_max") k-mers are sorted in LDS, longer ones by three pair sorts; options "s2c_lds" and "s2c_batch_pairs" and stat
+ * "s2c_sort_batches" as for k <= 31.  The file form keeps one file resident at a time, writes components_bin through mf_wcomps_write and
+ * the three-column stat_txt (may be NULL) itself; nothing is written when an argument is refused. */
+int  mf_wcomps_from_sequences_device(mf_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases, int k,
+                                     mf_wcomps **out);
+int  mf_seq2comp_wide(mf_ctx *ctx, const char *const *files, int nfiles, int k, const char *components_bin, const char *stat_txt,
+                      uint64_t *n_components, uint64_t *per_file);
 
-/* ---- A5/A6  .kmers.bin / .stat.txt --------------------------------------------------- */
+/* ---- A5/A6 .kmers.bin / .stat.txt --------------------------------------------------- */
 /* replaces IOUtils.printKmers (src/io/IOUtils.java:45-71; KmersCounterMain.java:99): 10-byte
  * big-endian records (int64 k-mer, int16 count) for count > threshold, ascending key order;
  * histogram of ALL counts to stat_txt (may be NULL). */

@@ -90,6 +90,7 @@ extern "C" int mf_wcomps_stats(const mf_wcomps *, uint64_t *, uint64_t *) __attr
 extern "C" void mf_wcomps_destroy(mf_wcomps *) __attribute__((weak));
 extern "C" int mf_features_wide(mf_ctx *, const char *, const char *, int, int, const char *, const char *) __attribute__((weak));
 extern "C" int mf_comp2seq_wide(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_seq2comp_wide(mf_ctx *, const char *const *, int, int, const char *, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_comp2graph_wide(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
 
 using std::string;
@@ -391,7 +392,7 @@ static bool wide_k(int k) {
     return true;
 }
 // view and bin2fasta read wide files on the host and call no library function: wide without a look at the library's symbols
-// (comp2graph calls ONE entry point, on wide files somebody else wrote, and reports it by name itself)
+// (comp2graph and seq2comp call ONE entry point each -- on wide files somebody else wrote, or writing them itself -- and report it by name themselves)
 static bool wide_host_k(int k) {
     if (!g_wide || k <= 31) return false;
     if (k > 63) die("The size of k-mer must be no more than 63.");
@@ -1563,19 +1564,21 @@ static vector<PV> tool_seq2comp(Run &r) {
     // (a LongArraySet with a linear scan per add there: quadratic in the sequence's length) -- here a segmented set-build on the
     // device (mf_seq2comp).  Components in file order, then record order (the reference: as its thread pool finishes); a sequence
     // shorter than k keeps its place as an empty component
+    // (--wide-kmers and k > 31: the same on 2k-bit k-mers into a wide components.bin, mf_seq2comp_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const vector<string> files = r.a.list("sequences");
     const string cf = r.str("components-file"), sf = r.wd + "/components-stat.txt";
     for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
-    r.entry(mf_seq2comp != nullptr, "mf_seq2comp");
+    if (wide) r.entry(mf_seq2comp_wide != nullptr, "mf_seq2comp_wide"); else r.entry(mf_seq2comp != nullptr, "mf_seq2comp");
     mf_ctx *ctx = r.ctx();
     logmsg("DEBUG", "Loading sequences from files...");
     auto fp = cptrs(files);
     vector<uint64_t> per(files.size() + 1, 0);
     uint64_t nc = 0;
     mkparent(cf);
-    check(mf_seq2comp(ctx, files.empty() ? nullptr : fp.data(), (int)files.size(), k, cf.c_str(), sf.c_str(), &nc, per.data()));
+    check((wide ? mf_seq2comp_wide : mf_seq2comp)(ctx, files.empty() ? nullptr : fp.data(), (int)files.size(), k, cf.c_str(), sf.c_str(), &nc, per.data()));
     for (size_t i = 0; i < files.size(); i++) {          // (the reference logs each pair as it goes; the numbers are the same)
         logmsg("INFO", "Loading file %s...", basename_of(files[i]).c_str());
         logmsg("INFO", "%llu components added", (unsigned long long)per[i]);

@@ -7,7 +7,7 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_cp_|k_specific|k_uk_")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
 # column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip, mf_wcomp2graph.hip; one thread per run of positions, per
 # run, per record, or one wave per record: mf_comppaths.hip)
@@ -24,6 +24,10 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
           # (k_s2c_lds: waves that share a workgroup's LDS table between wave-level barriers, two workgroups per CU)
           "mf_seq2comp": ["k_s2c_sizes", "k_s2c_lds", "k_s2c_pairs", "k_s2c_heads", "k_s2c_seg_heads", "k_s2c_seg_sizes", "k_s2c_compact", "k_s2c_place",
                           "k_s2c_shift"],
+          # (k_ws2c_lds: the same teams on 2k-bit k-mers -- a sequence's k-mers sorted in two LDS word arrays between team barriers; a spill
+          # would cost it the four workgroups per CU its 32 KiB of LDS leave room for)
+          "mf_wseq2comp": ["k_ws2c_sizes", "k_ws2c_lds", "k_ws2c_pairs", "k_ws2c_gather64", "k_ws2c_gather32", "k_ws2c_heads", "k_ws2c_seg_sizes",
+                           "k_ws2c_compact", "k_ws2c_place", "k_ws2c_shift"],
           "mf_comppaths": ["k_cp_select", "k_cp_members", "k_cp_heads", "k_cp_distinct", "k_cp_maxlist", "k_cp_split", "k_cp_join", "k_cp_sizes", "k_cp_mark",
                            "k_cp_pair", "k_cp_keep", "k_cp_bump", "k_cp_records", "k_cp_copy", "k_cp_keys", "k_cp_widths", "k_cp_slot_bytes",
                            "k_cp_write_head", "k_cp_write_bases"],

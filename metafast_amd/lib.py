@@ -59,6 +59,8 @@ _SIGS = {
     "mf_wcomps_unitigs_device": (i32, [vp, vp, i32, pvp]),
     "mf_comp2seq_wide": (i32, [vp, cp, i32, i32, cp, pu64, pu64]),
     "mf_wcomps_graph_device": (i32, [vp, vp, vp, i32, i32, pvp]),
+    "mf_wcomps_from_sequences_device": (i32, [vp, vp, vp, u64, u64, i32, pvp]),
+    "mf_seq2comp_wide": (i32, [vp, C.POINTER(cp), i32, i32, cp, cp, pu64, vp]),
     "mf_comp2graph_wide": (i32, [vp, cp, i32, C.POINTER(cp), i32, i32, cp, pu64, pu64, pu64]),
     "mf_comm_create_local": (i32, [vp, i32, vp]),
     "mf_comm_rccl_id": (i32, [vp]),
@@ -589,6 +591,23 @@ class Context:
         per = np.zeros(max(len(files), 1), dtype=np.uint64)
         _check(lib().mf_seq2comp(self.h, _cfiles(files) if files else None, len(files), k, os.fsencode(components_bin), _opt(stat_txt), C.byref(n),
                                  per.ctypes.data))
+        return n.value, [int(x) for x in per[:len(files)]]
+
+    def wcomps_from_sequences(self, d_bases, d_offsets, n_seqs, n_bases, k):
+        """NO-REFERENCE EXTENSION, 32 <= k <= 63: comps_from_sequences on 2k-bit k-mers -> WideComps, members ascending in (hi, lo)
+        inside every component"""
+        c = C.c_void_p()
+        _check(lib().mf_wcomps_from_sequences_device(self.h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_seqs, n_bases, k, C.byref(c)))
+        return WideComps(self, c)
+
+    def seq2comp_wide(self, files, k, components_bin, stat_txt=None):
+        """NO-REFERENCE EXTENSION, 32 <= k <= 63: seq2comp -> a wide components_bin and the three-column stat_txt; returns (components,
+        components per file)"""
+        files = list(files)
+        n = C.c_uint64()
+        per = np.zeros(max(len(files), 1), dtype=np.uint64)
+        _check(lib().mf_seq2comp_wide(self.h, _cfiles(files) if files else None, len(files), k, os.fsencode(components_bin), _opt(stat_txt), C.byref(n),
+                                      per.ctypes.data))
         return n.value, [int(x) for x in per[:len(files)]]
 
     # ---- component-paths ----
