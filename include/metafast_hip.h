@@ -442,6 +442,18 @@ int  mf_paths_write(const mf_paths *p, const char *out_dir, uint64_t *n_paths);
 int  mf_component_paths(mf_ctx *ctx, const char *components_bin, int k, const char *const *files, int nfiles, const uint32_t *selection,
                         uint64_t n_selection, int min_len, uint64_t max_paths, const char *out_dir, uint64_t *n_components,
                         uint64_t *n_paths);
+/* NO-REFERENCE EXTENSION, 32 <= k <= 63 (mf_wcomppaths.hip): component-paths on wide components, the semantics of the k <= 31 entry
+ * points on 2k-bit k-mers word for word.  mf_paths_create_wide gives the SAME handle type (the components know their k): mf_paths_add,
+ * mf_paths_finish, mf_paths_stats, mf_paths_slots, mf_paths_text, mf_paths_write and mf_paths_destroy work on it unchanged -- the handle
+ * remembers its width, and only the marking kernel's look at a k-mer differs (a 128-bit roll, an index of 8-byte slots over the distinct
+ * members as two word arrays).  The selection's rules, the errors and their texts, the rounding of weight / size, the cap and the limits
+ * are those of mf_paths_create.  The file form loads through mf_wcomps_load (a file of another width or another k is its error), keeps
+ * one sequence file resident at a time, and writes nothing before the components file has been accepted. */
+int  mf_paths_create_wide(mf_ctx *ctx, mf_wcomps *c, const uint32_t *selection, uint64_t n_selection, int min_len, uint64_t max_paths,
+                          mf_paths **out);
+int  mf_component_paths_wide(mf_ctx *ctx, const char *components_bin, int k, const char *const *files, int nfiles,
+                             const uint32_t *selection, uint64_t n_selection, int min_len, uint64_t max_paths, const char *out_dir,
+                             uint64_t *n_components, uint64_t *n_paths);
 
 /* ---- A9-A11 on several GPUs: every rank owns a shard of the cutter table ---------------------
  * The cutter table and the components step join ALL samples (ComponentCutterMain.runImpl,

@@ -92,6 +92,7 @@ extern "C" int mf_features_wide(mf_ctx *, const char *, const char *, int, int, 
 extern "C" int mf_comp2seq_wide(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_seq2comp_wide(mf_ctx *, const char *const *, int, int, const char *, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_comp2graph_wide(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
+extern "C" int mf_paths_create_wide(mf_ctx *, mf_wcomps *, const uint32_t *, uint64_t, int, uint64_t, mf_paths **) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -1594,8 +1595,10 @@ static vector<PV> tool_component_paths(Run &r) {
     // one lookup per k-mer position in an index over the members of all selected components, the runs found, paired, capped, sorted
     // and printed on the device (mf_comppaths.hip).  Without a selection the reference logs its message and ends cleanly; here the
     // run fails with it.  A number out of range is an exception there and an error here.
+    // (--wide-kmers and k > 31: a wide components.bin through mf_wcomps_load, the same handle from mf_paths_create_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const string cf = r.str("components-file"), od = r.str("output-dir");
     const vector<string> files = r.a.list("seq");
     const bool all = r.a.flag("all-components");
@@ -1610,21 +1613,29 @@ static vector<PV> tool_component_paths(Run &r) {
     if (!all && sel.empty()) die("No components to process!!! Do you forget to set --all-components or --components n1,n2,...?");
     if (!exists(cf)) die("Can't load components: file not found (%s)", cf.c_str());
     for (auto &f : files) if (!exists(f)) die("Can't load sequences: file not found (%s)", f.c_str());
+    if (wide) r.entry(mf_paths_create_wide && mf_wcomps_load && mf_wcomps_stats && mf_wcomps_destroy, "mf_paths_create_wide");
     r.entry(mf_paths_create && mf_paths_add && mf_paths_finish && mf_paths_destroy && mf_paths_slots && mf_paths_write && mf_paths_stats && mf_comps_load &&
             mf_comps_set_k && mf_comps_stats && mf_comps_destroy && mf_reads_load && mf_reads_stats && mf_reads_device_view && mf_reads_destroy, "mf_paths_create");
     mf_ctx *ctx = r.ctx();
     logmsg("DEBUG", "Loading components...");
     mf_comps *c = nullptr;
-    check(mf_comps_load(ctx, cf.c_str(), &c));
-    check(mf_comps_set_k(c, k));
+    mf_wcomps *wc = nullptr;
     uint64_t nc = 0;
-    check(mf_comps_stats(c, &nc, nullptr));
+    if (wide) {
+        check(mf_wcomps_load(ctx, cf.c_str(), k, &wc));
+        check(mf_wcomps_stats(wc, &nc, nullptr));
+    } else {
+        check(mf_comps_load(ctx, cf.c_str(), &c));
+        check(mf_comps_set_k(c, k));
+        check(mf_comps_stats(c, &nc, nullptr));
+    }
     logmsg("INFO", "%s components loaded from %s", group_digits(nc).c_str(), cf.c_str());
     if (all && nc == 0) die("No components to process!!!");
     logmsg("DEBUG", "Preparing...");
     mf_paths *paths = nullptr;
     const uint64_t max_paths = 1000000;                                   // MAX_PATHS_COUNT (:30)
-    check(mf_paths_create(ctx, c, all ? nullptr : sel.data(), all ? 0 : sel.size(), min_len, max_paths, &paths));
+    if (wide) check(mf_paths_create_wide(ctx, wc, all ? nullptr : sel.data(), all ? 0 : sel.size(), min_len, max_paths, &paths));
+    else check(mf_paths_create(ctx, c, all ? nullptr : sel.data(), all ? 0 : sel.size(), min_len, max_paths, &paths));
     logmsg("DEBUG", "Loading sequences and extracting paths...");
     for (auto &f : files) {                                               // one file resident at a time
         logmsg("INFO", "Loading file %s...", basename_of(f).c_str());
@@ -1650,7 +1661,7 @@ static vector<PV> tool_component_paths(Run &r) {
     uint64_t np = 0;
     check(mf_paths_write(paths, od.c_str(), &np));
     mf_paths_destroy(paths);
-    mf_comps_destroy(c);
+    if (wide) mf_wcomps_destroy(wc); else mf_comps_destroy(c);
     logmsg("INFO", "Paths for %llu component(s) were saved in directory %s", (unsigned long long)nslots, od.c_str());
     return {};
 }

@@ -31,6 +31,8 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
           "mf_comppaths": ["k_cp_select", "k_cp_members", "k_cp_heads", "k_cp_distinct", "k_cp_maxlist", "k_cp_split", "k_cp_join", "k_cp_sizes", "k_cp_mark",
                            "k_cp_pair", "k_cp_keep", "k_cp_bump", "k_cp_records", "k_cp_copy", "k_cp_keys", "k_cp_widths", "k_cp_slot_bytes",
                            "k_cp_write_head", "k_cp_write_bases"],
+          # (the member side and the marking kernel on 2k-bit k-mers: k_cp_mark of mf_cp.h instantiated over 128-bit keys)
+          "mf_wcomppaths": ["k_cp_wmembers", "k_cp_gather64", "k_cp_gather32", "k_cp_wheads", "k_cp_wdistinct", "k_cp_mark"],
           # (the row kernels of specific-kmers and specific-kmers-3 keep a row in LDS: a spill would cost them their occupancy)
           "mf_specific": ["k_specific_select", "k_specific_gather", "k_specific_rows_thread", "k_specific_rows_wave"],
           "mf_stats": ["k_specific3_rows_thread", "k_specific3_rows_wave"], "mf_kmersets": ["k_uk_knock"]}

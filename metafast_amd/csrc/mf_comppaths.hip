@@ -20,17 +20,14 @@
 //   finish   one stable sort by (slot, length descending); number inside the slot and byte width per record, a scan, and the writer
 //            kernels format the headers (decimal numbers on the device) and copy the bases with a newline every 70.
 // Nothing is truncated silently: what does not fit a 32-bit count, or HBM, is an error.
-#include "mf_common.h"
+// 32 <= k <= 63 (mf_wcomppaths.hip) shares all of this but the member index and the key side of k_cp_mark: mf_cp.h.
+#include "mf_cp.h"
 #include "mf_roll.h"
 #include <algorithm>
 #include <cmath>
 #include <memory>
 #include <sys/stat.h>
 #include <errno.h>
-
-#define CP_RUN 32                     // positions per thread of k_cp_mark
-#define CP_WG 256                     // threads per workgroup: a workgroup covers CP_RUN * CP_WG = 8192 positions
-#define CP_NONE 0xFFFFFFFFu
 
 // ---- create: the member index over the selected components ----
 __global__ void k_cp_select(const uint32_t *__restrict__ comp, const uint32_t *__restrict__ slot_of, uint64_t nk, uint32_t *__restrict__ flag) {
@@ -91,53 +88,17 @@ __global__ void k_cp_sizes(const uint64_t *__restrict__ off, uint64_t n, int k, 
     runs[i] = (uint32_t)((ni + CP_RUN - 1) / CP_RUN);
 }
 
-struct cp_members { mf_index_view ix; const uint32_t *lo; const uint32_t *slots; };
-struct cp_marks { uint32_t *slot; uint64_t *pos; };
-
-// thread r: the run of CP_RUN positions it owns belongs to the last sequence s with srun[s] <= r.  WRITE = false: cnt_s[r] / cnt_e[r] =
-// the starts / ends among its positions; WRITE = true: they go out at off_s[r] / off_e[r] as (slot, off[s] + position)
-template <bool WRITE>
-__global__ __launch_bounds__(CP_WG) void k_cp_mark(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ off, const uint64_t *__restrict__ srun, uint64_t n_seqs,
-                                                   uint64_t n_runs, int k, cp_members M, uint32_t *__restrict__ cnt_s, uint32_t *__restrict__ cnt_e,
-                                                   const uint64_t *__restrict__ off_s, const uint64_t *__restrict__ off_e, cp_marks S, cp_marks E) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_runs) return;
-    uint64_t a = 0, b = n_seqs;                            // the last s with srun[s] <= r (sequences without positions take no run: they are skipped)
-    while (b - a > 1u) { const uint64_t m = a + (b - a) / 2u; if (srun[m] <= r) a = m; else b = m; }
-    const uint64_t o = off[a];
-    const uint32_t ni = (uint32_t)(off[a + 1] - o) - (uint32_t)k + 1u, p0 = (uint32_t)(r - srun[a]) * CP_RUN;
-    const uint32_t cnt = ni - p0 < CP_RUN ? ni - p0 : CP_RUN;                 // (p0 < ni: the sequence has ceil(ni / CP_RUN) runs)
-    const uint32_t first = p0 ? p0 - 1u : 0u, total = (p0 ? 1u : 0u) + cnt + (p0 + cnt < ni ? 1u : 0u);
-    uint64_t ws = WRITE ? off_s[r] : 0ull, we = WRITE ? off_e[r] : 0ull;
-    uint32_t ns = 0, ne = 0;
-    uint32_t plo = 0, phi = 0, clo = 0, chi = 0;          // the listings of the position before (p) and of the current one (c): empty outside the sequence
-    // position q with listings [clo, chi), its neighbours' [plo, phi) and [nlo, nhi): all three ascend by slot
-    auto decide = [&](uint32_t q, uint32_t nlo, uint32_t nhi) {
-        uint32_t jp = plo, jn = nlo;
-        for (uint32_t i = clo; i < chi; i++) {
-            const uint32_t c = M.slots[i];
-            while (jp < phi && M.slots[jp] < c) jp++;
-            while (jn < nhi && M.slots[jn] < c) jn++;
-            if (!(jp < phi && M.slots[jp] == c)) {
-                if (WRITE) { S.slot[ws] = c; S.pos[ws] = o + q; ws++; }
-                ns++;
-            }
-            if (!(jn < nhi && M.slots[jn] == c)) {
-                if (WRITE) { E.slot[we] = c; E.pos[we] = o + q; we++; }
-                ne++;
-            }
-        }
-    };
-    s2c_roll(bases + o + first, total, k, [&](uint32_t i, uint64_t key) {
-        uint32_t idx, val, nlo = 0, nhi = 0;
-        if (mf_index_find(M.ix, key, &idx, &val)) { nlo = M.lo[idx]; nhi = M.lo[idx + 1]; }
-        const uint32_t q = first + i - 1u;                 // the current position, if there is one yet
-        if (i && q >= p0) decide(q, nlo, nhi);
-        plo = clo; phi = chi; clo = nlo; chi = nhi;
-    });
-    if (p0 + cnt == ni) decide(ni - 1u, 0u, 0u);           // the sequence's last position: nothing follows
-    if (!WRITE) { cnt_s[r] = ns; cnt_e[r] = ne; }
-}
+// k <= 31: s2c_roll and the index of a k-mer table (k_cp_mark: mf_cp.h)
+struct cp_keys64 {
+    mf_index_view ix;
+    template <typename F> __device__ __forceinline__ void each(const uint8_t *__restrict__ p, uint32_t count, int k, F &&f) const {
+        s2c_roll(p, count, k, [&](uint32_t i, uint64_t key) {
+            uint32_t idx, val;
+            const bool found = mf_index_find(ix, key, &idx, &val);
+            f(i, found, idx);
+        });
+    }
+};
 
 // the starts and the ends, each sorted by slot: run i = (ss[i], sp[i] .. ep[i]); flag[i] = long enough; head[slot] = the slot's first run
 __global__ void k_cp_pair(const uint32_t *__restrict__ ss, const uint64_t *__restrict__ sp, const uint32_t *__restrict__ es, const uint64_t *__restrict__ ep, uint64_t n,
@@ -246,29 +207,6 @@ __global__ __launch_bounds__(256) void k_cp_write_bases(const uint64_t *__restri
 // =============================================================================================
 // host side
 // =============================================================================================
-struct mf_paths {
-    mf_ctx *ctx = nullptr;
-    int k = 0; int64_t min_len = 0; uint64_t max_paths = 0;
-    uint64_t n_slots = 0;
-    std::vector<uint32_t> comp_no;                       // per slot: the component's number (from 1)
-    std::vector<int32_t> W;                              // per slot: Math.round(weight / (double) size)
-    uint64_t nm = 0, nd = 0; uint32_t max_listings = 0;  // listings, distinct k-mers, the most listings of one k-mer
-    mf_index index; size_t index_bytes = 0;
-    mf_buf<uint32_t> lo, slots;
-    mf_buf<unsigned long long> count;                    // per slot: paths kept so far
-    uint64_t n_rec = 0, n_text = 0, rec_cap = 0, text_cap = 0;       // the path store
-    mf_buf<uint32_t> rslot, rlen; mf_buf<uint64_t> roff; mf_buf<uint8_t> text;
-    bool finished = false;
-    std::vector<uint64_t> h_count, h_boff;               // per slot: paths; first byte of the slot's text (n_slots + 1)
-    mf_buf<uint8_t> out; uint64_t out_bytes = 0;
-    ~mf_paths() {
-        if (index.slots) mf_release(ctx, index.slots, index_bytes);
-    }
-};
-
-static inline unsigned cp_grid(uint64_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-static int cp_slot_bits(uint64_t n_slots) { int cb = 1; while (cb < 32 && (1ull << cb) < n_slots) cb++; return cb; }
-
 // out[0 .. n] = exclusive prefix of in, *total (device) = out[n]; the items may be anything below 2^32
 static int cp_scan(mf_ctx *ctx, const uint32_t *in, uint64_t *out, uint64_t n, uint64_t *total) {
     if (n <= 65536) return mf_scan<1>(ctx, in, out, n, total);               // (one workgroup, 64-bit sums)
@@ -292,6 +230,69 @@ template <typename T> static int cp_grow(mf_ctx *ctx, mf_buf<T> &b, uint64_t use
     return MF_OK;
 }
 
+// ---- create, the steps that see no k-mer: both widths (mf_cp.h) ----
+int cp_slots_of(mf_paths *P, uint64_t n, const uint64_t *sizes, const int64_t *weights, const uint32_t *selection, uint64_t n_selection,
+                std::vector<uint32_t> &slot_of) {
+    mf_ctx *ctx = P->ctx;
+    // the slots: the selection without its repeats, in the order given; all components in theirs
+    slot_of.assign((size_t)std::max<uint64_t>(n, 1), CP_NONE);
+    if (!selection) {
+        for (uint64_t i = 0; i < n; i++) { slot_of[i] = (uint32_t)i; P->comp_no.push_back((uint32_t)i + 1u); }
+    } else {
+        for (uint64_t j = 0; j < n_selection; j++) {
+            const uint32_t no = selection[j];
+            if (no < 1 || (uint64_t)no > n) return mf_set_error("component-paths: there is no component %u (the file holds %llu, numbered from 1)", no, (unsigned long long)n);
+            if (slot_of[no - 1] != CP_NONE) continue;
+            slot_of[no - 1] = (uint32_t)P->comp_no.size();
+            P->comp_no.push_back(no);
+        }
+    }
+    const uint64_t ns = P->n_slots = P->comp_no.size();
+    for (uint64_t s = 0; s < ns; s++) {
+        const uint64_t size = sizes[P->comp_no[s] - 1]; const int64_t weight = weights[P->comp_no[s] - 1];
+        double w = 0.0;
+        if (size) {                                        // (a component without members matches nothing: its weight is never printed)
+            w = floor((double)weight / (double)size + 0.5);      // Math.round
+            if (!(w >= -2147483648.0 && w <= 2147483647.0))
+                return mf_set_error("component-paths: the average k-mer weight of component %u does not fit a 32-bit integer", P->comp_no[s]);
+        }
+        P->W.push_back((int32_t)w);
+    }
+    MF_TRY(P->count.alloc(ctx, ns));
+    MF_HIP(hipMemsetAsync(P->count.p, 0, (ns ? ns : 1) * 8, ctx->stream));
+    return MF_OK;
+}
+int cp_select(mf_ctx *ctx, const uint32_t *d_comp, uint64_t n_comps, uint64_t nk, const std::vector<uint32_t> &slot_of, mf_buf<uint32_t> &dslot,
+              mf_buf<uint32_t> &flag, mf_buf<uint64_t> &rank, uint64_t *nm) {
+    hipStream_t st = ctx->stream;
+    mf_buf<uint64_t> tot;
+    MF_TRY(dslot.alloc(ctx, n_comps)); MF_TRY(flag.alloc(ctx, nk)); MF_TRY(rank.alloc(ctx, nk + 1)); MF_TRY(tot.alloc(ctx, 1));
+    MF_HIP(hipMemcpyAsync(dslot.p, slot_of.data(), n_comps * 4, hipMemcpyHostToDevice, st));
+    k_cp_select<<<cp_grid(nk), 256, 0, st>>>(d_comp, dslot.p, nk, flag.p);
+    MF_TRY(mf_scan<1>(ctx, flag.p, rank.p, nk, tot.p));
+    unsigned long long h = 0;
+    MF_HIP(hipMemcpyAsync(&h, tot.p, 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipStreamSynchronize(st));
+    *nm = h;
+    return MF_OK;
+}
+int cp_max_listings(mf_paths *P) {
+    mf_ctx *ctx = P->ctx;
+    hipStream_t st = ctx->stream;
+    mf_buf<unsigned int> maxl;
+    MF_TRY(maxl.alloc(ctx, 1));
+    MF_HIP(hipMemsetAsync(maxl.p, 0, 4, st));
+    k_cp_maxlist<<<cp_grid(P->nd), 256, 0, st>>>(P->lo.p, P->nd, maxl.p);
+    MF_HIP(hipGetLastError());
+    unsigned int h = 0;
+    MF_HIP(hipMemcpyAsync(&h, maxl.p, 4, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipStreamSynchronize(st));
+    P->max_listings = std::max(1u, h);
+    // a thread of k_cp_mark counts up to CP_RUN x listings starts in 32 bits
+    if (P->max_listings >= (1u << 26)) return mf_set_error("component-paths: a k-mer is listed by %u of the selected components (fewer than 2^26)", P->max_listings);
+    return MF_OK;
+}
+
 extern "C" void mf_paths_destroy(mf_paths *p) { delete p; }
 
 extern "C" int mf_paths_create(mf_ctx *ctx, mf_comps *c, const uint32_t *selection, uint64_t n_selection, int min_len, uint64_t max_paths, mf_paths **out) {
@@ -307,43 +308,16 @@ extern "C" int mf_paths_create(mf_ctx *ctx, mf_comps *c, const uint32_t *selecti
     hipStream_t st = ctx->stream;
     std::unique_ptr<mf_paths> P(new mf_paths());
     P->ctx = ctx; P->k = c->k; P->min_len = min_len; P->max_paths = max_paths;
-    // the slots: the selection without its repeats, in the order given; all components in theirs
-    std::vector<uint32_t> slot_of((size_t)std::max<uint64_t>(c->n, 1), CP_NONE);
-    if (!selection) {
-        for (uint64_t i = 0; i < c->n; i++) { slot_of[i] = (uint32_t)i; P->comp_no.push_back((uint32_t)i + 1u); }
-    } else {
-        for (uint64_t j = 0; j < n_selection; j++) {
-            const uint32_t no = selection[j];
-            if (no < 1 || (uint64_t)no > c->n) return mf_set_error("component-paths: there is no component %u (the file holds %llu, numbered from 1)", no, (unsigned long long)c->n);
-            if (slot_of[no - 1] != CP_NONE) continue;
-            slot_of[no - 1] = (uint32_t)P->comp_no.size();
-            P->comp_no.push_back(no);
-        }
-    }
-    const uint64_t ns = P->n_slots = P->comp_no.size();
-    for (uint64_t s = 0; s < ns; s++) {
-        const uint64_t size = c->sizes[P->comp_no[s] - 1]; const int64_t weight = c->weights[P->comp_no[s] - 1];
-        double w = 0.0;
-        if (size) {                                        // (a component without members matches nothing: its weight is never printed)
-            w = floor((double)weight / (double)size + 0.5);      // Math.round
-            if (!(w >= -2147483648.0 && w <= 2147483647.0))
-                return mf_set_error("component-paths: the average k-mer weight of component %u does not fit a 32-bit integer", P->comp_no[s]);
-        }
-        P->W.push_back((int32_t)w);
-    }
-    MF_TRY(P->count.alloc(ctx, ns));
-    MF_HIP(hipMemsetAsync(P->count.p, 0, (ns ? ns : 1) * 8, st));
+    std::vector<uint32_t> slot_of;
+    MF_TRY(cp_slots_of(P.get(), c->n, c->sizes.data(), c->weights.data(), selection, n_selection, slot_of));
+    const uint64_t ns = P->n_slots;
     const uint64_t nk = c->n_kmers;
     if (nk && ns) {
         mf_buf<uint32_t> dslot, flag; mf_buf<uint64_t> rank, tot; mf_buf<unsigned int> scal;
-        MF_TRY(dslot.alloc(ctx, c->n)); MF_TRY(flag.alloc(ctx, nk)); MF_TRY(rank.alloc(ctx, nk + 1)); MF_TRY(tot.alloc(ctx, 1)); MF_TRY(scal.alloc(ctx, 2));
-        MF_HIP(hipMemcpyAsync(dslot.p, slot_of.data(), c->n * 4, hipMemcpyHostToDevice, st));
-        MF_HIP(hipMemsetAsync(scal.p, 0, 8, st));
-        k_cp_select<<<cp_grid(nk), 256, 0, st>>>(c->d_comp, dslot.p, nk, flag.p);
-        MF_TRY(mf_scan<1>(ctx, flag.p, rank.p, nk, tot.p));
-        unsigned long long nm = 0;
-        MF_HIP(hipMemcpyAsync(&nm, tot.p, 8, hipMemcpyDeviceToHost, st));
-        MF_HIP(hipStreamSynchronize(st));
+        uint64_t nm = 0;
+        MF_TRY(cp_select(ctx, c->d_comp, c->n, nk, slot_of, dslot, flag, rank, &nm));
+        MF_TRY(tot.alloc(ctx, 1)); MF_TRY(scal.alloc(ctx, 1));
+        MF_HIP(hipMemsetAsync(scal.p, 0, 4, st));
         P->nm = nm;
         if (nm) {
             mf_buf<uint64_t> mk, mk1, mk2; mf_buf<uint32_t> ms, ms1;
@@ -360,24 +334,19 @@ extern "C" int mf_paths_create(mf_ctx *ctx, mf_comps *c, const uint32_t *selecti
             MF_TRY(hflag.alloc(ctx, nm)); MF_TRY(hrank.alloc(ctx, nm + 1));
             k_cp_heads<<<cp_grid(nm), 256, 0, st>>>(mk2.p, nm, P->k, hflag.p, &scal.p[0]);
             MF_TRY(mf_scan<1>(ctx, hflag.p, hrank.p, nm, tot.p));
-            unsigned long long nd = 0; unsigned int h_scal[2] = {0, 0};
+            unsigned long long nd = 0; unsigned int h_bad = 0;
             MF_HIP(hipMemcpyAsync(&nd, tot.p, 8, hipMemcpyDeviceToHost, st));
-            MF_HIP(hipMemcpyAsync(h_scal, scal.p, 4, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipMemcpyAsync(&h_bad, scal.p, 4, hipMemcpyDeviceToHost, st));
             MF_HIP(hipStreamSynchronize(st));
-            if (h_scal[0]) return mf_set_error("component-paths: a component holds a k-mer that does not fit %d bases", P->k);
+            if (h_bad) return mf_set_error("component-paths: a component holds a k-mer that does not fit %d bases", P->k);
             P->nd = nd;
             mf_buf<uint64_t> dk;
             MF_TRY(dk.alloc(ctx, nd)); MF_TRY(P->lo.alloc(ctx, nd + 1));
             k_cp_distinct<<<cp_grid(nm + 1), 256, 0, st>>>(mk2.p, hflag.p, hrank.p, nm, dk.p, P->lo.p);
-            k_cp_maxlist<<<cp_grid(nd), 256, 0, st>>>(P->lo.p, nd, &scal.p[1]);
             MF_HIP(hipGetLastError());
             MF_TRY(mf_index_build(ctx, dk.p, nullptr, nd, &P->index, &P->index_bytes));
-            MF_HIP(hipMemcpyAsync(h_scal, scal.p, 8, hipMemcpyDeviceToHost, st));
             MF_HIP(hipGetLastError());
-            MF_HIP(hipStreamSynchronize(st));              // (dk and the sort's buffers go back to the arena)
-            P->max_listings = std::max(1u, h_scal[1]);
-            // a thread of k_cp_mark counts up to CP_RUN x listings starts in 32 bits
-            if (P->max_listings >= (1u << 26)) return mf_set_error("component-paths: a k-mer is listed by %u of the selected components (fewer than 2^26)", P->max_listings);
+            MF_TRY(cp_max_listings(P.get()));               // (synchronises: dk and the sort's buffers go back to the arena)
             if (!selection && c->shared < 0) c->shared = nd < nm ? 1 : 0;       // (all members were looked at: does the member list hold a k-mer twice?)
         }
     }
@@ -419,7 +388,7 @@ extern "C" int mf_paths_add(mf_paths *P, const void *d_bases, const void *d_offs
     runs.reset();
 
     // 2. marking: count, scan, emit
-    const cp_members M{mf_view(P->index), P->lo.p, P->slots.p};
+    const cp_members<cp_keys64> M{cp_keys64{P->wide ? mf_index_view{} : mf_view(P->index)}, P->lo.p, P->slots.p};
     mf_buf<uint64_t> os, oe;
     MF_TRY(os.alloc(ctx, n_runs + 1)); MF_TRY(oe.alloc(ctx, n_runs + 1));
     {
@@ -427,8 +396,9 @@ extern "C" int mf_paths_add(mf_paths *P, const void *d_bases, const void *d_offs
         MF_TRY(cs.alloc(ctx, n_runs)); MF_TRY(ce.alloc(ctx, n_runs));
         {
             mf_ktimer tm(ctx, "k_cp_mark");
-            k_cp_mark<false><<<cp_grid(n_runs, CP_WG), CP_WG, 0, st>>>(bases, off, srun.p, n, n_runs, k, M, cs.p, ce.p, nullptr, nullptr, cp_marks{nullptr, nullptr},
-                                                                     cp_marks{nullptr, nullptr});
+            if (P->wide) MF_TRY(cp_mark_wide(P, false, cp_mark_args{bases, off, srun.p, n, n_runs, cs.p, ce.p, nullptr, nullptr, cp_marks{nullptr, nullptr}, cp_marks{nullptr, nullptr}}));
+            else k_cp_mark<false><<<cp_grid(n_runs, CP_WG), CP_WG, 0, st>>>(bases, off, srun.p, n, n_runs, k, M, cs.p, ce.p, nullptr, nullptr, cp_marks{nullptr, nullptr},
+                                                                          cp_marks{nullptr, nullptr});
         }
         MF_HIP(hipGetLastError());
         MF_TRY(cp_scan(ctx, cs.p, os.p, n_runs, &tot.p[0]));
@@ -449,8 +419,9 @@ extern "C" int mf_paths_add(mf_paths *P, const void *d_bases, const void *d_offs
         MF_TRY(us.alloc(ctx, nr)); MF_TRY(ups.alloc(ctx, nr)); MF_TRY(ue.alloc(ctx, nr)); MF_TRY(upe.alloc(ctx, nr));
         {
             mf_ktimer tm(ctx, "k_cp_mark");
-            k_cp_mark<true><<<cp_grid(n_runs, CP_WG), CP_WG, 0, st>>>(bases, off, srun.p, n, n_runs, k, M, nullptr, nullptr, os.p, oe.p, cp_marks{us.p, ups.p},
-                                                                    cp_marks{ue.p, upe.p});
+            if (P->wide) MF_TRY(cp_mark_wide(P, true, cp_mark_args{bases, off, srun.p, n, n_runs, nullptr, nullptr, os.p, oe.p, cp_marks{us.p, ups.p}, cp_marks{ue.p, upe.p}}));
+            else k_cp_mark<true><<<cp_grid(n_runs, CP_WG), CP_WG, 0, st>>>(bases, off, srun.p, n, n_runs, k, M, nullptr, nullptr, os.p, oe.p, cp_marks{us.p, ups.p},
+                                                                         cp_marks{ue.p, upe.p});
         }
         MF_HIP(hipGetLastError());
         // 3. pairing: both lists by slot, position order kept inside a slot

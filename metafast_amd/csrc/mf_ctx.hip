@@ -228,7 +228,7 @@ extern "C" int64_t mf_ctx_stat(mf_ctx *ctx, const char *name) {
     if (s == "s2c_lds_max") return 4096;                  // (S2C_T of mf_seq2comp.hip: the longest sequence, in k-mers, of the LDS class)
     if (s == "ws2c_lds_max") return 2048;                 // (WS2C_T of mf_wseq2comp.hip: the same for 2k-bit k-mers, 32 <= k <= 63)
     if (s == "s2c_sort_batches") return (int64_t)ctx->n_s2c_batches;
-    if (s == "cp_run") return 32;                         // (CP_RUN of mf_comppaths.hip: the positions a thread of k_cp_mark takes ...
+    if (s == "cp_run") return 32;                         // (CP_RUN of mf_cp.h: the positions a thread of k_cp_mark takes ...
     if (s == "cp_block") return 32 * 256;                 //  ... and CP_RUN * CP_WG: the positions of a workgroup)
     if (s == "hipmalloc_calls") return (int64_t)ctx->n_hipmalloc;
     if (s == "hipmalloc_bytes") return (int64_t)ctx->b_hipmalloc;

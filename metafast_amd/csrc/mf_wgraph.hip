@@ -37,20 +37,22 @@ __global__ void k_windex_build(unsigned long long *__restrict__ slots, uint64_t 
         s = (s + 1) & mask;
     }
 }
+int mf_windex_build(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, uint64_t n, int k, mf_buf<unsigned long long> &index, uint64_t *mask) {
+    if (n >= 0xFFFFFFFFull) return mf_set_error("wide table: more than 2^32 entries cannot be indexed");
+    uint64_t cap = 1024;
+    while (cap < 2 * n) cap <<= 1;
+    MF_TRY(index.alloc(ctx, cap));
+    *mask = cap - 1;
+    mf_ktimer tm(ctx, "k_windex_build");
+    MF_HIP(hipMemsetAsync(index.p, 0xFF, cap * 8, ctx->stream));
+    k_windex_build<<<ggrid(n), 256, 0, ctx->stream>>>(index.p, cap - 1, hi, lo, n, k);
+    return MF_OK;
+}
 int mf_wtable_ensure_index(mf_wtable *t) {
     MF_TRY(mf_wtable_flatten(t));
     if (t->index.p || !t->n) return MF_OK;
-    if (t->n >= 0xFFFFFFFFull) return mf_set_error("wide table: more than 2^32 entries cannot be indexed");
-    mf_ctx *ctx = t->ctx;
-    uint64_t cap = 1024;
-    while (cap < 2 * t->n) cap <<= 1;
-    MF_TRY(t->index.alloc(ctx, cap));
-    t->index_mask = cap - 1;
-    mf_ktimer tm(ctx, "k_windex_build");
-    MF_HIP(hipMemsetAsync(t->index.p, 0xFF, cap * 8, ctx->stream));
     auto &pc = *t->pieces[0];
-    k_windex_build<<<ggrid(t->n), 256, 0, ctx->stream>>>(t->index.p, t->index_mask, pc.hi.p, pc.lo.p, t->n, t->k);
-    return MF_OK;
+    return mf_windex_build(t->ctx, pc.hi.p, pc.lo.p, t->n, t->k, t->index, &t->index_mask);
 }
 
 // ---------------------------------------------------------------------------------------------

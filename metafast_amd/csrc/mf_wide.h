@@ -42,6 +42,9 @@ int mf_wide_order(mf_ctx *ctx, int k, const uint64_t *src_hi, const uint64_t *sr
 int mf_wtable_ensure_ascending(mf_wtable *t);             // (drops an index built over the other order)
 int mf_wtable_flatten(mf_wtable *t);                      // all pieces into one (no-op for <= 1 piece)
 int mf_wtable_ensure_index(mf_wtable *t);                 // flatten + index
+// the index itself over n distinct k-mers (hi, lo)[n] of k bases, n < 2^32 - 1 (mf_wgraph.hip): the table's, and the one component-paths
+// builds over the distinct members of its selection (mf_wcomppaths.hip)
+int mf_windex_build(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, uint64_t n, int k, mf_buf<unsigned long long> &index, uint64_t *mask);
 // entries of (hi, lo, cnt)[n] with cnt > thr -> a new piece (order kept)
 int mf_wide_compact(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, int thr, mf_wtable::piece &out);
 

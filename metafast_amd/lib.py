@@ -152,6 +152,8 @@ _SIGS = {
     "mf_paths_text": (i32, [vp, i64, vp, u64, pu64]),
     "mf_paths_write": (i32, [vp, cp, pu64]),
     "mf_component_paths": (i32, [vp, cp, i32, C.POINTER(cp), i32, vp, u64, i32, u64, cp, pu64, pu64]),
+    "mf_paths_create_wide": (i32, [vp, vp, vp, u64, i32, u64, pvp]),
+    "mf_component_paths_wide": (i32, [vp, cp, i32, C.POINTER(cp), i32, vp, u64, i32, u64, cp, pu64, pu64]),
     "mf_features_device": (i32, [vp, vp, vp, i32, vp, vp]),
     "mf_features_reads_device": (i32, [vp, vp, vp, vp, u64, u64, i32, i32, vp, vp]),
     "mf_features_reads": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, cp, cp]),
@@ -631,6 +633,24 @@ class Context:
         _check(lib().mf_component_paths(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files),
                                         sel.ctypes.data if sel is not None else None, len(sel) if sel is not None else 0, min_len, max_paths,
                                         os.fsencode(out_dir), C.byref(nc), C.byref(npth)))
+        return nc.value, npth.value
+
+    def paths_wide(self, wcomps, selection=None, min_len=50, max_paths=MAX_PATHS_COUNT):
+        """NO-REFERENCE EXTENSION, 32 <= k <= 63 (mf_wcomppaths.hip): paths on WideComps (they know their k) -> the same Paths object"""
+        sel = None if selection is None else np.ascontiguousarray(selection, dtype=np.uint32)
+        p = C.c_void_p()
+        _check(lib().mf_paths_create_wide(self.h, wcomps.h, sel.ctypes.data if sel is not None else None, len(sel) if sel is not None else 0, min_len,
+                                          max_paths, C.byref(p)))
+        return Paths(self, p)
+
+    def component_paths_wide(self, components_bin, k, files, out_dir, selection=None, min_len=50, max_paths=MAX_PATHS_COUNT):
+        """NO-REFERENCE EXTENSION: component_paths' file form on a wide components.bin; returns (components in the file, paths written)"""
+        files = list(files)
+        sel = None if selection is None else np.ascontiguousarray(selection, dtype=np.uint32)
+        nc, npth = C.c_uint64(), C.c_uint64()
+        _check(lib().mf_component_paths_wide(self.h, os.fsencode(components_bin), k, _cfiles(files) if files else None, len(files),
+                                             sel.ctypes.data if sel is not None else None, len(sel) if sel is not None else 0, min_len, max_paths,
+                                             os.fsencode(out_dir), C.byref(nc), C.byref(npth)))
         return nc.value, npth.value
 
     # ---- A12 ----

@@ -9,9 +9,16 @@ Wall time of mf_paths_add (a fresh mf_paths each time, the index built before) a
 sides, after one warm-up call each, best of three; then one more call of each under option profile for the kernels' own times.
 
     python tools/component_paths_rate.py --out profiles/component_paths_rate.txt
+
+--wide (32 <= k <= 63): the same workload through wcomps_from_sequences and paths_wide (mf_wcomppaths.hip); there is no reads route at
+that width, so only mf_paths_add and k_cp_mark are timed.  --append adds to --out instead of starting it again.
+
+    python tools/component_paths_rate.py --repeats 5 --out profiles/wcomponent_paths_rate.txt
+    python tools/component_paths_rate.py --repeats 5 --wide -k 33 --append --out profiles/wcomponent_paths_rate.txt
 """
 import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -29,12 +36,15 @@ def main():
     ap.add_argument("--min-len", type=int, default=50)
     ap.add_argument("--seed", type=int, default=20200203)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--append", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "component_paths_rate.txt"))
     args = ap.parse_args()
     import torch
     from metafast_amd import lib as L
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    open(args.out, "w").close()
+    if not args.append:
+        open(args.out, "w").close()
 
     def say(s):
         print(s, flush=True)
@@ -61,14 +71,14 @@ def main():
         from_gene = (torch.arange(a, b, device="cuda") % 2 == 0).repeat_interleave(args.seq_len)
         bases[a * args.seq_len: b * args.seq_len] = torch.where(from_gene, text, rnd)
     ctx = L.Context(0, stream=torch.cuda.current_stream())
-    c = ctx.comps_from_sequences(genes.data_ptr(), goff.data_ptr(), args.genes, gb, args.k)
+    c = (ctx.wcomps_from_sequences if args.wide else ctx.comps_from_sequences)(genes.data_ptr(), goff.data_ptr(), args.genes, gb, args.k)
     npos = args.seqs * max(0, args.seq_len - args.k + 1)
     say(f"# component_paths_rate: {args.genes} components (random sequences of {args.gene_len} bases, {c.stats()[1]} members), {args.seqs} sequences of "
         f"{args.seq_len} bases ({nb} bases, {npos} k-mer positions; every second one a window of the components' text), k = {args.k}, -l {args.min_len}, all "
         f"components; {torch.cuda.get_device_name(0)}")
 
     def paths_once():
-        p = ctx.paths(c, min_len=args.min_len)
+        p = ctx.paths_wide(c, min_len=args.min_len) if args.wide else ctx.paths(c, min_len=args.min_len)
         ctx.synchronize()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -91,11 +101,24 @@ def main():
     no, cnt, nbytes, cap = p.slots()
     say(f"paths kept: {int(cnt.sum())} in {int((cnt > 0).sum())} components, {int(nbytes.sum())} bytes of text; most listings of one k-mer: {p.max_listings()}")
     del p
-    features_once()
+    if not args.wide:
+        features_once()
     wall_p = [paths_once()[0] for _ in range(max(args.repeats, 3))]
-    wall_f = [features_once() for _ in range(max(args.repeats, 3))]
+    wall_f = [] if args.wide else [features_once() for _ in range(max(args.repeats, 3))]
     say("mf_paths_add (marking, two sorts, pairing, cap, store): wall per call (ms): " + " ".join(f"{w * 1e3:.1f}" for w in wall_p) +
-        f"; best {min(wall_p) * 1e3:.1f} ms, spread {(max(wall_p) - min(wall_p)) * 1e3:.1f} ms, {npos / min(wall_p) / 1e9:.2f} G positions / s")
+        f"; best {min(wall_p) * 1e3:.1f} ms, median {statistics.median(wall_p) * 1e3:.1f} ms, spread {(max(wall_p) - min(wall_p)) * 1e3:.1f} ms, "
+        f"{npos / min(wall_p) / 1e9:.2f} G positions / s")
+    if args.wide:
+        ctx.set_option("profile", 1)
+        ctx.reset_timers()
+        paths_once()
+        ctx.synchronize()
+        n_m, ms_m = ctx.kernel_time("k_cp_mark")
+        n_s, ms_s = ctx.kernel_time("k_radix_sort")
+        ctx.set_option("profile", 0)
+        say(f"one more call under option profile: k_cp_mark {n_m} launches (count + emit) {ms_m:.2f} ms = {npos / (ms_m / 1e3) / 1e9:.2f} G positions / s; "
+            f"k_radix_sort (starts, ends) {n_s} timed sorts {ms_s:.2f} ms")
+        return
     say("mf_features_reads_device (k_presence + the vector): wall per call (ms): " + " ".join(f"{w * 1e3:.1f}" for w in wall_f) +
         f"; best {min(wall_f) * 1e3:.1f} ms, spread {(max(wall_f) - min(wall_f)) * 1e3:.1f} ms")
     ctx.set_option("profile", 1)
