@@ -206,6 +206,26 @@ int  mf_wcomps_export(const mf_wcomps *c, uint64_t *sizes, int64_t *weights, int
                       uint64_t *kmers_lo);
 /* [mf_features_device] vec[c] = sum of the sample's counts > threshold over the component's k-mers, breadth[c] = found / size */
 int  mf_features_wide_device(mf_ctx *ctx, mf_wcomps *c, mf_wtable *sample, int threshold, int64_t *vec, double *breadth);
+/* [mf_features_device_selected / mf_features_reads_device(_selected)] the other two inputs of features-calculator on wide components
+ * (mf_wfeatures.hip), the k <= 31 definitions word for word on 2k-bit k-mers (oracle/mf_oracle_core.inc: or_features_selected,
+ * or_features_reads_selected, compiled for 128-bit keys).  k is the components' own.  A component is summed over its member LISTINGS: a
+ * k-mer that two components list is read once for each.  selected (NULL: no selection): only the listings whose k-mer has a value > 0 in
+ * that table take part -- in vec, in found and in the denominator of breadth = found / cnt, which is 0.0 / 0.0 = NaN for a component
+ * with no such listing; a negative threshold makes absent k-mers count as found.  Reads form: every position of every read of >= k bases
+ * whose canonical k-mer is a member adds 1 to it, in 64 bits -- a k-mer seen 40 000 times counts 40 000, where a sample table holds 32767;
+ * reads shorter than k give nothing, no reads give vec = 0 and breadth = 0 / cnt; d_bases are ASCII letters of either case without
+ * alignment or slack demands (a run of positions reads its own bases only), d_offsets as for mf_count_device; offsets that go backwards
+ * or do not end at n_bases are errors.  Errors carry the entry point's name: NULL arguments, a handle of another context, a sample or
+ * selected table of another k, k outside 32 ... 63, 2^32 - 1 or more members.  No components: MF_OK, nothing written.  The file forms
+ * load the components with mf_wcomps_load(k) first (nothing is written before it has accepted the file, and an empty one is the
+ * reference's "No components were found" error), take the files of ONE library through mf_reads_load or one wide .kmers.bin uncut,
+ * and write .vec / .breadth as for k <= 31.  mf_ctx_stat("wf_run"): the read positions one thread takes. */
+int  mf_features_wide_device_selected(mf_ctx *ctx, mf_wcomps *c, mf_wtable *sample, mf_wtable *selected, int threshold, int64_t *vec,
+                                      double *breadth);
+int  mf_features_reads_wide_device(mf_ctx *ctx, mf_wcomps *c, const void *d_bases, const void *d_offsets, uint64_t n_reads,
+                                   uint64_t n_bases, int threshold, int64_t *vec, double *breadth);
+int  mf_features_reads_wide_device_selected(mf_ctx *ctx, mf_wcomps *c, const void *d_bases, const void *d_offsets, uint64_t n_reads,
+                                            uint64_t n_bases, mf_wtable *selected, int threshold, int64_t *vec, double *breadth);
 /* ... and its files (mf_wio.hip).  No reference format exists for k > 31; these are the project's own:
  *   wide .kmers.bin     headerless, 18-byte big-endian records: int64 high word, int64 low word, int16 count (the words of
  *                       mf_wtable_export); strictly ascending in (high, low); only records with count > threshold
@@ -230,6 +250,13 @@ int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **
 /* [mf_features] both files loaded, mf_features_wide_device, .vec / .breadth as for k <= 31 */
 int  mf_features_wide(mf_ctx *ctx, const char *components_bin, const char *kmers_bin, int k, int threshold, const char *vec_path,
                       const char *breadth_path);
+/* [mf_features_selected / mf_features_reads(_selected)] the file forms of the calls above */
+int  mf_features_wide_selected(mf_ctx *ctx, const char *components_bin, const char *kmers_bin, int k, int threshold, mf_wtable *selected,
+                               const char *vec_path, const char *breadth_path);
+int  mf_features_reads_wide(mf_ctx *ctx, const char *components_bin, const char *const *files, int nfiles, int k, int threshold,
+                            const char *vec_path, const char *breadth_path);
+int  mf_features_reads_wide_selected(mf_ctx *ctx, const char *components_bin, const char *const *files, int nfiles, int k, int threshold,
+                                     mf_wtable *selected, const char *vec_path, const char *breadth_path);
 /* [mf_comps_unitigs_device / mf_comp2seq] comp2seq on wide components (mf_wcomp2seq.hip): the semantics of the k <= 31 entry points on
  * 2k-bit k-mers.  split != 0: per component the unitigs (threshold 0, minimal length k) of its canonical k-mers, each weighted with its
  * multiplicity in the member list, a neighbour counting only inside the SAME component, all components in one pass; split == 0: the

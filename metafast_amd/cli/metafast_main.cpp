@@ -89,6 +89,8 @@ extern "C" int mf_wcomps_load(mf_ctx *, const char *, int, mf_wcomps **) __attri
 extern "C" int mf_wcomps_stats(const mf_wcomps *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" void mf_wcomps_destroy(mf_wcomps *) __attribute__((weak));
 extern "C" int mf_features_wide(mf_ctx *, const char *, const char *, int, int, const char *, const char *) __attribute__((weak));
+extern "C" int mf_features_wide_selected(mf_ctx *, const char *, const char *, int, int, mf_wtable *, const char *, const char *) __attribute__((weak));
+extern "C" int mf_features_reads_wide_selected(mf_ctx *, const char *, const char *const *, int, int, int, mf_wtable *, const char *, const char *) __attribute__((weak));
 extern "C" int mf_comp2seq_wide(mf_ctx *, const char *, int, int, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_seq2comp_wide(mf_ctx *, const char *const *, int, int, const char *, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_comp2graph_wide(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
@@ -626,16 +628,18 @@ static string run_component_cutter(Env &e, const Args &a, const vector<string> &
     mf_table_destroy(t);
     return comp_file;
 }
-// features-calculator (src/tools/FeaturesCalculatorMain.java:77-167), k-mers files branch
+// features-calculator (src/tools/FeaturesCalculatorMain.java:77-167): reads files and k-mers files, with or without --selected
+// (--wide-kmers and k > 31: the same three inputs on a wide components.bin and wide .kmers.bin files, mf_wfeatures.hip; matrix-builder keeps its
+// refusal of --selected and --use-reads-for-calculating-features above k = 31 and never comes here with them)
 static vector<string> run_features(Env &e, const Args &a, const string &comp_file, const vector<string> &reads, const vector<string> &kmers,
-                                   int k, int thr, const string &wd) {
+                                   int k, int thr, const string &wd, bool single_tool = false) {
     if (comp_file.empty()) die("Mandatory option --components-file is not set");
     if (kmers.empty() && reads.empty()) die("No input files: pass reads (-i) or k-mers files (-ka)");
     const bool wide = wide_k(k);
-    if (wide) {                                                              // (k-mers files only: no selected set, no features from reads)
-        no_wide(!a.list("selected").empty(), "selected");
-        no_wide(a.flag("use-reads-for-calculating-features"), "use-reads-for-calculating-features");
-        no_wide(!reads.empty(), "reads");
+    if (!wide && single_tool) check_k(k);                                    // (the builder has checked its k)
+    if (wide && (!reads.empty() || !a.list("selected").empty())) {
+        if (!mf_features_reads_wide_selected) die("features-calculator: this build of the library has no mf_features_reads_wide_selected");
+        if (!mf_features_wide_selected) die("features-calculator: this build of the library has no mf_features_wide_selected");
     }
     parse_devices(e, a);
     string out_dir = wd + "/vectors";
@@ -649,6 +653,13 @@ static vector<string> run_features(Env &e, const Args &a, const string &comp_fil
         if (!t) { auto fp = cptrs(sel_files); check(mf_table_load_kmers(ctx_of(e, a), fp.data(), (int)fp.size(), 0, k, &t)); }
         return t;
     };
+    vector<mf_wtable *> wsel(e.devs.size(), nullptr);                         // (the same for wide files)
+    auto wselected = [&]() -> mf_wtable * {
+        if (sel_files.empty()) return nullptr;
+        mf_wtable *&t = wsel[(size_t)t_slot];
+        if (!t) { auto fp = cptrs(sel_files); check(mf_wtable_load_kmers(ctx_of(e, a), fp.data(), (int)fp.size(), 0, k, &t)); }
+        return t;
+    };
     // reads files first, one vector per FILE, then k-mers files (FeaturesCalculatorMain.java:117-162)
     vector<string> vecs(reads.size() + kmers.size());
     for_each_library(e, a, vecs.size(), [&](size_t i) {
@@ -658,20 +669,23 @@ static vector<string> run_features(Env &e, const Args &a, const string &comp_fil
             string base = library_name(rf);
             string vec = out_dir + "/" + base + ".vec", br = out_dir + "/" + base + ".breadth";
             const char *fs[1] = {rf.c_str()};
-            check(mf_features_reads_selected(ctx, comp_file.c_str(), fs, 1, k, thr, selected(), vec.c_str(), br.c_str()));
+            if (wide) check(mf_features_reads_wide_selected(ctx, comp_file.c_str(), fs, 1, k, thr, wselected(), vec.c_str(), br.c_str()));
+            else check(mf_features_reads_selected(ctx, comp_file.c_str(), fs, 1, k, thr, selected(), vec.c_str(), br.c_str()));
             logmsg("INFO", "Features for file %s printed to %s", basename_of(rf).c_str(), vec.c_str());
             vecs[i] = vec;
         } else {
             const string &kf = kmers[i - reads.size()];
             string base = remove_ext(basename_of(kf), {".kmers.bin"});
             string vec = out_dir + "/" + base + ".vec", br = out_dir + "/" + base + ".breadth";
-            if (wide) check(mf_features_wide(ctx, comp_file.c_str(), kf.c_str(), k, thr, vec.c_str(), br.c_str()));
+            if (wide && sel_files.empty()) check(mf_features_wide(ctx, comp_file.c_str(), kf.c_str(), k, thr, vec.c_str(), br.c_str()));
+            else if (wide) check(mf_features_wide_selected(ctx, comp_file.c_str(), kf.c_str(), k, thr, wselected(), vec.c_str(), br.c_str()));
             else check(mf_features_selected(ctx, comp_file.c_str(), kf.c_str(), k, thr, selected(), vec.c_str(), br.c_str()));
             logmsg("INFO", "Features for file %s printed to %s", basename_of(kf).c_str(), vec.c_str());
             vecs[i] = vec;
         }
     });
     for (mf_table *t : sel) if (t) mf_table_destroy(t);
+    for (mf_wtable *t : wsel) if (t) mf_wtable_destroy(t);
     return vecs;
 }
 // Double.toString (what Java's "%s" prints for a double): shortest digits that round-trip, decimal notation in [1e-3, 1e7)
@@ -1132,7 +1146,7 @@ static vector<PV> tool_component_cutter(Run &r) {
     return {PV::file("components-file", cf), PV::file("components-stat", cutter_stat(r.wd, b1, b2))};
 }
 static vector<PV> tool_features(Run &r) {
-    return {PV::files("features-files", run_features(r.e, r.a, r.str("components-file"), r.a.list("reads"), r.a.list("kmers"), r.k, r.num("threshold"), r.wd)),
+    return {PV::files("features-files", run_features(r.e, r.a, r.str("components-file"), r.a.list("reads"), r.a.list("kmers"), r.k, r.num("threshold"), r.wd, true)),
             PV::file("features-dir", r.wd + "/vectors")};
 }
 static vector<PV> tool_dist_matrix(Run &r) {

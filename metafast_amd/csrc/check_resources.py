@@ -7,7 +7,7 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_|k_wf_|k_w_features")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
 # column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip, mf_wcomp2graph.hip; one thread per run of positions, per
 # run, per record, or one wave per record: mf_comppaths.hip)
@@ -32,6 +32,8 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
                            "k_cp_pair", "k_cp_keep", "k_cp_bump", "k_cp_records", "k_cp_copy", "k_cp_keys", "k_cp_widths", "k_cp_slot_bytes",
                            "k_cp_write_head", "k_cp_write_bases"],
           # (the member side and the marking kernel on 2k-bit k-mers: k_cp_mark of mf_cp.h instantiated over 128-bit keys)
+          # (the wide features, mf_wfeatures.hip: a thread per listing or per run of read positions, two 128-bit registers rolled per thread)
+          "mf_wfeatures": ["k_wf_index", "k_wf_sizes", "k_wf_split", "k_wf_join", "k_wf_presence", "k_wf_select", "k_wf_occ", "k_w_features"],
           "mf_wcomppaths": ["k_cp_wmembers", "k_cp_gather64", "k_cp_gather32", "k_cp_wheads", "k_cp_wdistinct", "k_cp_mark"],
           # (the row kernels of specific-kmers and specific-kmers-3 keep a row in LDS: a spill would cost them their occupancy)
           "mf_specific": ["k_specific_select", "k_specific_gather", "k_specific_rows_thread", "k_specific_rows_wave"],

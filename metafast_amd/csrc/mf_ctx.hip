@@ -211,6 +211,7 @@ extern "C" int mf_ctx_set_option(mf_ctx *ctx, const char *name, int64_t v) {
 }
 
 // counters and gauges of the context, by name (-1: unknown name)
+int mf_wf_run();                  // WF_RUN as mf_wfeatures.hip was built (stat "wf_run")
 extern "C" int64_t mf_ctx_stat(mf_ctx *ctx, const char *name) {
     if (!ctx || !name) return mf_set_error("mf_ctx_stat: NULL argument");
     const std::string s(name);
@@ -227,6 +228,7 @@ extern "C" int64_t mf_ctx_stat(mf_ctx *ctx, const char *name) {
     if (s == "device_parser_stepped_back") return (int64_t)ctx->n_dparse_stepped_back;
     if (s == "s2c_lds_max") return 4096;                  // (S2C_T of mf_seq2comp.hip: the longest sequence, in k-mers, of the LDS class)
     if (s == "ws2c_lds_max") return 2048;                 // (WS2C_T of mf_wseq2comp.hip: the same for 2k-bit k-mers, 32 <= k <= 63)
+    if (s == "wf_run") return mf_wf_run();                // (WF_RUN of mf_wfeatures.hip: the positions a thread of k_wf_presence takes)
     if (s == "s2c_sort_batches") return (int64_t)ctx->n_s2c_batches;
     if (s == "cp_run") return 32;                         // (CP_RUN of mf_cp.h: the positions a thread of k_cp_mark takes ...
     if (s == "cp_block") return 32 * 256;                 //  ... and CP_RUN * CP_WG: the positions of a workgroup)

@@ -1,4 +1,4 @@
-// mf_wgraph.hip -- NO-REFERENCE EXTENSION: unitigs, components and features for 32 <= k <= 63 (2k-bit k-mers).
+// mf_wgraph.hip -- NO-REFERENCE EXTENSION: unitigs and components for 32 <= k <= 63 (2k-bit k-mers); the features on them: mf_wfeatures.hip.
 //
 // The reference rejects k > 31 (src/tools/KmersCounterMain.java:66-73: one Java long per k-mer); BASELINE.json's config 4 names a k = 63
 // leg whose metric is "counted + graphed".  Nothing here replaces a reference function or takes part in a parity claim; the checker is
@@ -245,57 +245,7 @@ extern "C" int mf_wcomps_export(const mf_wcomps *c, uint64_t *sizes, int64_t *we
     return MF_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// A12  features: a thread per component k-mer probes the sample's index (k_features_rev of mf_cc.hip on wide keys)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_w_features(mf_windex_view ix, const uint64_t *__restrict__ chi, const uint64_t *__restrict__ clo, const uint32_t *__restrict__ comp_of,
-                                                    uint64_t nk, int threshold, unsigned long long *__restrict__ vec, unsigned int *__restrict__ found) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t comp = 0xFFFFFFFFu, val = 0, hit = 0;
-    if (j < nk) {
-        comp = comp_of[j];
-        const uint32_t p = mf_windex_find(ix, chi[j], clo[j]);
-        if (p != 0xFFFFFFFFu) { const uint32_t v = ix.cnt[p]; if ((int)v > threshold) { val = v; hit = 1; } }
-    }
-    const uint32_t first = __shfl(comp, 0, 64);
-    if (__ballot(comp != first) == 0ull) {
-        for (int d = 32; d >= 1; d >>= 1) { val += __shfl_down(val, d, 64); hit += __shfl_down(hit, d, 64); }
-        if (mf_lane() == 0 && hit) { atomicAdd(&vec[first], (unsigned long long)val); atomicAdd(&found[first], hit); }
-    } else if (hit) {
-        atomicAdd(&vec[comp], (unsigned long long)val);
-        atomicAdd(&found[comp], 1u);
-    }
-}
-extern "C" int mf_features_wide_device(mf_ctx *ctx, mf_wcomps *c, mf_wtable *sample, int threshold, int64_t *vec, double *breadth) {
-    mf_range rng_("mf:features_wide");
-    if (!ctx || !c || !sample || !vec) return mf_set_error("mf_features_wide_device: NULL argument");
-    if (sample->ctx != ctx || c->ctx != ctx) return mf_set_error("mf_features_wide_device: a handle belongs to another context");
-    if (sample->k != c->k) return mf_set_error("mf_features_wide_device: components of %d-mers, sample of %d-mers", c->k, sample->k);
-    MF_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const uint64_t nc = c->n;
-    if (!nc) return MF_OK;
-    mf_buf<unsigned long long> dvec; mf_buf<unsigned int> dfound;
-    MF_TRY(dvec.alloc(ctx, nc)); MF_TRY(dfound.alloc(ctx, nc));
-    MF_HIP(hipMemsetAsync(dvec.p, 0, nc * 8, st));
-    MF_HIP(hipMemsetAsync(dfound.p, 0, nc * 4, st));
-    if (sample->n && c->n_kmers) {
-        MF_TRY(mf_wtable_ensure_index(sample));
-        mf_ktimer tm(ctx, "k_features");
-        k_w_features<<<ggrid(c->n_kmers), 256, 0, st>>>(mf_wtable_view(sample), c->hi.p, c->lo.p, c->comp.p, c->n_kmers, threshold, dvec.p, dfound.p);
-    }
-    std::vector<unsigned int> hf(nc);
-    MF_HIP(hipMemcpyAsync(vec, dvec.p, nc * 8, hipMemcpyDeviceToHost, st));
-    MF_HIP(hipMemcpyAsync(hf.data(), dfound.p, nc * 4, hipMemcpyDeviceToHost, st));
-    MF_HIP(hipStreamSynchronize(st));
-    if (breadth)
-        for (uint64_t i = 0; i < nc; i++) {
-            // a negative threshold makes absent k-mers (value 0) count as found (value > threshold), as in mf_cc.hip
-            const double f = threshold < 0 ? (double)c->sizes[i] : (double)hf[i];
-            breadth[i] = f / (double)c->sizes[i];
-        }
-    return MF_OK;
-}
+// (A12 features on wide components: mf_wfeatures.hip)
 // Long2ShortHashMap.get for a batch of host k-mers (as mf_table_lookup): values[i] = count or -1
 __global__ void k_w_lookup(mf_windex_view ix, const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, uint64_t n, int32_t *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

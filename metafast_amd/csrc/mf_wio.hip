@@ -479,21 +479,4 @@ extern "C" int mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf
     return MF_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// mf_features_wide: the shape of mf_features -- both files loaded, mf_features_wide_device, the .vec / .breadth writers of the k <= 31 path
-// ---------------------------------------------------------------------------------------------
-extern "C" int mf_features_wide(mf_ctx *ctx, const char *components_bin, const char *kmers_bin, int k, int threshold, const char *vec_path, const char *breadth_path) {
-    mf_range rng_("mf:features_wide(files)");
-    if (!ctx || !components_bin || !kmers_bin) return mf_set_error("mf_features_wide: NULL argument");
-    mf_wcomps *c = nullptr;
-    MF_TRY(mf_wcomps_load(ctx, components_bin, k, &c));
-    std::unique_ptr<mf_wcomps, void (*)(mf_wcomps *)> cg(c, mf_wcomps_destroy);
-    if (c->n == 0) return mf_set_error("No components were found in input files! Can't continue the calculations.");
-    mf_wtable *t = nullptr;
-    const char *files[1] = {kmers_bin};
-    MF_TRY(mf_wtable_load_kmers(ctx, files, 1, -1, k, &t));                   // (every record of the file, as mf_features)
-    std::unique_ptr<mf_wtable, void (*)(mf_wtable *)> tg(t, mf_wtable_destroy);
-    std::vector<int64_t> vec(c->n); std::vector<double> br(c->n);
-    MF_TRY(mf_features_wide_device(ctx, c, t, threshold, vec.data(), br.data()));
-    return mf_write_features_files(vec, br, vec_path, breadth_path);
-}
+// (mf_features_wide and the other file forms of the wide features: mf_wfeatures.hip)

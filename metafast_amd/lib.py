@@ -56,6 +56,12 @@ _SIGS = {
     "mf_wcomps_write": (i32, [vp, cp, cp]),
     "mf_wcomps_load": (i32, [vp, cp, i32, pvp]),
     "mf_features_wide": (i32, [vp, cp, cp, i32, i32, cp, cp]),
+    "mf_features_wide_device_selected": (i32, [vp, vp, vp, vp, i32, vp, vp]),
+    "mf_features_reads_wide_device": (i32, [vp, vp, vp, vp, u64, u64, i32, vp, vp]),
+    "mf_features_reads_wide_device_selected": (i32, [vp, vp, vp, vp, u64, u64, vp, i32, vp, vp]),
+    "mf_features_wide_selected": (i32, [vp, cp, cp, i32, i32, vp, cp, cp]),
+    "mf_features_reads_wide": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, cp, cp]),
+    "mf_features_reads_wide_selected": (i32, [vp, cp, C.POINTER(cp), i32, i32, i32, vp, cp, cp]),
     "mf_wcomps_unitigs_device": (i32, [vp, vp, i32, pvp]),
     "mf_comp2seq_wide": (i32, [vp, cp, i32, i32, cp, pu64, pu64]),
     "mf_wcomps_graph_device": (i32, [vp, vp, vp, i32, i32, pvp]),
@@ -421,11 +427,28 @@ class Context:
         _check(lib().mf_cut_components_wide_device(self.h, cutter.h, b1, b2, C.byref(c)))
         return WideComps(self, c)
 
-    def features_wide(self, comps, sample, threshold=0):
+    def features_wide(self, comps, sample, threshold=0, selected=None):
+        """NO-REFERENCE EXTENSION: features on WideComps and a WideTable; selected: WideTable of the --selected k-mers or None"""
         n = len(comps)
         vec = np.zeros(n, dtype=np.int64)
         br = np.zeros(n, dtype=np.float64)
-        _check(lib().mf_features_wide_device(self.h, comps.h, sample.h, threshold, vec.ctypes.data, br.ctypes.data))
+        if selected is None:
+            _check(lib().mf_features_wide_device(self.h, comps.h, sample.h, threshold, vec.ctypes.data, br.ctypes.data))
+        else:
+            _check(lib().mf_features_wide_device_selected(self.h, comps.h, sample.h, selected.h, threshold, vec.ctypes.data, br.ctypes.data))
+        return vec, br
+
+    def features_reads_wide(self, comps, d_bases, d_offsets, n_reads, n_bases, threshold=0, selected=None):
+        """NO-REFERENCE EXTENSION: features of a sample straight from its reads in HBM on WideComps (k is theirs): 64-bit counts"""
+        n = len(comps)
+        vec = np.zeros(n, dtype=np.int64)
+        br = np.zeros(n, dtype=np.float64)
+        if selected is None:
+            _check(lib().mf_features_reads_wide_device(self.h, comps.h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_reads, n_bases, threshold,
+                                                       vec.ctypes.data, br.ctypes.data))
+        else:
+            _check(lib().mf_features_reads_wide_device_selected(self.h, comps.h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_reads, n_bases, selected.h,
+                                                                threshold, vec.ctypes.data, br.ctypes.data))
         return vec, br
 
     # ---- the wide path's files (mf_wio.hip; formats: DESIGN 4.4) ----
@@ -447,9 +470,22 @@ class Context:
         _check(lib().mf_wcomps_load(self.h, os.fsencode(components_bin), k, C.byref(c)))
         return WideComps(self, c)
 
-    def features_wide_files(self, components_bin, kmers_bin, k, threshold=0, vec_path=None, breadth_path=None):
+    def features_wide_files(self, components_bin, kmers_bin, k, threshold=0, vec_path=None, breadth_path=None, selected=None):
         """NO-REFERENCE EXTENSION: features (files) on wide files; .vec / .breadth as for k <= 31"""
-        _check(lib().mf_features_wide(self.h, os.fsencode(components_bin), os.fsencode(kmers_bin), k, threshold, _opt(vec_path), _opt(breadth_path)))
+        if selected is None:
+            _check(lib().mf_features_wide(self.h, os.fsencode(components_bin), os.fsencode(kmers_bin), k, threshold, _opt(vec_path), _opt(breadth_path)))
+        else:
+            _check(lib().mf_features_wide_selected(self.h, os.fsencode(components_bin), os.fsencode(kmers_bin), k, threshold, selected.h, _opt(vec_path),
+                                                   _opt(breadth_path)))
+
+    def features_reads_wide_files(self, components_bin, files, k, threshold=0, vec_path=None, breadth_path=None, selected=None):
+        """NO-REFERENCE EXTENSION: features (files) from the reads files of ONE library on a wide components.bin"""
+        if selected is None:
+            _check(lib().mf_features_reads_wide(self.h, os.fsencode(components_bin), _cfiles(files) if files else None, len(files), k, threshold,
+                                                _opt(vec_path), _opt(breadth_path)))
+        else:
+            _check(lib().mf_features_reads_wide_selected(self.h, os.fsencode(components_bin), _cfiles(files) if files else None, len(files), k, threshold,
+                                                         selected.h, _opt(vec_path), _opt(breadth_path)))
 
     def count_device_above(self, d_bases, d_offsets, n_reads, n_bases, k, threshold, min_read_len=0):
         """count, keeping only the k-mers with count > threshold (what the k-mer counter hands on, IOUtils.printKmers);
