@@ -275,3 +275,79 @@ extern "C" int mf_wtable_drop_index(mf_wtable *t) {
     t->index.reset(); t->index_mask = 0;
     return MF_OK;
 }
+
+// For the tests (not in include/metafast_hip.h): the neighbour look-up alone, on a table made up on the host.  hi / lo / cnt[n]: distinct canonical
+// k-mers of k bases (32 .. 63), strictly ascending in (hi, lo), counts 1 .. MF_MAX_COUNT; q_hi / q_lo[m]: look-up queries (any 128-bit words).
+// Everything is checked here, on the host, before anything is launched.  The index is built by mf_windex_build (n < 2^32 - 1 is its limit: a
+// position is 32 bits and all ones mean "none"; the hook itself stops at 2^31 - 1, where mf_build_unitigs_wide_device stops), the kernels are the
+// ones production launches, unchanged:
+//   nbr_out[8 n]                          k_w_cc_adjacency
+//   info_out / ridx_out / lidx_out / pal_out[n]    k_w_ut_flags (pal always written, for an odd k too: all 0)
+//   values_out[m]                         k_w_lookup: the count or -1 (n = 0: no index, all -1)
+//   *cap_out, slots_out[*cap_out]         the index itself (0, untouched: n = 0); slots_room: the room behind slots_out, in slots
+extern "C" int mf_debug_wide_neighbours(mf_ctx *ctx, int k, uint64_t n, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t m, const uint64_t *q_hi,
+                                        const uint64_t *q_lo, uint32_t *nbr_out, uint8_t *info_out, uint32_t *ridx_out, uint32_t *lidx_out, uint8_t *pal_out,
+                                        int32_t *values_out, uint64_t *cap_out, unsigned long long *slots_out, uint64_t slots_room) {
+    if (!ctx || !cap_out) return mf_set_error("mf_debug_wide_neighbours: NULL argument");
+    if (k < 32 || k > 63) return mf_set_error("mf_debug_wide_neighbours: k = %d (32 .. 63)", k);
+    if (n >= 0x7FFFFFFFull) return mf_set_error("mf_debug_wide_neighbours: %llu k-mers (fewer than 2^31 - 1 are supported)", (unsigned long long)n);
+    if (n && (!hi || !lo || !cnt || !nbr_out || !info_out || !ridx_out || !lidx_out || !pal_out || !slots_out)) return mf_set_error("mf_debug_wide_neighbours: NULL argument");
+    if (m && (!q_hi || !q_lo || !values_out)) return mf_set_error("mf_debug_wide_neighbours: NULL argument");
+    mf_u128 prev = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const mf_u128 x = ((mf_u128)hi[i] << 64) | (mf_u128)lo[i];
+        if (x >> (2 * k)) return mf_set_error("mf_debug_wide_neighbours: k-mer %llu does not fit %d bits", (unsigned long long)i, 2 * k);
+        mf_u128 r = 0, y = x;
+        for (int j = 0; j < k; j++) { r = (r << 2) | (mf_u128)(3u - (unsigned)(y & 3)); y >>= 2; }
+        if (r < x) return mf_set_error("mf_debug_wide_neighbours: k-mer %llu is not canonical (its reverse complement is smaller)", (unsigned long long)i);
+        if (i && !(prev < x)) return mf_set_error("mf_debug_wide_neighbours: k-mer %llu is not above k-mer %llu (distinct and ascending in (hi, lo))", (unsigned long long)i, (unsigned long long)(i - 1));
+        if (cnt[i] < 1 || cnt[i] > MF_MAX_COUNT) return mf_set_error("mf_debug_wide_neighbours: count %u of k-mer %llu (1 .. %d)", (unsigned)cnt[i], (unsigned long long)i, MF_MAX_COUNT);
+        prev = x;
+    }
+    uint64_t cap = 0;
+    if (n) { cap = 1024; while (cap < 2 * n) cap <<= 1; }   // (what mf_windex_build will choose: the room is checked before anything is launched)
+    if (slots_room < cap) return mf_set_error("mf_debug_wide_neighbours: room for %llu index slots, the index has %llu", (unsigned long long)slots_room, (unsigned long long)cap);
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    *cap_out = 0;
+    mf_buf<uint64_t> dhi, dlo, dqh, dql; mf_buf<uint16_t> dcnt; mf_buf<unsigned long long> index; mf_buf<int32_t> dv;
+    mf_buf<uint32_t> nbr, ridx, lidx; mf_buf<uint8_t> info, pal;
+    mf_windex_view ix{};
+    ix.k = k;
+    if (n) {
+        MF_TRY(dhi.alloc(ctx, n)); MF_TRY(dlo.alloc(ctx, n)); MF_TRY(dcnt.alloc(ctx, n));
+        MF_HIP(hipMemcpyAsync(dhi.p, hi, n * 8, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(dlo.p, lo, n * 8, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(dcnt.p, cnt, n * 2, hipMemcpyHostToDevice, st));
+        uint64_t mask = 0;
+        MF_TRY(mf_windex_build(ctx, dhi.p, dlo.p, n, k, index, &mask));
+        if (mask + 1 != cap) return mf_set_error("mf_debug_wide_neighbours: the index has %llu slots, %llu were expected", (unsigned long long)(mask + 1), (unsigned long long)cap);
+        ix.slots = index.p; ix.mask = mask; ix.hi = dhi.p; ix.lo = dlo.p; ix.cnt = dcnt.p; ix.n = n;
+        MF_TRY(nbr.alloc(ctx, 8 * n)); MF_TRY(info.alloc(ctx, n)); MF_TRY(ridx.alloc(ctx, n)); MF_TRY(lidx.alloc(ctx, n)); MF_TRY(pal.alloc(ctx, n));
+        k_w_cc_adjacency<<<ggrid(n), 256, 0, st>>>(ix, n, k, nbr.p);
+        MF_HIP(hipGetLastError());
+        ut_arrays A;
+        A.gk = dlo.p; A.ghi = dhi.p; A.gv = dcnt.p; A.n = n; A.k = k;
+        A.info = info.p; A.ridx = ridx.p; A.lidx = lidx.p; A.pal = pal.p;
+        A.node = nullptr; A.jump = nullptr; A.starts = nullptr; A.n_starts = nullptr;
+        k_w_ut_flags<<<ggrid(n), 256, 0, st>>>(ix, A);
+        MF_HIP(hipGetLastError());
+        MF_HIP(hipMemcpyAsync(nbr_out, nbr.p, 8 * n * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(info_out, info.p, n, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(ridx_out, ridx.p, n * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(lidx_out, lidx.p, n * 4, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(pal_out, pal.p, n, hipMemcpyDeviceToHost, st));
+        MF_HIP(hipMemcpyAsync(slots_out, index.p, cap * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (m) {
+        MF_TRY(dqh.alloc(ctx, m)); MF_TRY(dql.alloc(ctx, m)); MF_TRY(dv.alloc(ctx, m));
+        MF_HIP(hipMemcpyAsync(dqh.p, q_hi, m * 8, hipMemcpyHostToDevice, st));
+        MF_HIP(hipMemcpyAsync(dql.p, q_lo, m * 8, hipMemcpyHostToDevice, st));
+        k_w_lookup<<<ggrid(m), 256, 0, st>>>(ix, dqh.p, dql.p, m, dv.p);
+        MF_HIP(hipGetLastError());
+        MF_HIP(hipMemcpyAsync(values_out, dv.p, m * 4, hipMemcpyDeviceToHost, st));
+    }
+    MF_HIP(hipStreamSynchronize(st));                      // (the buffers are released below)
+    *cap_out = cap;
+    return MF_OK;
+}

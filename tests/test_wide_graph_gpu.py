@@ -2,7 +2,8 @@
 has a k = 63 leg; the reference rejects k > 31 (src/tools/KmersCounterMain.java:66-73).  No parity claim against the reference: the checker
 is oracle/mf_oracle_wide.c = the pinned oracle's own text compiled for 128-bit keys (tied to the pinned build at k <= 31, the golden matrix
 included: tests/test_oracle_wide_cpu.py).  Through the C-ABI, bit-exact: cut tables, unitigs (strand-normalised multisets with weights and
-the 0 / 1 / 2-emission census), cutter tables, components at several threshold levels, features, the distance matrix."""
+the 0 / 1 / 2-emission census), cutter tables, components at several threshold levels, features, the distance matrix.
+The neighbour look-up's edges (full clusters, tag collisions, the 64-bit seam, palindromes, hairpins, wrap-around): tests/test_wnbr_gpu.py."""
 import numpy as np
 import pytest
 
