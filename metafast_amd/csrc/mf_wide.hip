@@ -480,6 +480,131 @@ int mf_wide_compact(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const u
     return MF_OK;
 }
 
+// ---- one pass of the sort path: n_p canonical k-mers in any order -> ascending, and their run lengths ----
+// what the order of a pass took (the verbose line of count_wide_impl; mf_debug_wide_pass)
+struct wide_pass_route {
+    unsigned int nlist[3] = {0, 0, 0};                    // buckets k_wide_finish listed -> those k_wide_big<64> passed on -> those k_wide_big<256> passed on
+    unsigned long long hstat[4] = {0, 0, 0, 0};           // the large buckets a k_wide_big finished: entries, buckets, the largest, distinct k-mers (summed)
+    uint64_t big_total = 0;                               // the entries of the last list's buckets
+    int kept = 0;                                         // 1: the order inside the buckets was made in LDS, 0: all 2k bits of the pass went through the radix sort
+    int tb = 0;                                           // the leading bits the radix passes order
+    uint32_t big = 0;                                     // option wide_big_bucket as it was applied
+};
+// (h0, l0): the pass, (h1, l1): a second pair of the same size (the sorts' ping-pong); options wide_finish, wide_big_bucket, wide_distinct of the context.
+// -> (h0, l0) ascending, (h1, l1) released, pc: the distinct k-mers with their counts (pc.n of them), rt.  tot: two words of device memory.
+static int wide_pass(mf_ctx *ctx, mf_buf<uint64_t> &h0, mf_buf<uint64_t> &l0, mf_buf<uint64_t> &h1, mf_buf<uint64_t> &l1, uint64_t n_p, int k, mf_buf<uint64_t> &tot,
+                     mf_wtable::piece *pc, wide_pass_route &rt) {
+    hipStream_t st = ctx->stream;
+    auto fail = [](int rc) { return rc; };
+    const int hb = 2 * k - 64;
+    // the leading bits the radix passes order: 32 -- or the high word's 24 .. 31 bits alone (k = 44 .. 47: a pass over a few bits of the low word saved)
+    const int tb = (hb >= 24 && hb < WF_BITS) ? hb : WF_BITS, hb_tb = hb | (tb << 8);
+    const uint32_t big = (uint32_t)std::min<int64_t>(WF_BIG, std::max<int64_t>(1, ctx->opt_wide_big_bucket));
+    const uint32_t dlimit = (uint32_t)std::min<int64_t>(1280, std::max<int64_t>(1, ctx->opt_wide_distinct));
+    // ascending (hi, lo).  a: the pair of arrays that holds the pass, b: the other pair (the sorts write both: no temporaries)
+    uint64_t *ah = h0.p, *al = l0.p, *bh = h1.p, *bl = l1.p;
+    auto swap_ab = [&]() { std::swap(ah, bh); std::swap(al, bl); };
+    auto sort_hi = [&](int first, int bits) { int sec = 0; if (mf_sort_u64_u64_pingpong(ctx, ah, al, n_p, first, bits, bh, bl, &sec) < 0) return MF_ERR; if (sec) swap_ab(); return MF_OK; };
+    auto sort_lo = [&](int first, int bits) { int sec = 0; if (mf_sort_u64_u64_pingpong(ctx, al, ah, n_p, first, bits, bl, bh, &sec) < 0) return MF_ERR; if (sec) swap_ab(); return MF_OK; };
+    bool sorted = false;
+    unsigned int nlist[3] = {0, 0, 0};
+    unsigned long long hstat[4] = {0, 0, 0, 0};                                      // the large buckets: entries, buckets, the largest, distinct k-mers
+    uint64_t big_total = 0;
+    if (ctx->opt_wide_finish) {
+        mf_ktimer tm(ctx, "k_wide_sort");
+        // radix passes over the leading WF_BITS bits alone (stable LSD: the low word's share of them first), then the order inside the buckets in LDS
+        const uint64_t n_tiles = (n_p + WF_TILE - 1) / WF_TILE;
+        const uint32_t tile_cap = (WF_TILE - 1) / (big + 1) + 1;                  // (a listed bucket holds more than `big` entries and starts in the tile)
+        mf_buf<unsigned long long> tile_big, bigs, wstats; mf_buf<unsigned int> n_big; mf_buf<uint32_t> tile_cnt; mf_buf<uint64_t> tile_off;
+        if (tile_big.alloc(ctx, n_tiles * tile_cap) < 0 || tile_cnt.alloc(ctx, n_tiles) < 0 || tile_off.alloc(ctx, n_tiles + 1) < 0 || n_big.alloc(ctx, 1) < 0 || wstats.alloc(ctx, 128 * 16) < 0) return fail(MF_ERR);
+        if (hipMemsetAsync(wstats.p, 0, 128 * 16 * 8, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
+        if (hb >= tb) { if (sort_hi(hb - tb, tb) < 0) return fail(MF_ERR); }
+        else {
+            if (sort_lo(64 - (tb - hb), tb - hb) < 0) return fail(MF_ERR);
+            if (hb && sort_hi(0, hb) < 0) return fail(MF_ERR);
+        }
+        // a: ascending in the leading bits -> b: ascending
+        mf_buf<unsigned long long> list2, list3;
+        unsigned int nb1 = 0, nb2 = 0, nb = 0;
+        auto fetch = [&](unsigned int *v) { return hipMemcpyAsync(v, n_big.p, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemsetAsync(n_big.p, 0, 4, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess; };
+        if (hipMemsetAsync(n_big.p, 0, 4, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
+        { mf_ktimer tf(ctx, "k_wide_finish");
+        k_wide_finish<<<(unsigned)n_tiles, WF_T, 0, st>>>(ah, al, n_p, hb_tb, big, bh, bl, tile_big.p, tile_cap, tile_cnt.p); }
+        if (mf_scan<1>(ctx, tile_cnt.p, tile_off.p, n_tiles, tot.p) < 0) return fail(MF_ERR);
+        { uint64_t v = 0;
+          if (hipMemcpyAsync(&v, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+          nb1 = (unsigned int)v; }
+        if (nb1) {
+            if (bigs.alloc(ctx, nb1) < 0 || list2.alloc(ctx, nb1) < 0) return fail(MF_ERR);
+            { mf_ktimer tf(ctx, "k_wide_big");
+            k_wide_big_list<<<wgrid(n_tiles), 256, 0, st>>>(tile_big.p, tile_cap, tile_cnt.p, tile_off.p, n_tiles, bigs.p);
+            k_wide_big<64, 512><<<nb1, 64, 0, st>>>(ah, al, n_p, hb_tb, bigs.p, std::min<uint32_t>(dlimit, 320u), bh, bl, list2.p, n_big.p, wstats.p); }
+            if (!fetch(&nb2)) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+        }
+        if (nb2) {
+            if (list3.alloc(ctx, nb2) < 0) return fail(MF_ERR);
+            { mf_ktimer tf(ctx, "k_wide_big2");
+            k_wide_big<256, 2048><<<nb2, 256, 0, st>>>(ah, al, n_p, hb_tb, list2.p, dlimit, bh, bl, list3.p, n_big.p, wstats.p); }
+            if (!fetch(&nb)) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+        }
+        sorted = true;
+        if (nb) {
+            mf_buf<uint64_t> bs, toff, th0, tl0, th1, tl1; mf_buf<uint32_t> blen, dummy, dummy2;
+            if (bs.alloc(ctx, nb) < 0 || toff.alloc(ctx, (uint64_t)nb + 1) < 0 || blen.alloc(ctx, nb) < 0 || dummy.alloc(ctx, nb) < 0 || dummy2.alloc(ctx, nb) < 0) return fail(MF_ERR);
+            if (hipMemsetAsync(dummy.p, 0, (size_t)nb * 4, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
+            if (mf_sort_u64_u32(ctx, (const uint64_t *)list3.p, dummy.p, nb, 33, bs.p, dummy2.p) < 0) return fail(MF_ERR);
+            k_wide_big_extent<<<wgrid(nb), 256, 0, st>>>(ah, al, n_p, hb_tb, bs.p, nb, blen.p);
+            if (mf_scan<1>(ctx, blen.p, toff.p, nb, tot.p) < 0) return fail(MF_ERR);
+            if (hipMemcpyAsync(&big_total, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+            ctx->n_wide_big += big_total;
+            if (big_total > n_p / 4) sorted = false;                              // too many for a side sort: all of the pass below (a still holds it)
+            else {
+                if (th0.alloc(ctx, big_total) < 0 || tl0.alloc(ctx, big_total) < 0 || th1.alloc(ctx, big_total) < 0 || tl1.alloc(ctx, big_total) < 0) return fail(MF_ERR);
+                k_wide_big_move<false><<<wgrid(big_total), 256, 0, st>>>(bs.p, toff.p, nb, big_total, ah, al, th0.p, tl0.p);
+                if (mf_sort_u64_u64(ctx, tl0.p, th0.p, big_total, 64, tl1.p, th1.p) < 0) return fail(MF_ERR);
+                if (hb) { if (mf_sort_u64_u64(ctx, th1.p, tl1.p, big_total, hb, th0.p, tl0.p) < 0) return fail(MF_ERR); } else { th0.swap(th1); tl0.swap(tl1); }
+                k_wide_big_move<true><<<wgrid(big_total), 256, 0, st>>>(bs.p, toff.p, nb, big_total, th0.p, tl0.p, bh, bl);
+                if (hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+            }
+        }
+        {
+            std::vector<unsigned long long> hs(128 * 16);
+            if (hipMemcpyAsync(hs.data(), wstats.p, hs.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+            for (int i = 0; i < 128; i++) { hstat[0] += hs[16 * i]; hstat[1] += hs[16 * i + 1]; hstat[2] = std::max(hstat[2], hs[16 * i + 2]); hstat[3] += hs[16 * i + 3]; }
+        }
+        nlist[0] = nb1; nlist[1] = nb2; nlist[2] = nb;
+        if (sorted) swap_ab();
+    }
+    rt.kept = sorted ? 1 : 0;
+    if (!sorted) {   // LSD over all 2k bits -- by the low word, then (stable) by the high word's 2k - 64 bits
+        mf_ktimer tm(ctx, "k_wide_sort");
+        if (sort_lo(0, 64) < 0 || (hb && sort_hi(0, hb) < 0)) return fail(MF_ERR);
+    }
+    if (ah != h0.p) { h0.swap(h1); l0.swap(l1); }                                  // (h0, l0): the ascending pass
+    h1.reset(); l1.reset();
+    // run lengths
+    mf_buf<uint32_t> flag; mf_buf<uint64_t> idx;
+    if (flag.alloc(ctx, n_p) < 0 || idx.alloc(ctx, n_p + 1) < 0) return fail(MF_ERR);
+    k_wide_flags<<<wgrid(n_p), 256, 0, st>>>(h0.p, l0.p, n_p, flag.p);
+    if (mf_scan<1>(ctx, flag.p, idx.p, n_p, tot.p) < 0) return fail(MF_ERR);
+    uint64_t nd = 0;
+    if (hipMemcpyAsync(&nd, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+    ctx->n_wide_hashed += hstat[0];
+    std::copy(nlist, nlist + 3, rt.nlist); std::copy(hstat, hstat + 4, rt.hstat);
+    rt.big_total = big_total; rt.tb = tb; rt.big = big;
+    mf_buf<uint64_t> start;
+    if (pc->hi.alloc(ctx, nd) < 0 || pc->lo.alloc(ctx, nd) < 0 || pc->cnt.alloc(ctx, nd) < 0 || start.alloc(ctx, nd) < 0) return fail(MF_ERR);
+    {
+        mf_ktimer tm(ctx, "k_wide_runs");
+        k_wide_heads<<<wgrid(n_p), 256, 0, st>>>(h0.p, l0.p, flag.p, idx.p, n_p, pc->hi.p, pc->lo.p, start.p);
+        k_wide_counts<<<wgrid(nd), 256, 0, st>>>(start.p, nd, n_p, pc->cnt.p);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+    pc->n = nd;
+    return MF_OK;
+}
+
 static int count_wide_impl(mf_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_read_len, int threshold,
                            mf_wtable **out) {
     mf_range rng_("mf:count_wide");
@@ -495,7 +620,6 @@ static int count_wide_impl(mf_ctx *ctx, const void *d_bases, const void *d_offse
     if (!n_reads || !n_bases) return MF_OK;
     auto fail = [&](int rc) { delete t; *out = nullptr; return rc; };
     const uint64_t n_words = (n_bases + 31) / 32;
-    const int hb = 2 * k - 64;
     mf_buf<uint32_t> vmask; mf_buf<unsigned long long> chist, cursor; mf_buf<uint64_t> tot;
     if (vmask.alloc(ctx, n_words) < 0 || chist.alloc(ctx, (1u << WG_CB) + 2) < 0 || cursor.alloc(ctx, 8) < 0 || tot.alloc(ctx, 2) < 0) return fail(MF_ERR);
     const unsigned gen_grid = (unsigned)std::min<uint64_t>((n_words + WG_T - 1) / WG_T, (uint64_t)ctx->n_cu * 8);
@@ -538,10 +662,6 @@ static int count_wide_impl(mf_ctx *ctx, const void *d_bases, const void *d_offse
     typedef mf_wtable::piece piece;
     std::vector<std::unique_ptr<piece>> &pieces = t->pieces;
     uint64_t nd_total = 0, occ_seen = 0, n_kept = 0;
-    // the leading bits the radix passes order: 32 -- or the high word's 24 .. 31 bits alone (k = 44 .. 47: a pass over a few bits of the low word saved)
-    const int tb = (hb >= 24 && hb < WF_BITS) ? hb : WF_BITS, hb_tb = hb | (tb << 8);
-    const uint32_t big = (uint32_t)std::min<int64_t>(WF_BIG, std::max<int64_t>(1, ctx->opt_wide_big_bucket));
-    const uint32_t dlimit = (uint32_t)std::min<int64_t>(1280, std::max<int64_t>(1, ctx->opt_wide_distinct));
     for (uint32_t c0 = 0; c0 < (1u << WG_CB);) {
         uint32_t c1 = c0;
         uint64_t n_p = 0;
@@ -558,108 +678,17 @@ static int count_wide_impl(mf_ctx *ctx, const void *d_bases, const void *d_offse
             if (hipMemsetAsync(cursor.p, 0, 8, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
             k_wide_kmers<false><<<gen_grid, WG_T, 0, st>>>((const uint8_t *)d_bases, n_bases, vmask.p, n_words, k, cfirst, c1, nullptr, h0.p, l0.p, cursor.p);
         }
-        // ascending (hi, lo).  a: the pair of arrays that holds the pass, b: the other pair (the sorts write both: no temporaries)
-        uint64_t *ah = h0.p, *al = l0.p, *bh = h1.p, *bl = l1.p;
-        auto swap_ab = [&]() { std::swap(ah, bh); std::swap(al, bl); };
-        auto sort_hi = [&](int first, int bits) { int sec = 0; if (mf_sort_u64_u64_pingpong(ctx, ah, al, n_p, first, bits, bh, bl, &sec) < 0) return MF_ERR; if (sec) swap_ab(); return MF_OK; };
-        auto sort_lo = [&](int first, int bits) { int sec = 0; if (mf_sort_u64_u64_pingpong(ctx, al, ah, n_p, first, bits, bl, bh, &sec) < 0) return MF_ERR; if (sec) swap_ab(); return MF_OK; };
-        bool sorted = false;
-        unsigned int nlist[3] = {0, 0, 0};
-        unsigned long long hstat[4] = {0, 0, 0, 0};                                      // the large buckets: entries, buckets, the largest, distinct k-mers
-        if (ctx->opt_wide_finish) {
-            mf_ktimer tm(ctx, "k_wide_sort");
-            // radix passes over the leading WF_BITS bits alone (stable LSD: the low word's share of them first), then the order inside the buckets in LDS
-            const uint64_t n_tiles = (n_p + WF_TILE - 1) / WF_TILE;
-            const uint32_t tile_cap = (WF_TILE - 1) / (big + 1) + 1;                  // (a listed bucket holds more than `big` entries and starts in the tile)
-            mf_buf<unsigned long long> tile_big, bigs, wstats; mf_buf<unsigned int> n_big; mf_buf<uint32_t> tile_cnt; mf_buf<uint64_t> tile_off;
-            if (tile_big.alloc(ctx, n_tiles * tile_cap) < 0 || tile_cnt.alloc(ctx, n_tiles) < 0 || tile_off.alloc(ctx, n_tiles + 1) < 0 || n_big.alloc(ctx, 1) < 0 || wstats.alloc(ctx, 128 * 16) < 0) return fail(MF_ERR);
-            if (hipMemsetAsync(wstats.p, 0, 128 * 16 * 8, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
-            if (hb >= tb) { if (sort_hi(hb - tb, tb) < 0) return fail(MF_ERR); }
-            else {
-                if (sort_lo(64 - (tb - hb), tb - hb) < 0) return fail(MF_ERR);
-                if (hb && sort_hi(0, hb) < 0) return fail(MF_ERR);
-            }
-            // a: ascending in the leading bits -> b: ascending
-            mf_buf<unsigned long long> list2, list3;
-            unsigned int nb1 = 0, nb2 = 0, nb = 0;
-            auto fetch = [&](unsigned int *v) { return hipMemcpyAsync(v, n_big.p, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemsetAsync(n_big.p, 0, 4, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess; };
-            if (hipMemsetAsync(n_big.p, 0, 4, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
-            { mf_ktimer tf(ctx, "k_wide_finish");
-            k_wide_finish<<<(unsigned)n_tiles, WF_T, 0, st>>>(ah, al, n_p, hb_tb, big, bh, bl, tile_big.p, tile_cap, tile_cnt.p); }
-            if (mf_scan<1>(ctx, tile_cnt.p, tile_off.p, n_tiles, tot.p) < 0) return fail(MF_ERR);
-            { uint64_t v = 0;
-              if (hipMemcpyAsync(&v, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-              nb1 = (unsigned int)v; }
-            if (nb1) {
-                if (bigs.alloc(ctx, nb1) < 0 || list2.alloc(ctx, nb1) < 0) return fail(MF_ERR);
-                { mf_ktimer tf(ctx, "k_wide_big");
-                k_wide_big_list<<<wgrid(n_tiles), 256, 0, st>>>(tile_big.p, tile_cap, tile_cnt.p, tile_off.p, n_tiles, bigs.p);
-                k_wide_big<64, 512><<<nb1, 64, 0, st>>>(ah, al, n_p, hb_tb, bigs.p, std::min<uint32_t>(dlimit, 320u), bh, bl, list2.p, n_big.p, wstats.p); }
-                if (!fetch(&nb2)) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-            }
-            if (nb2) {
-                if (list3.alloc(ctx, nb2) < 0) return fail(MF_ERR);
-                { mf_ktimer tf(ctx, "k_wide_big2");
-                k_wide_big<256, 2048><<<nb2, 256, 0, st>>>(ah, al, n_p, hb_tb, list2.p, dlimit, bh, bl, list3.p, n_big.p, wstats.p); }
-                if (!fetch(&nb)) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-            }
-            sorted = true;
-            if (nb) {
-                mf_buf<uint64_t> bs, toff, th0, tl0, th1, tl1; mf_buf<uint32_t> blen, dummy, dummy2;
-                if (bs.alloc(ctx, nb) < 0 || toff.alloc(ctx, (uint64_t)nb + 1) < 0 || blen.alloc(ctx, nb) < 0 || dummy.alloc(ctx, nb) < 0 || dummy2.alloc(ctx, nb) < 0) return fail(MF_ERR);
-                if (hipMemsetAsync(dummy.p, 0, (size_t)nb * 4, st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: memset failed"));
-                if (mf_sort_u64_u32(ctx, (const uint64_t *)list3.p, dummy.p, nb, 33, bs.p, dummy2.p) < 0) return fail(MF_ERR);
-                k_wide_big_extent<<<wgrid(nb), 256, 0, st>>>(ah, al, n_p, hb_tb, bs.p, nb, blen.p);
-                if (mf_scan<1>(ctx, blen.p, toff.p, nb, tot.p) < 0) return fail(MF_ERR);
-                uint64_t big_total = 0;
-                if (hipMemcpyAsync(&big_total, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-                ctx->n_wide_big += big_total;
-                if (big_total > n_p / 4) sorted = false;                              // too many for a side sort: all of the pass below (a still holds it)
-                else {
-                    if (th0.alloc(ctx, big_total) < 0 || tl0.alloc(ctx, big_total) < 0 || th1.alloc(ctx, big_total) < 0 || tl1.alloc(ctx, big_total) < 0) return fail(MF_ERR);
-                    k_wide_big_move<false><<<wgrid(big_total), 256, 0, st>>>(bs.p, toff.p, nb, big_total, ah, al, th0.p, tl0.p);
-                    if (mf_sort_u64_u64(ctx, tl0.p, th0.p, big_total, 64, tl1.p, th1.p) < 0) return fail(MF_ERR);
-                    if (hb) { if (mf_sort_u64_u64(ctx, th1.p, tl1.p, big_total, hb, th0.p, tl0.p) < 0) return fail(MF_ERR); } else { th0.swap(th1); tl0.swap(tl1); }
-                    k_wide_big_move<true><<<wgrid(big_total), 256, 0, st>>>(bs.p, toff.p, nb, big_total, th0.p, tl0.p, bh, bl);
-                    if (hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-                }
-            }
-            {
-                std::vector<unsigned long long> hs(128 * 16);
-                if (hipMemcpyAsync(hs.data(), wstats.p, hs.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-                for (int i = 0; i < 128; i++) { hstat[0] += hs[16 * i]; hstat[1] += hs[16 * i + 1]; hstat[2] = std::max(hstat[2], hs[16 * i + 2]); hstat[3] += hs[16 * i + 3]; }
-            }
-            nlist[0] = nb1; nlist[1] = nb2; nlist[2] = nb;
-            if (sorted) swap_ab();
-        }
-        if (!sorted) {   // LSD over all 2k bits -- by the low word, then (stable) by the high word's 2k - 64 bits
-            mf_ktimer tm(ctx, "k_wide_sort");
-            if (sort_lo(0, 64) < 0 || (hb && sort_hi(0, hb) < 0)) return fail(MF_ERR);
-        }
-        if (ah != h0.p) { h0.swap(h1); l0.swap(l1); }                                  // (h0, l0): the ascending pass
-        h1.reset(); l1.reset();
-        // run lengths
-        mf_buf<uint32_t> flag; mf_buf<uint64_t> idx;
-        if (flag.alloc(ctx, n_p) < 0 || idx.alloc(ctx, n_p + 1) < 0) return fail(MF_ERR);
-        k_wide_flags<<<wgrid(n_p), 256, 0, st>>>(h0.p, l0.p, n_p, flag.p);
-        if (mf_scan<1>(ctx, flag.p, idx.p, n_p, tot.p) < 0) return fail(MF_ERR);
-        uint64_t nd = 0; unsigned long long emitted = 0;
-        if (hipMemcpyAsync(&nd, tot.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(&emitted, cursor.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-        ctx->n_wide_hashed += hstat[0];
-        if (ctx->opt_verbose) fprintf(stderr, "[mf] count_wide: classes [%u, %u): %llu k-mers, %llu distinct; %llu in %llu buckets of more than %u entries (hash table; the largest %llu entries, %.1f distinct k-mers on average; lists: %u -> %u -> %u)\n", cfirst, c1,
-                                      (unsigned long long)n_p, (unsigned long long)nd, hstat[0], hstat[1], big, hstat[2], hstat[1] ? (double)hstat[3] / (double)hstat[1] : 0.0, nlist[0], nlist[1], nlist[2]);
-        if (emitted != n_p) return fail(mf_set_error("mf_count_wide_device: internal error, a pass wrote %llu of %llu k-mers", emitted, (unsigned long long)n_p));
         auto pc = std::make_unique<piece>();
-        mf_buf<uint64_t> start;
-        if (pc->hi.alloc(ctx, nd) < 0 || pc->lo.alloc(ctx, nd) < 0 || pc->cnt.alloc(ctx, nd) < 0 || start.alloc(ctx, nd) < 0) return fail(MF_ERR);
-        {
-            mf_ktimer tm(ctx, "k_wide_runs");
-            k_wide_heads<<<wgrid(n_p), 256, 0, st>>>(h0.p, l0.p, flag.p, idx.p, n_p, pc->hi.p, pc->lo.p, start.p);
-            k_wide_counts<<<wgrid(nd), 256, 0, st>>>(start.p, nd, n_p, pc->cnt.p);
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
-        pc->n = nd; nd_total += nd;
+        wide_pass_route rt;
+        { const int rc = wide_pass(ctx, h0, l0, h1, l1, n_p, k, tot, pc.get(), rt); if (rc < 0) return fail(rc); }
+        const uint64_t nd = pc->n;
+        unsigned long long emitted = 0;
+        if (hipMemcpyAsync(&emitted, cursor.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return fail(mf_set_error("mf_count_wide_device: %s", hipGetErrorString(hipGetLastError())));
+        if (ctx->opt_verbose) fprintf(stderr, "[mf] count_wide: classes [%u, %u): %llu k-mers, %llu distinct; %llu in %llu buckets of more than %u entries (hash table; the largest %llu entries, %.1f distinct k-mers on average; lists: %u -> %u -> %u)\n", cfirst, c1,
+                                      (unsigned long long)n_p, (unsigned long long)nd, rt.hstat[0], rt.hstat[1], rt.big, rt.hstat[2], rt.hstat[1] ? (double)rt.hstat[3] / (double)rt.hstat[1] : 0.0, rt.nlist[0], rt.nlist[1], rt.nlist[2]);
+        if (emitted != n_p) return fail(mf_set_error("mf_count_wide_device: internal error, a pass wrote %llu of %llu k-mers", emitted, (unsigned long long)n_p));
+        nd_total += nd;
         if (threshold >= 1) {                                                            // the cut inside the pass: the uncut piece goes back to the arena
             auto kept = std::make_unique<piece>();
             if (mf_wide_compact(ctx, pc->hi.p, pc->lo.p, pc->cnt.p, nd, threshold, *kept) < 0) return fail(MF_ERR);
@@ -780,5 +809,46 @@ extern "C" int mf_wtable_export(const mf_wtable *t, uint64_t *keys_hi, uint64_t 
         if (counts) MF_HIP(hipMemcpy(counts + at, pc->cnt.p, pc->n * 2, hipMemcpyDeviceToHost));
         at += pc->n;
     }
+    return MF_OK;
+}
+
+// =============================================================================================
+// Debugging aid of tests/test_wsort_gpu.py (not part of the C-ABI).
+//   mf_debug_wide_pass   n canonical k-mers (hi, lo) from the host, in any order, equal ones included, through wide_pass -- the body count_wide_impl runs per
+//                        pass, with the context's options wide_finish, wide_big_bucket and wide_distinct -> the n occurrences ascending (hi_out, lo_out), the
+//                        distinct k-mers with their counts (d_hi, d_lo, d_cnt: room for n entries each), *nd of them, and
+//                        info[0..10) = nlist[0..3), hstat[0..4), big_total, finish route kept (1) or all bits of the pass sorted (0), tb.
+//                        n = 0: nothing is launched (count_wide_impl skips an empty pass); info = zeros and tb.
+// =============================================================================================
+extern "C" int mf_debug_wide_pass(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, uint64_t n, uint64_t *hi_out, uint64_t *lo_out, uint64_t *d_hi, uint64_t *d_lo,
+                                  uint16_t *d_cnt, uint64_t *nd, uint64_t *info) {
+    if (!ctx || !nd || !info || (n && (!hi || !lo || !hi_out || !lo_out || !d_hi || !d_lo || !d_cnt))) return mf_set_error("mf_debug_wide_pass: NULL argument");
+    if (k < 32 || k > 63) return mf_set_error("mf_debug_wide_pass: k = %d (32 .. 63)", k);
+    if (n >= (1ull << 32)) return mf_set_error("mf_debug_wide_pass: %llu entries (fewer than 2^32 are supported)", (unsigned long long)n);
+    const int hb = 2 * k - 64;
+    for (uint64_t i = 0; i < n; i++)
+        if (hi[i] >> hb) return mf_set_error("mf_debug_wide_pass: entry %llu: high word %llx has more than 2k - 64 = %d bits", (unsigned long long)i, (unsigned long long)hi[i], hb);
+    *nd = 0;
+    std::fill(info, info + 10, 0ull);
+    info[9] = (uint64_t)((hb >= 24 && hb < WF_BITS) ? hb : WF_BITS);
+    if (!n) return MF_OK;
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    mf_buf<uint64_t> h0, l0, h1, l1, tot;
+    MF_TRY(h0.alloc(ctx, n)); MF_TRY(l0.alloc(ctx, n)); MF_TRY(h1.alloc(ctx, n)); MF_TRY(l1.alloc(ctx, n)); MF_TRY(tot.alloc(ctx, 2));
+    MF_HIP(hipMemcpyAsync(h0.p, hi, n * 8, hipMemcpyHostToDevice, st));
+    MF_HIP(hipMemcpyAsync(l0.p, lo, n * 8, hipMemcpyHostToDevice, st));
+    mf_wtable::piece pc;
+    wide_pass_route rt;
+    MF_TRY(wide_pass(ctx, h0, l0, h1, l1, n, k, tot, &pc, rt));
+    MF_HIP(hipMemcpyAsync(hi_out, h0.p, n * 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipMemcpyAsync(lo_out, l0.p, n * 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipMemcpyAsync(d_hi, pc.hi.p, pc.n * 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipMemcpyAsync(d_lo, pc.lo.p, pc.n * 8, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipMemcpyAsync(d_cnt, pc.cnt.p, pc.n * 2, hipMemcpyDeviceToHost, st));
+    MF_HIP(hipStreamSynchronize(st));
+    *nd = pc.n;
+    const uint64_t v[10] = {rt.nlist[0], rt.nlist[1], rt.nlist[2], rt.hstat[0], rt.hstat[1], rt.hstat[2], rt.hstat[3], rt.big_total, (uint64_t)rt.kept, (uint64_t)rt.tb};
+    std::copy(v, v + 10, info);
     return MF_OK;
 }
