@@ -244,6 +244,26 @@ int  mf_wtable_write_kmers(mf_wtable *t, int threshold, const char *kmers_bin, c
 /* [mf_table_load_kmers] records with count <= freq_threshold dropped; one file: one ascending piece, no sort; several files: a k-mer gets the
  * sum of its counts, saturating at 32767 */
 int  mf_wtable_load_kmers(mf_ctx *ctx, const char *const *files, int nfiles, int freq_threshold, int k, mf_wtable **out);
+/* [mf_table_write_kmers_filtered] the records of t with count > threshold whose k-mer has a value > filter_threshold in `filter` (absent: 0),
+ * in the format and order of mf_wtable_write_kmers; *n_written (may be NULL) = records.  Both tables of one context and one k; the filter
+ * gets its lookup index (mf_wtable_lookup's), t is ordered in place. */
+int  mf_wtable_write_kmers_filtered(mf_wtable *t, int threshold, mf_wtable *filter, int filter_threshold, const char *kmers_bin,
+                                    uint64_t *n_written);
+/* [mf_unique_kmers_multi_tables] the same definition on (high, low) keys (mf_wjoin.hip): cnt(x), sum(x) wrapped to a Java short, an x that a
+ * filter table holds with count > b knocked out, *n_union = distinct keys of the inputs, out[i - min_samples] = the records (x, sum(x)) with
+ * sum(x) > b and cnt(x) >= i as ascending wide tables, the list ending with the first empty one (included); out and counts sized as there.
+ * The join sorts and reduces per slice of the KEY RANGE (option "stats_slices" forces their number; the result is the same for every number);
+ * a slice that does not fit its share of HBM is an error that names the option.  Errors as there (min_samples > max_samples with the
+ * reference's message, max_bad < 0, more than 32767 inputs), and: a NULL table, a table of another context, tables of different k -- each
+ * names the list and the table's number.  Tables in any order (fresh from the count or loaded) are taken as they are. */
+int  mf_unique_kmers_multi_wide_tables(mf_ctx *ctx, mf_wtable *const *inputs, int n_inputs, mf_wtable *const *filters, int n_filters,
+                                       int max_bad, int min_samples, int max_samples, mf_wtable **out, int *n_out, uint64_t *n_union,
+                                       uint64_t *counts);
+/* [mf_unique_kmers_multi] wide .kmers.bin files, each loaded with mf_wtable_load_kmers(file, max_bad), one sample resident at a time (a file
+ * is read once per slice) -> <out_dir>/filtered_<i>.kmers.bin, wide records.  32 <= k <= 63. */
+int  mf_unique_kmers_multi_wide(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters,
+                                int max_bad, int k, int min_samples, int max_samples, const char *out_dir, int *n_out, uint64_t *n_union,
+                                uint64_t *counts);
 /* [mf_comps_write / mf_comps_load] on load the members must be < 4^k and ascending inside a component */
 int  mf_wcomps_write(const mf_wcomps *c, const char *components_bin, const char *stat_txt);
 int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **out);

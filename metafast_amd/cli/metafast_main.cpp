@@ -95,6 +95,9 @@ extern "C" int mf_comp2seq_wide(mf_ctx *, const char *, int, int, const char *, 
 extern "C" int mf_seq2comp_wide(mf_ctx *, const char *const *, int, int, const char *, const char *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_comp2graph_wide(mf_ctx *, const char *, int, const char *const *, int, int, const char *, uint64_t *, uint64_t *, uint64_t *) __attribute__((weak));
 extern "C" int mf_paths_create_wide(mf_ctx *, mf_wcomps *, const uint32_t *, uint64_t, int, uint64_t, mf_paths **) __attribute__((weak));
+extern "C" int mf_unique_kmers_multi_wide(mf_ctx *, const char *const *, int, const char *const *, int, int, int, int, int, const char *, int *, uint64_t *, uint64_t *)
+    __attribute__((weak));
+extern "C" int mf_wtable_write_kmers_filtered(mf_wtable *, int, mf_wtable *, int, const char *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -1159,7 +1162,7 @@ static vector<PV> tool_posneg(Run &r) {
     vector<string> pos = r.a.list("positiveReads"), neg = r.a.list("negativeReads");
     logmsg("INFO", "Found %zu samples in positive class and %zu samples in negative class to process", pos.size(), neg.size());
     if (pos.empty() || neg.empty()) die("No libraries to process!!! Can't continue the calculations.");
-    check_k(k);
+    if (!wide_k(k)) check_k(k);                                            // (--wide-kmers and k > 31: run_kmer_counter_many counts wide, the files are wide .kmers.bin)
     const int b = r.num("maximal-bad-frequency");
     vector<string> kp, kn;
     for (int side = 0; side < 2; side++) {                                 // (each step with the counter's own defaults in ITS work directory)
@@ -1176,8 +1179,11 @@ static vector<PV> tool_posneg(Run &r) {
 static vector<PV> tool_kmers_filter(Run &r) {
     // KmersFilter.java:80-121: every input k-mers file is written again with the records whose k-mer is frequent enough
     // in the filter files (IOUtils.filterAndPrintKmers, src/io/IOUtils.java:101-123)
+    // (--wide-kmers and k > 31: the same on wide .kmers.bin files, mf_wtable_write_kmers_filtered)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
+    if (wide) r.entry(mf_wtable_write_kmers_filtered && mf_wtable_load_kmers && mf_wtable_stats && mf_wtable_destroy, "mf_wtable_write_kmers_filtered");
     const int b = r.num("maximal-bad-frequence"), mt = r.num("max-thresh");
     const string out_dir = r.str("output-dir");
     mkdirs(out_dir);
@@ -1185,25 +1191,32 @@ static vector<PV> tool_kmers_filter(Run &r) {
     const vector<string> ff = r.a.list("filter-kmers");
     auto fp = cptrs(ff);
     mf_table *filter = nullptr;
-    check(mf_table_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &filter));
+    mf_wtable *wfilter = nullptr;
+    check(wide ? mf_wtable_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &wfilter) : mf_table_load_kmers(ctx, fp.data(), (int)fp.size(), b, k, &filter));
     vector<string> written;
     for (auto &f : r.a.list("k-mers")) {
         mf_table *t = nullptr;
+        mf_wtable *wt = nullptr;
         const char *one[1] = {f.c_str()};
-        check(mf_table_load_kmers(ctx, one, 1, b, k, &t));
+        check(wide ? mf_wtable_load_kmers(ctx, one, 1, b, k, &wt) : mf_table_load_kmers(ctx, one, 1, b, k, &t));
         string name = basename_of(f);
         for (size_t q; (q = name.find(".kmers.bin")) != string::npos;) name.erase(q, 10);        // replaceAll(".kmers.bin", "")
         const string out = out_dir + "/" + name + ".kmers.bin";
         uint64_t c = 0, size = 0;
-        check(mf_table_write_kmers_filtered(t, b, filter, mt * (int)ff.size(), out.c_str(), &c));
-        check(mf_table_stats(t, &size, nullptr));
+        if (wide) {
+            check(mf_wtable_write_kmers_filtered(wt, b, wfilter, mt * (int)ff.size(), out.c_str(), &c));
+            check(mf_wtable_stats(wt, &size, nullptr, nullptr));
+        } else {
+            check(mf_table_write_kmers_filtered(t, b, filter, mt * (int)ff.size(), out.c_str(), &c));
+            check(mf_table_stats(t, &size, nullptr));
+        }
         logmsg("INFO", "%s k-mers found, %s (%.1f%%) of them survived after filtering", group_digits(size).c_str(), group_digits(c).c_str(),
                size ? c * 100.0 / size : 0.0);
         logmsg("INFO", "Filtered k-mers printed to %s", out.c_str());
-        mf_table_destroy(t);
+        if (wide) mf_wtable_destroy(wt); else mf_table_destroy(t);
         written.push_back(out);
     }
-    mf_table_destroy(filter);
+    if (wide) mf_wtable_destroy(wfilter); else mf_table_destroy(filter);
     return {written.empty() ? PV::null("resulting-kmers-file") : PV::file("resulting-kmers-file", written.back())};
 }
 static vector<PV> tool_kmers_samples_counter(Run &r) {
@@ -1396,20 +1409,22 @@ static vector<PV> tool_kmers_per_sample(Run &r) {
 }
 static vector<PV> tool_unique_kmers_multi(Run &r) {
     // UniqueKmersMultipleSamplesFinder.java:84-185: the k-mers that enough input files hold and no filter file does
+    // (--wide-kmers and k > 31: the same on wide .kmers.bin files, mf_unique_kmers_multi_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const int mn = r.num("min-samples"), mx = r.num("max-samples"), b = r.num("maximal-bad-frequence");
     if (mn > mx) die("--min-samples parameter cannot be greater than --max-samples parameter.");
     const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
     const vector<string> files = r.a.list("k-mers"), filt = r.a.list("filter-kmers");
-    r.entry(mf_unique_kmers_multi != nullptr, "mf_unique_kmers_multi");
+    if (wide) r.entry(mf_unique_kmers_multi_wide != nullptr, "mf_unique_kmers_multi_wide"); else r.entry(mf_unique_kmers_multi != nullptr, "mf_unique_kmers_multi");
     mf_ctx *ctx = r.ctx();
     mkdirs(out_dir); mkdirs(st_dir);
     auto fp = cptrs(files), ff = cptrs(filt);
     const int64_t top = std::min<int64_t>(mx, std::max<int64_t>(mn, (int64_t)files.size() + 1));
     vector<uint64_t> c((size_t)std::max<int64_t>(1, top - mn + 1), 0);
     int n_out = 0; uint64_t n_union = 0;
-    check(mf_unique_kmers_multi(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, mn, mx, out_dir.c_str(), &n_out, &n_union, c.data()));
+    check((wide ? mf_unique_kmers_multi_wide : mf_unique_kmers_multi)(ctx, fp.data(), (int)fp.size(), ff.data(), (int)ff.size(), b, k, mn, mx, out_dir.c_str(), &n_out, &n_union, c.data()));
     for (int q = 0; q < n_out; q++) {
         const string out = out_dir + "/filtered_" + std::to_string(mn + q) + ".kmers.bin";
         logmsg("INFO", "%s k-mers found, %s (%s%%) of them is good (present in one dataset and missing in other)", group_digits(n_union).c_str(),

@@ -48,6 +48,10 @@ int mf_windex_build(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, uint64_
 // entries of (hi, lo, cnt)[n] with cnt > thr -> a new piece (order kept)
 int mf_wide_compact(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, int thr, mf_wtable::piece &out);
 
+// (hi, lo, cnt)[n] in any order -> the entries ascending in (hi, lo) (equal k-mers side by side), flag[i] = 1 at the head of a run of equal k-mers,
+// idx[i] = runs before entry i (idx[n] = n_runs), by two stable radix passes (mf_wio.hip)
+struct mf_wide_runs { mf_buf<uint64_t> hi, lo, idx; mf_buf<uint16_t> cnt; mf_buf<uint32_t> flag; uint64_t n_runs = 0; };
+int mf_wide_sort_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wide_runs &r);
 // (hi, lo, cnt)[n] in any order -> out: the distinct k-mers ascending with the saturating sum of their counts (mf_wio.hip)
 int mf_wide_merge_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wtable::piece &out);
 

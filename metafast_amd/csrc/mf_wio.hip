@@ -228,12 +228,12 @@ __global__ void k_wio_sum_runs(const uint64_t *__restrict__ hi, const uint64_t *
     const uint64_t o = idx[i];
     ohi[o] = hi[i]; olo[o] = lo[i]; ocnt[o] = (uint16_t)(s > (uint32_t)MF_MAX_COUNT ? (uint32_t)MF_MAX_COUNT : s);
 }
-// (hi, lo, cnt)[n] in any order -> out: the distinct k-mers ascending, each with the saturating sum of its entries' counts.  Two stable passes
-// -- the low word, then the high word's 2k - 64 bits -- that carry the entry's index, then the saturating sum of every run of equal k-mers
-// (mf_wtable_load_kmers over several files; comp2seq's table of all members, mf_wcomp2seq.hip)
-int mf_wide_merge_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wtable::piece &out) {
+// (hi, lo, cnt)[n] in any order -> r: the entries ascending in (hi, lo), the head of every run of equal k-mers flagged, idx = the run an entry
+// stands in.  Two stable passes -- the low word, then the high word's 2k - 64 bits -- that carry the entry's index (what mf_wide_merge_runs
+// sums up, and the wide join of mf_wjoin.hip reduces)
+int mf_wide_sort_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wide_runs &r) {
     hipStream_t st = ctx->stream;
-    out.n = 0;
+    r.n_runs = 0;
     if (!n) return MF_OK;
     const int hb = 2 * k - 64;
     mf_buf<uint64_t> k0, k1, i0, i1;
@@ -244,20 +244,29 @@ int mf_wide_merge_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *l
         k_wio_gather64<<<wio_grid(n), 256, 0, st>>>(i1.p, hi, n, k0.p);                    // hi' in k0
         MF_TRY(mf_sort_u64_u64(ctx, k0.p, i1.p, n, hb, k1.p, i0.p));                       // (hi'', idx'') in (k1, i0)
     } else i0.swap(i1);                                                                    // (k = 32: every high word is 0)
-    mf_buf<uint64_t> slo; mf_buf<uint16_t> scnt;
-    MF_TRY(slo.alloc(ctx, n)); MF_TRY(scnt.alloc(ctx, n));
-    k_wio_gather_pair<<<wio_grid(n), 256, 0, st>>>(i0.p, lo, cnt, n, slo.p, scnt.p);
-    const uint64_t *shi = k1.p;
+    MF_TRY(r.lo.alloc(ctx, n)); MF_TRY(r.cnt.alloc(ctx, n));
+    k_wio_gather_pair<<<wio_grid(n), 256, 0, st>>>(i0.p, lo, cnt, n, r.lo.p, r.cnt.p);
     if (!hb) { MF_HIP(hipMemsetAsync(k1.p, 0, n * 8, st)); }
-    mf_buf<uint32_t> flag; mf_buf<uint64_t> idx, tot;
-    MF_TRY(flag.alloc(ctx, n)); MF_TRY(idx.alloc(ctx, n + 1)); MF_TRY(tot.alloc(ctx, 1));
-    k_wio_heads<<<wio_grid(n), 256, 0, st>>>(shi, slo.p, n, flag.p);
-    MF_TRY(mf_scan<1>(ctx, flag.p, idx.p, n, tot.p));
-    uint64_t nd = 0;
-    MF_HIP(hipMemcpyAsync(&nd, tot.p, 8, hipMemcpyDeviceToHost, st));
+    r.hi.swap(k1);
+    mf_buf<uint64_t> tot;
+    MF_TRY(r.flag.alloc(ctx, n)); MF_TRY(r.idx.alloc(ctx, n + 1)); MF_TRY(tot.alloc(ctx, 1));
+    k_wio_heads<<<wio_grid(n), 256, 0, st>>>(r.hi.p, r.lo.p, n, r.flag.p);
+    MF_TRY(mf_scan<1>(ctx, r.flag.p, r.idx.p, n, tot.p));
+    MF_HIP(hipMemcpyAsync(&r.n_runs, tot.p, 8, hipMemcpyDeviceToHost, st));
     MF_HIP(hipStreamSynchronize(st));
+    return MF_OK;
+}
+// (hi, lo, cnt)[n] in any order -> out: the distinct k-mers ascending, each with the saturating sum of its entries' counts: the saturating sum of
+// every run of equal k-mers that mf_wide_sort_runs leaves (mf_wtable_load_kmers over several files; comp2seq's table of all members, mf_wcomp2seq.hip)
+int mf_wide_merge_runs(mf_ctx *ctx, int k, const uint64_t *hi, const uint64_t *lo, const uint16_t *cnt, uint64_t n, mf_wtable::piece &out) {
+    hipStream_t st = ctx->stream;
+    out.n = 0;
+    if (!n) return MF_OK;
+    mf_wide_runs r;
+    MF_TRY(mf_wide_sort_runs(ctx, k, hi, lo, cnt, n, r));
+    const uint64_t nd = r.n_runs;
     MF_TRY(out.hi.alloc(ctx, nd)); MF_TRY(out.lo.alloc(ctx, nd)); MF_TRY(out.cnt.alloc(ctx, nd));
-    k_wio_sum_runs<<<wio_grid(n), 256, 0, st>>>(shi, slo.p, scnt.p, flag.p, idx.p, n, out.hi.p, out.lo.p, out.cnt.p);
+    k_wio_sum_runs<<<wio_grid(n), 256, 0, st>>>(r.hi.p, r.lo.p, r.cnt.p, r.flag.p, r.idx.p, n, out.hi.p, out.lo.p, out.cnt.p);
     MF_HIP(hipStreamSynchronize(st));
     out.n = nd;
     return MF_OK;

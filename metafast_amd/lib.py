@@ -53,6 +53,9 @@ _SIGS = {
     "mf_count_reads_wide": (i32, [vp, C.POINTER(cp), i32, i32, i32, pvp]),
     "mf_wtable_write_kmers": (i32, [vp, i32, cp, cp, pu64]),
     "mf_wtable_load_kmers": (i32, [vp, C.POINTER(cp), i32, i32, i32, pvp]),
+    "mf_wtable_write_kmers_filtered": (i32, [vp, i32, vp, i32, cp, pu64]),
+    "mf_unique_kmers_multi_wide_tables": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, C.POINTER(C.c_int), pu64, vp]),
+    "mf_unique_kmers_multi_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, i32, i32, cp, C.POINTER(C.c_int), pu64, vp]),
     "mf_wcomps_write": (i32, [vp, cp, cp]),
     "mf_wcomps_load": (i32, [vp, cp, i32, pvp]),
     "mf_features_wide": (i32, [vp, cp, cp, i32, i32, cp, cp]),
@@ -878,6 +881,28 @@ class Context:
                                            min_samples, max_samples, os.fsencode(out_dir), C.byref(n_out), C.byref(n_union), counts.ctypes.data))
         return n_union.value, [int(c) for c in counts[:n_out.value]]
 
+    def unique_kmers_multi_wide(self, inputs, filters, max_bad=1, min_samples=1, max_samples=1):
+        """NO-REFERENCE EXTENSION: unique_kmers_multi on WideTables (32 <= k <= 63) ->
+        ([WideTable of filtered_<i> for i = min_samples ... up to the first empty one], n_union, [c_i])"""
+        hi = (C.c_void_p * max(len(inputs), 1))(*[t.h for t in inputs])
+        hf = (C.c_void_p * max(len(filters), 1))(*[t.h for t in filters])
+        slots = self._ukm_slots(len(inputs), min_samples, max_samples)
+        out = (C.c_void_p * slots)()
+        counts = np.zeros(slots, dtype=np.uint64)
+        n_out, n_union = C.c_int(), C.c_uint64()
+        _check(lib().mf_unique_kmers_multi_wide_tables(self.h, hi, len(inputs), hf, len(filters), max_bad, min_samples, max_samples, out,
+                                                       C.byref(n_out), C.byref(n_union), counts.ctypes.data))
+        return [WideTable(self, C.c_void_p(out[i])) for i in range(n_out.value)], n_union.value, [int(c) for c in counts[:n_out.value]]
+
+    def unique_kmers_multi_wide_files(self, in_files, filter_files, k, out_dir, max_bad=1, min_samples=1, max_samples=1):
+        """the same from wide .kmers.bin files -> out_dir/filtered_<i>.kmers.bin (wide records); returns (n_union, [c_i])"""
+        slots = self._ukm_slots(len(in_files), min_samples, max_samples)
+        counts = np.zeros(slots, dtype=np.uint64)
+        n_out, n_union = C.c_int(), C.c_uint64()
+        _check(lib().mf_unique_kmers_multi_wide(self.h, _cfiles(in_files), len(in_files), _cfiles(filter_files), len(filter_files), max_bad, k,
+                                                min_samples, max_samples, os.fsencode(out_dir), C.byref(n_out), C.byref(n_union), counts.ctypes.data))
+        return n_union.value, [int(c) for c in counts[:n_out.value]]
+
     def kmers_multiple_filters(self, table, cd, uc, nonibd, max_bad=1):
         """IOUtils.MultipleFiltersAndPrintKmers (src/io/IOUtils.java:125-213) on resident tables -> (Table of the kept entries,
         int64[m][3] distinct (cd, uc, nonibd) triples in ascending order, uint64[m] entries of each, found, kept)"""
@@ -994,6 +1019,13 @@ class WideTable:
         """wide .kmers.bin (records with count > threshold, ascending) + optionally .stat.txt; -> number of records written"""
         n = C.c_uint64()
         _check(lib().mf_wtable_write_kmers(self.h, threshold, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
+        return n.value
+
+    def write_kmers_filtered(self, threshold, filter_table, filter_threshold, kmers_bin):
+        """the records with count > threshold whose k-mer has a value > filter_threshold in filter_table (absent: 0) -> wide .kmers.bin;
+        -> number of records written"""
+        n = C.c_uint64()
+        _check(lib().mf_wtable_write_kmers_filtered(self.h, threshold, filter_table.h, filter_threshold, os.fsencode(kmers_bin), C.byref(n)))
         return n.value
 
     def lookup(self, kmers):
