@@ -44,6 +44,7 @@ typedef struct mf_seqs  mf_seqs;   /* unitigs with weights (Deque<Sequence>)    
 typedef struct mf_comps mf_comps;  /* connected components (List<ConnectedComponent>)       */
 typedef struct mf_dcc   mf_dcc;    /* one rank's part of the distributed component cutter   */
 typedef struct mf_reads mf_reads;  /* the reads of a list of files, in HBM (NamedSource<Dna>) */
+typedef struct mf_kps mf_kps;      /* the k-mer x sample abundance table of a cohort (mf_kmers_per_sample_tables, ..._wide_tables) */
 
 const char *mf_last_error(void);
 const char *mf_version(void);
@@ -264,6 +265,28 @@ int  mf_unique_kmers_multi_wide_tables(mf_ctx *ctx, mf_wtable *const *inputs, in
 int  mf_unique_kmers_multi_wide(mf_ctx *ctx, const char *const *in_files, int n_inputs, const char *const *filter_files, int n_filters,
                                 int max_bad, int k, int min_samples, int max_samples, const char *out_dir, int *n_out, uint64_t *n_union,
                                 uint64_t *counts);
+/* [mf_kmers_per_sample_tables] the same definition on (high, low) keys (mf_wkps.hip): the candidates are the k-mers some sample
+ * (the first included) holds with count > max_bad, n(x) = the samples j >= 1 (count_first != 0: j >= 0) that do, selected: n(x) >= thresh =
+ * n * percent / 100 in Java int arithmetic (thresh <= 0: every candidate, thresh > n: none).  *out = an mf_kps handle (below, with the narrow
+ * tool): the M selected k-mers ascending in (high, low), their n(x), the n x M row-major uint16 matrix of the samples' counts (0 = absent or
+ * count <= max_bad).  mf_kps_destroy, mf_kps_stats, mf_kps_row_text and mf_kps_header_text (its k must be the tables' k) take the handle;
+ * mf_kps_export and mf_kps_device_view hold one word a k-mer and refuse it by name: mf_kps_export_wide and mf_kps_device_view_wide are its
+ * forms (and refuse a handle of k <= 31).  The union sorts and reduces per slice of the key range (option "stats_slices"; the result is the
+ * same for every number).  Errors, each named and none a write out of bounds: n < 1 or n > 32767; a NULL table, a table of another
+ * context, tables of different k, k outside 32 ... 63; a sample or a slice of 2^31 or more entries (raise stats_slices); 2^32 - 1 or more
+ * selected k-mers (raise -perc); a matrix of n x M x 2 bytes that does not fit the free device memory (raise -perc, or use the file form).
+ * Tables in any order (fresh from the count, in several pieces, or loaded) are taken as they are. */
+int  mf_kmers_per_sample_wide_tables(mf_ctx *ctx, mf_wtable *const *tables, int n, int max_bad, int percent, int count_first, mf_kps **out);
+/* device pointers, valid until the destroy: uint64 high[M], uint64 low[M], uint16 n(x)[M], uint16 matrix[n][M]; any may be NULL */
+int  mf_kps_device_view_wide(const mf_kps *r, const void **d_hi, const void **d_lo, const void **d_nsamples, const void **d_matrix);
+/* host copies: hi[M], lo[M], nsamples[M], matrix[n * M]; any may be NULL */
+int  mf_kps_export_wide(const mf_kps *r, uint64_t *hi, uint64_t *lo, uint16_t *nsamples, uint16_t *matrix);
+/* [mf_kmers_per_sample] the file form on wide .kmers.bin files, max_bad = 0: every load is mf_wtable_load_kmers(file, 1, 0, k), one sample
+ * resident at a time -- loaded, gathered, formatted, downloaded and written before the next; the matrix is never resident and every file
+ * is read twice (once more per further slice).  out_txt as there: "\t" + the k bases per selected k-mer, then per file its name with
+ * every ".kmers.bin" removed and "\t" + count per selected k-mer.  32 <= k <= 63; *n_kmers (may be NULL) = M. */
+int  mf_kmers_per_sample_wide(mf_ctx *ctx, const char *const *files, int n, int k, int percent, int count_first, const char *out_txt,
+                              uint64_t *n_kmers);
 /* [mf_comps_write / mf_comps_load] on load the members must be < 4^k and ascending inside a component */
 int  mf_wcomps_write(const mf_wcomps *c, const char *components_bin, const char *stat_txt);
 int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **out);
@@ -764,7 +787,6 @@ int mf_kmers_grouped_count(mf_ctx *ctx, const char *const *kmers_files, int n_km
  * samples' counts (0 = absent or count <= max_bad).  Errors: n < 1 or n > 32767, a key >= 2^62, 2^32 - 1 or more selected k-mers, more
  * than 2^32 - 1 union k-mers in one hash slice, and a matrix of n x M x 2 bytes that does not fit the free device memory (select fewer
  * k-mers with a higher percent, or use the file form). */
-typedef struct mf_kps mf_kps;
 int  mf_kmers_per_sample_tables(mf_ctx *ctx, mf_table *const *tables, int n, int max_bad, int percent, int count_first, mf_kps **out);
 void mf_kps_destroy(mf_kps *r);
 int  mf_kps_stats(const mf_kps *r, uint64_t *n_kmers, int *n_samples);                 /* either may be NULL */

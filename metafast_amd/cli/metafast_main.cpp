@@ -98,6 +98,7 @@ extern "C" int mf_paths_create_wide(mf_ctx *, mf_wcomps *, const uint32_t *, uin
 extern "C" int mf_unique_kmers_multi_wide(mf_ctx *, const char *const *, int, const char *const *, int, int, int, int, int, const char *, int *, uint64_t *, uint64_t *)
     __attribute__((weak));
 extern "C" int mf_wtable_write_kmers_filtered(mf_wtable *, int, mf_wtable *, int, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_per_sample_wide(mf_ctx *, const char *const *, int, int, int, int, const char *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -1389,20 +1390,22 @@ static vector<PV> tool_kmers_grouped_counter(Run &r) {
 static vector<PV> tool_kmers_per_sample(Run &r) {
     // KmersPerSampleCounter.java:56-157: the abundance in every file of the k-mers that enough files hold (no -b: every load is at 0).
     // The first file is not counted, as in the reference (:82-96): count_first = 0.
+    // (--wide-kmers and k > 31: the same on wide .kmers.bin files, mf_kmers_per_sample_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const int perc = r.num("percent-present");
     const string out_dir = r.str("output-dir");
     const vector<string> files = r.a.list("k-mers");
     mkdirs(out_dir);
-    r.entry(mf_kmers_per_sample != nullptr, "mf_kmers_per_sample");
+    if (wide) r.entry(mf_kmers_per_sample_wide != nullptr, "mf_kmers_per_sample_wide"); else r.entry(mf_kmers_per_sample != nullptr, "mf_kmers_per_sample");
     mf_ctx *ctx = r.ctx();
     auto fp = cptrs(files);
     const string out = out_dir + "/selected_kmers_" + std::to_string(perc) + ".txt";
     uint64_t c = 0;
     logmsg("INFO", "Loading all k-mers...");
     logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
-    check(mf_kmers_per_sample(ctx, fp.data(), (int)fp.size(), k, perc, 0, out.c_str(), &c));
+    check((wide ? mf_kmers_per_sample_wide : mf_kmers_per_sample)(ctx, fp.data(), (int)fp.size(), k, perc, 0, out.c_str(), &c));
     logmsg("DEBUG", "Selected k-mers = %s", group_digits(c).c_str());
     logmsg("INFO", "K-mers printed to %s", out.c_str());
     return {};

@@ -14,10 +14,8 @@
 // The file form streams: one sample is loaded, gathered, formatted, downloaded and written before the next; the N x M matrix never
 // exists and every file is read twice, as in the reference.
 #include "mf_join.h"
+#include "mf_kps.h"
 #include <algorithm>
-
-#define MF_KPS_MAX_N 32767                // n(x) is a Java short
-#define MF_KPS_MAX_WIDTH 6                // "\t" + the five digits of a uint16
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // kernels
@@ -84,16 +82,11 @@ __global__ __launch_bounds__(256) void k_kps_format(const uint16_t *__restrict__
 // ---------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------
-static unsigned kps_grid(uint64_t m) { return (unsigned)std::max<uint64_t>(1, (m + 255) / 256); }      // (m < 2^32)
-
 // the selected k-mers: ascending keys, n(x), and the index key -> column
 struct kps_sel {
     uint64_t m = 0, cap = 0;
     mf_buf<uint64_t> keys; mf_buf<uint16_t> ns; mf_buf<mf_uslot> slots;
 };
-
-// KmersPerSampleCounter.java:101, in Java int arithmetic: the product wraps, the division truncates toward zero
-static int kps_thresh(int N, int percent) { return (int)(int32_t)((uint32_t)N * (uint32_t)percent) / 100; }
 
 static int kps_check(const char *what, const void *ctx, const void *in, int n) {
     if (!ctx || (n > 0 && !in)) return mf_set_error("%s: NULL argument", what);
@@ -148,16 +141,8 @@ static int kps_gather(mf_ctx *ctx, const mf_join_get &get, int j, int max_bad, c
     });
 }
 
-// the text of one row: buffers kept over the rows of a run
-struct kps_text {
-    mf_buf<uint32_t> w; mf_buf<uint64_t> off, total; mf_buf<uint8_t> out;
-    int alloc(mf_ctx *ctx, uint64_t m) {
-        MF_TRY(w.alloc(ctx, m)); MF_TRY(off.alloc(ctx, m + 1)); MF_TRY(total.alloc(ctx, 1));
-        return out.alloc(ctx, m * MF_KPS_MAX_WIDTH);
-    }
-};
-// row[0 .. m) -> tx.out[0 .. *bytes) = "\t" + decimal per value
-static int kps_format(mf_ctx *ctx, const uint16_t *row, uint64_t m, kps_text &tx, uint64_t *bytes) {
+// row[0 .. m) -> tx.out[0 .. *bytes) = "\t" + decimal per value (shared with the wide tool: mf_kps.h)
+int kps_format(mf_ctx *ctx, const uint16_t *row, uint64_t m, kps_text &tx, uint64_t *bytes) {
     *bytes = 0;
     if (!m) return MF_OK;
     {
@@ -189,7 +174,7 @@ static int kps_header(mf_ctx *ctx, const uint64_t *keys, uint64_t m, int k, mf_b
 }
 
 // device bytes -> the file, through two halves of the context's staging memory: a piece crosses while the one before it is written
-static int kps_write(mf_ctx *ctx, const uint8_t *d_src, uint64_t bytes, FILE *f, const char *path) {
+int kps_write(mf_ctx *ctx, const uint8_t *d_src, uint64_t bytes, FILE *f, const char *path) {
     const size_t SLOT = (size_t)16 << 20;
     if (!bytes) return MF_OK;
     MF_TRY(mf_ensure_pin_pool(ctx, 8 * SLOT));                                 // (what the table writers of mf_io.hip ask for: one pool)
@@ -206,7 +191,7 @@ static int kps_write(mf_ctx *ctx, const uint8_t *d_src, uint64_t bytes, FILE *f,
 }
 
 // File.getName().replace(".kmers.bin", "") (:144): every occurrence goes, left to right, in one pass
-static std::string kps_row_name(const char *path) {
+std::string kps_row_name(const char *path) {
     std::string s(path);
     const size_t sl = s.rfind('/');
     if (sl != std::string::npos) s.erase(0, sl + 1);
@@ -217,12 +202,16 @@ static std::string kps_row_name(const char *path) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------------------------------------------------------
-struct mf_kps {
-    mf_ctx *ctx = nullptr;
-    int n_samples = 0;
-    uint64_t m = 0;
-    mf_buf<uint64_t> keys; mf_buf<uint16_t> ns, mat;
-};
+int kps_matrix_fits(mf_ctx *ctx, int n, uint64_t m) {
+    size_t fr = 0, tot = 0;
+    MF_HIP(hipMemGetInfo(&fr, &tot));
+    const uint64_t room = ctx->opt_kps_matrix_bytes > 0 ? (uint64_t)ctx->opt_kps_matrix_bytes : (uint64_t)fr + mf_arena_idle(ctx);
+    if (m && (uint64_t)n > room / 2 / m)
+        return mf_set_error("kmers-per-sample: the count matrix of %d samples x %llu k-mers x 2 bytes does not fit the %llu bytes of free device memory: "
+                            "select fewer k-mers with a higher -perc (--percent-present), or use the file form, which streams the rows",
+                            n, (unsigned long long)m, (unsigned long long)room);
+    return MF_OK;
+}
 
 extern "C" int mf_kmers_per_sample_tables(mf_ctx *ctx, mf_table *const *tables, int n, int max_bad, int percent, int count_first, mf_kps **out) {
     mf_range rng_("mf:kmers_per_sample");
@@ -235,14 +224,7 @@ extern "C" int mf_kmers_per_sample_tables(mf_ctx *ctx, mf_table *const *tables, 
     const mf_join_get get = mf_join_tables(tables);
     kps_sel sel;
     MF_TRY(kps_select(ctx, get, n, total, max_bad, percent, count_first, sel));
-    // the matrix has to fit what is free now (the arena's idle regions are free to it)
-    size_t fr = 0, tot = 0;
-    MF_HIP(hipMemGetInfo(&fr, &tot));
-    const uint64_t room = ctx->opt_kps_matrix_bytes > 0 ? (uint64_t)ctx->opt_kps_matrix_bytes : (uint64_t)fr + mf_arena_idle(ctx);
-    if (sel.m && (uint64_t)n > room / 2 / sel.m)
-        return mf_set_error("kmers-per-sample: the count matrix of %d samples x %llu k-mers x 2 bytes does not fit the %llu bytes of free device memory: "
-                            "select fewer k-mers with a higher -perc (--percent-present), or use the file form, which streams the rows",
-                            n, (unsigned long long)sel.m, (unsigned long long)room);
+    MF_TRY(kps_matrix_fits(ctx, n, sel.m));
     std::unique_ptr<mf_kps> r(new mf_kps());
     r->ctx = ctx; r->n_samples = n; r->m = sel.m;
     MF_TRY(r->mat.alloc(ctx, (size_t)n * sel.m));
@@ -268,6 +250,7 @@ extern "C" int mf_kps_stats(const mf_kps *r, uint64_t *n_kmers, int *n_samples) 
 
 extern "C" int mf_kps_device_view(const mf_kps *r, const void **d_keys, const void **d_nsamples, const void **d_matrix) {
     if (!r) return mf_set_error("mf_kps_device_view: NULL argument");
+    if (r->wide_k) return mf_set_error("mf_kps_device_view: a result of k = %d holds two words a k-mer: call mf_kps_device_view_wide", r->wide_k);
     if (d_keys) *d_keys = r->keys.p;
     if (d_nsamples) *d_nsamples = r->ns.p;
     if (d_matrix) *d_matrix = r->mat.p;
@@ -276,6 +259,7 @@ extern "C" int mf_kps_device_view(const mf_kps *r, const void **d_keys, const vo
 
 extern "C" int mf_kps_export(const mf_kps *r, uint64_t *keys, uint16_t *nsamples, uint16_t *matrix) {
     if (!r) return mf_set_error("mf_kps_export: NULL argument");
+    if (r->wide_k) return mf_set_error("mf_kps_export: a result of k = %d holds two words a k-mer: call mf_kps_export_wide", r->wide_k);
     mf_ctx *ctx = r->ctx;
     MF_HIP(hipSetDevice(ctx->device));
     if (r->m) {
@@ -298,13 +282,15 @@ static int kps_text_out(mf_ctx *ctx, const uint8_t *d_text, uint64_t bytes, uint
 
 extern "C" int mf_kps_header_text(const mf_kps *r, int k, uint8_t *text, uint64_t cap, uint64_t *n) {
     if (!r || !n || (cap && !text)) return mf_set_error("mf_kps_header_text: NULL argument");
-    if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
+    if (r->wide_k && k != r->wide_k) return mf_set_error("mf_kps_header_text: k = %d, the result holds k-mers of k = %d", k, r->wide_k);
+    if (!r->wide_k && (k < 1 || k > 31)) return mf_set_error("k must be in [1,31]");
     mf_ctx *ctx = r->ctx;
     MF_HIP(hipSetDevice(ctx->device));
     *n = r->m * (uint64_t)(k + 1);
     if (cap < *n) return MF_OK;                          // (the size alone: the caller comes again with room)
     mf_buf<uint8_t> d; uint64_t bytes = 0;
-    MF_TRY(kps_header(ctx, r->keys.p, r->m, k, d, &bytes));
+    if (r->wide_k) MF_TRY(mf_wkps_header(ctx, r->hi.p, r->lo.p, r->m, k, d, &bytes));
+    else MF_TRY(kps_header(ctx, r->keys.p, r->m, k, d, &bytes));
     return kps_text_out(ctx, d.p, bytes, text, cap, n);
 }
 

@@ -17,15 +17,25 @@ struct mf_wjoin_sample {
 };
 using mf_wjoin_get = std::function<int(int j, mf_wjoin_sample &)>;
 
-// what a slice leaves: its distinct k-mers ascending, cnt = the samples that hold one, sum = the sum of their counts mod 2^16, knocked = 0
+// what a slice leaves: its distinct k-mers ascending, cnt = the samples that hold one, sum = the sum of their counts mod 2^16 (with weights: the sum of
+// the weights of the samples that hold it), knocked = 0
 struct mf_wjoin_union { mf_buf<uint64_t> hi, lo; mf_buf<uint16_t> cnt, sum; mf_buf<uint8_t> knocked; uint64_t n = 0; };
 
 // S slices of the key range and the room (entries) of a slice's gather buffer for `total` entries in all samples: option stats_slices forces S
 int mf_wjoin_plan(mf_ctx *ctx, uint64_t total, uint32_t *S, uint64_t *cap);
-// slice s of S: every entry with count > b of the n_in samples -> u.  A slice that holds more than cap entries is an error (raise stats_slices)
-int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, int b, uint32_t S, uint32_t s, uint64_t cap, mf_wjoin_union &u);
+// slice s of S: every entry with count > b of the n_in samples -> u.  A slice that holds more than cap entries is an error (raise stats_slices).
+// weight (n_in values on the host, or NULL): sample j's entries bring weight[j] in place of their counts
+int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, int b, uint32_t S, uint32_t s, uint64_t cap, mf_wjoin_union &u,
+                         const uint16_t *weight = nullptr);
 // every entry with count > b of sample t that u holds sets that k-mer's knocked byte
 int mf_wjoin_knock(mf_ctx *ctx, const mf_wtable *t, int b, mf_wjoin_union &u);
+// the entries with sel > thr of (hi, lo, val, sel)[n], order kept -> (ohi, olo, oval[, osel])[*m]; osel may be NULL
+int mf_wjoin_select(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *val, const uint16_t *sel, uint64_t n, int thr, mf_buf<uint64_t> &ohi,
+                    mf_buf<uint64_t> &olo, mf_buf<uint16_t> &oval, mf_buf<uint16_t> *osel, uint64_t *m);
+// the k of a list of tables, every one checked: NULL, another context, another k.  *k = 0: no table so far; total may be NULL
+int mf_wjoin_tables_check(mf_ctx *ctx, mf_wtable *const *t, int n, const char *what, int *k, uint64_t *total);
+// the records (18 bytes each) of a list of wide .kmers.bin files, by their sizes
+int mf_wjoin_file_records(const char *const *files, int n, uint64_t *total);
 
 #ifdef __HIPCC__
 // The slice of a k-mer: the leading 24 bits of its 2k scaled to [0, S) -- monotone in the k-mer, so a slice is a range of keys and the slices'

@@ -21,7 +21,8 @@ static unsigned wj_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 2
 
 // the entries with count > b of a sample's piece that belong to slice s -> (ohi, olo, ocnt)[*cursor ...], in any order (the sort comes next); an entry
 // past `cap` is counted and not written: the host reads the cursor and reports the slice.  (uniform trip count: mf_wave_reserve)
-__global__ __launch_bounds__(256) void k_wj_gather(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, const uint16_t *__restrict__ cnt, uint64_t n, int b,
+// weight >= 0: the payload of an entry is the sample's weight, not its count (mf_wjoin_slice_union)
+__global__ __launch_bounds__(256) void k_wj_gather(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, const uint16_t *__restrict__ cnt, uint64_t n, int b, int weight,
                                                    int hb, uint32_t S, uint32_t s, uint64_t *__restrict__ ohi, uint64_t *__restrict__ olo, uint16_t *__restrict__ ocnt,
                                                    uint64_t cap, unsigned int *__restrict__ cursor) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void k_wj_gather(const uint64_t *__restrict__ 
             if ((int)c > b) { h = hi[i]; l = lo[i]; keep = mf_wjoin_slice(h, l, hb, S) == s; }
         }
         const uint32_t r = mf_wave_reserve(cursor, keep ? 1u : 0u);
-        if (keep && (uint64_t)r < cap) { ohi[r] = h; olo[r] = l; ocnt[r] = c; }
+        if (keep && (uint64_t)r < cap) { ohi[r] = h; olo[r] = l; ocnt[r] = weight >= 0 ? (uint16_t)weight : c; }
     }
 }
 // the head of a run of equal k-mers (at most one entry per sample: at most 32767 long) -> (hi, lo, entries, the sum of their counts mod 2^16) at the run's number
@@ -123,7 +124,8 @@ int mf_wjoin_plan(mf_ctx *ctx, uint64_t total, uint32_t *S_out, uint64_t *cap_ou
     return MF_OK;
 }
 
-int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, int b, uint32_t S, uint32_t s, uint64_t cap, mf_wjoin_union &u) {
+int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, int b, uint32_t S, uint32_t s, uint64_t cap, mf_wjoin_union &u,
+                         const uint16_t *weight) {
     hipStream_t st = ctx->stream;
     const int hb = 2 * k - 64;
     u.n = 0;
@@ -138,7 +140,7 @@ int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, 
         for (auto &pc : sm.t->pieces) {
             if (!pc->n) continue;
             mf_ktimer tm(ctx, "k_wj_gather");
-            k_wj_gather<<<wj_grid(pc->n), 256, 0, st>>>(pc->hi.p, pc->lo.p, pc->cnt.p, pc->n, b, hb, S, s, ghi.p, glo.p, gcnt.p, cap, cur.p);
+            k_wj_gather<<<wj_grid(pc->n), 256, 0, st>>>(pc->hi.p, pc->lo.p, pc->cnt.p, pc->n, b, weight ? (int)weight[j] : -1, hb, S, s, ghi.p, glo.p, gcnt.p, cap, cur.p);
         }
         MF_HIP(hipMemcpyAsync(&m, cur.p, 4, hipMemcpyDeviceToHost, st));
         const hipError_t e = hipStreamSynchronize(st);
@@ -173,8 +175,8 @@ int mf_wjoin_knock(mf_ctx *ctx, const mf_wtable *t, int b, mf_wjoin_union &u) {
 }
 
 // the entries with sel > thr of (hi, lo, val, sel)[n], order kept -> (ohi, olo, oval[, osel])[*m]
-static int wj_select(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *val, const uint16_t *sel, uint64_t n, int thr, mf_buf<uint64_t> &ohi,
-                     mf_buf<uint64_t> &olo, mf_buf<uint16_t> &oval, mf_buf<uint16_t> *osel, uint64_t *m) {
+int mf_wjoin_select(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *val, const uint16_t *sel, uint64_t n, int thr, mf_buf<uint64_t> &ohi,
+                    mf_buf<uint64_t> &olo, mf_buf<uint16_t> &oval, mf_buf<uint16_t> *osel, uint64_t *m) {
     hipStream_t st = ctx->stream;
     uint64_t keep = 0;
     mf_buf<uint32_t> flag; mf_buf<uint64_t> idx, tot;
@@ -246,7 +248,7 @@ static int wukm_join(mf_ctx *ctx, int k, const mf_wjoin_get &get_in, int n_in, c
         }
         // the survivors of the slice, in buffers of their size
         auto p = std::make_unique<part>();
-        MF_TRY(wj_select(ctx, u.hi.p, u.lo.p, u.sum.p, u.cnt.p, u.n, 0, p->hi, p->lo, p->sum, &p->sel, &p->n));
+        MF_TRY(mf_wjoin_select(ctx, u.hi.p, u.lo.p, u.sum.p, u.cnt.p, u.n, 0, p->hi, p->lo, p->sum, &p->sel, &p->n));
         n += p->n;
         if (p->n) parts.push_back(std::move(p));
     }
@@ -270,7 +272,7 @@ static int wukm_join(mf_ctx *ctx, int k, const mf_wjoin_get &get_in, int n_in, c
     for (int64_t i = min_samples; i <= (int64_t)max_samples; i++) {
         mf_buf<uint64_t> ohi, olo; mf_buf<uint16_t> ov; uint64_t m = 0;
         // (no key is held by more than n_in samples, and every survivor by at least one)
-        if (i <= n_in) MF_TRY(wj_select(ctx, all.hi.p, all.lo.p, all.sum.p, all.sel.p, n, (int)std::max<int64_t>(i - 1, 0), ohi, olo, ov, nullptr, &m));
+        if (i <= n_in) MF_TRY(mf_wjoin_select(ctx, all.hi.p, all.lo.p, all.sum.p, all.sel.p, n, (int)std::max<int64_t>(i - 1, 0), ohi, olo, ov, nullptr, &m));
         mf_wtable *t = nullptr;
         MF_TRY(wj_table(ctx, k, b, ohi, olo, ov, m, &t));
         outs.push_back(t);
@@ -281,7 +283,7 @@ static int wukm_join(mf_ctx *ctx, int k, const mf_wjoin_get &get_in, int n_in, c
 }
 
 // the k of a list of tables, every one checked: NULL, another context, another k.  *k = 0: no table so far
-static int wj_tables_check(mf_ctx *ctx, mf_wtable *const *t, int n, const char *what, int *k, uint64_t *total) {
+int mf_wjoin_tables_check(mf_ctx *ctx, mf_wtable *const *t, int n, const char *what, int *k, uint64_t *total) {
     for (int j = 0; j < n; j++) {
         if (!t[j]) return mf_set_error("%s: table %d is NULL", what, j);
         if (t[j]->ctx != ctx) return mf_set_error("%s: table %d belongs to another context", what, j);
@@ -302,8 +304,8 @@ extern "C" int mf_unique_kmers_multi_wide_tables(mf_ctx *ctx, mf_wtable *const *
     MF_TRY(wukm_check(n_inputs, max_bad, min_samples, max_samples));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t total = 0; int k = 0;
-    MF_TRY(wj_tables_check(ctx, inputs, n_inputs, "mf_unique_kmers_multi_wide_tables (inputs)", &k, &total));
-    MF_TRY(wj_tables_check(ctx, filters, n_filters, "mf_unique_kmers_multi_wide_tables (filters)", &k, nullptr));
+    MF_TRY(mf_wjoin_tables_check(ctx, inputs, n_inputs, "mf_unique_kmers_multi_wide_tables (inputs)", &k, &total));
+    MF_TRY(mf_wjoin_tables_check(ctx, filters, n_filters, "mf_unique_kmers_multi_wide_tables (filters)", &k, nullptr));
     if (!k) k = 32;                                         // (no table at all: one empty result)
     const mf_wjoin_get gi = [inputs](int j, mf_wjoin_sample &s) { s.t = inputs[j]; return MF_OK; };
     const mf_wjoin_get gf = [filters](int j, mf_wjoin_sample &s) { s.t = filters[j]; return MF_OK; };
@@ -315,7 +317,7 @@ extern "C" int mf_unique_kmers_multi_wide_tables(mf_ctx *ctx, mf_wtable *const *
     return MF_OK;
 }
 
-static int wj_file_records(const char *const *files, int n, uint64_t *total) {
+int mf_wjoin_file_records(const char *const *files, int n, uint64_t *total) {
     *total = 0;
     for (int j = 0; j < n; j++) {
         if (!files[j]) return mf_set_error("file %d is NULL", j);
@@ -336,8 +338,8 @@ extern "C" int mf_unique_kmers_multi_wide(mf_ctx *ctx, const char *const *in_fil
     MF_TRY(wukm_check(n_inputs, max_bad, min_samples, max_samples));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t total = 0, tf = 0;
-    MF_TRY(wj_file_records(in_files, n_inputs, &total));
-    MF_TRY(wj_file_records(filter_files, n_filters, &tf));
+    MF_TRY(mf_wjoin_file_records(in_files, n_inputs, &total));
+    MF_TRY(mf_wjoin_file_records(filter_files, n_filters, &tf));
     // one sample resident at a time, loaded like IOUtils.loadKmers(file, b)
     auto files = [ctx, max_bad, k](const char *const *f) {
         return [=](int j, mf_wjoin_sample &s) { s.own = true; return mf_wtable_load_kmers(ctx, f + j, 1, max_bad, k, &s.t); };

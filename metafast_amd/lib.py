@@ -56,6 +56,10 @@ _SIGS = {
     "mf_wtable_write_kmers_filtered": (i32, [vp, i32, vp, i32, cp, pu64]),
     "mf_unique_kmers_multi_wide_tables": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, C.POINTER(C.c_int), pu64, vp]),
     "mf_unique_kmers_multi_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, i32, i32, cp, C.POINTER(C.c_int), pu64, vp]),
+    "mf_kmers_per_sample_wide_tables": (i32, [vp, vp, i32, i32, i32, i32, pvp]),
+    "mf_kmers_per_sample_wide": (i32, [vp, C.POINTER(cp), i32, i32, i32, i32, cp, pu64]),
+    "mf_kps_device_view_wide": (i32, [vp, pvp, pvp, pvp, pvp]),
+    "mf_kps_export_wide": (i32, [vp, vp, vp, vp, vp]),
     "mf_wcomps_write": (i32, [vp, cp, cp]),
     "mf_wcomps_load": (i32, [vp, cp, i32, pvp]),
     "mf_features_wide": (i32, [vp, cp, cp, i32, i32, cp, cp]),
@@ -855,6 +859,20 @@ class Context:
         _check(lib().mf_kmers_per_sample(self.h, _cfiles(files), len(files), k, percent, 1 if count_first else 0, os.fsencode(out_txt), C.byref(n)))
         return n.value
 
+    def kmers_per_sample_wide(self, tables, percent=20, max_bad=0, count_first=False):
+        """NO-REFERENCE EXTENSION: kmers_per_sample on WideTables (32 <= k <= 63) -> KmersPerSample whose export() gives the k-mers as
+        two words, (hi, lo, n, matrix)"""
+        h = (C.c_void_p * max(len(tables), 1))(*[t.h if t is not None else None for t in tables])
+        r = C.c_void_p()
+        _check(lib().mf_kmers_per_sample_wide_tables(self.h, h, len(tables), max_bad, percent, 1 if count_first else 0, C.byref(r)))
+        return KmersPerSample(self, r, wide=True)
+
+    def kmers_per_sample_wide_files(self, files, k, out_txt, percent=20, count_first=False):
+        """the same from wide .kmers.bin files, streamed -> out_txt (selected_kmers_<percent>.txt); returns the number of selected k-mers"""
+        n = C.c_uint64()
+        _check(lib().mf_kmers_per_sample_wide(self.h, _cfiles(files), len(files), k, percent, 1 if count_first else 0, os.fsencode(out_txt), C.byref(n)))
+        return n.value
+
     @staticmethod
     def _ukm_slots(n_inputs, min_samples, max_samples):
         return max(1, min(max_samples, max(min_samples, n_inputs + 1)) - min_samples + 1)
@@ -1252,10 +1270,11 @@ class WideComps:
 
 
 class KmersPerSample:
-    """the result of Context.kmers_per_sample: M selected k-mers x N samples, resident in HBM"""
+    """the result of Context.kmers_per_sample (or kmers_per_sample_wide: wide = True, the k-mers as two words): M selected k-mers x N
+    samples, resident in HBM"""
 
-    def __init__(self, ctx, h):
-        self.ctx, self.h = ctx, h
+    def __init__(self, ctx, h, wide=False):
+        self.ctx, self.h, self.wide = ctx, h, wide
 
     def close(self):
         if getattr(self, "h", None) and _lib is not None and self.ctx.h:
@@ -1275,14 +1294,23 @@ class KmersPerSample:
         return n.value, m.value
 
     def device_view(self):
-        """device pointers (keys uint64[M], n(x) uint16[M], matrix uint16[N][M])"""
+        """device pointers (keys uint64[M], n(x) uint16[M], matrix uint16[N][M]); a wide result: (hi, lo, n(x), matrix)"""
         k, s, m = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if self.wide:
+            l = C.c_void_p()
+            _check(lib().mf_kps_device_view_wide(self.h, C.byref(k), C.byref(l), C.byref(s), C.byref(m)))
+            return k.value, l.value, s.value, m.value
         _check(lib().mf_kps_device_view(self.h, C.byref(k), C.byref(s), C.byref(m)))
         return k.value, s.value, m.value
 
     def export(self):
-        """-> (keys uint64[M] ascending, n(x) uint16[M], matrix uint16[N][M])"""
+        """-> (keys uint64[M] ascending, n(x) uint16[M], matrix uint16[N][M]); a wide result: (hi uint64[M], lo uint64[M], n(x), matrix),
+        ascending in (hi, lo)"""
         n, m = self.shape()
+        if self.wide:
+            hi, lo, ns, mat = np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.uint16), np.zeros((n, m), np.uint16)
+            _check(lib().mf_kps_export_wide(self.h, hi.ctypes.data, lo.ctypes.data, ns.ctypes.data, mat.ctypes.data))
+            return hi, lo, ns, mat
         keys, ns, mat = np.zeros(m, np.uint64), np.zeros(m, np.uint16), np.zeros((n, m), np.uint16)
         _check(lib().mf_kps_export(self.h, keys.ctypes.data, ns.ctypes.data, mat.ctypes.data))
         return keys, ns, mat
