@@ -128,6 +128,7 @@ struct mf_ctx {
     int64_t dcc_test_calls[3] = {0, 0, 0};   // (option dcc_test_fail: the calls made so far, by which)
     struct mf_skm_snap *skm_snap = nullptr;  // tests only (mf_debug_skm_records, mf_skm.hip): the counting run hands its records over in front of k_skm_count and ends there; null otherwise
     struct mf_wskm_snap *wskm_snap = nullptr;   // tests only (mf_debug_wskm_records, mf_wskm.hip): the wide record path copies every stage's output to the host as it goes; null otherwise
+    struct mf_count_snap *count_snap = nullptr;   // tests only (mf_debug_count_stages, mf_count.hip): the one-record-per-k-mer path copies every stage's output to the host as it goes; null otherwise
     // workspace arena: a few large hipMalloc'd regions, sub-allocated with first-fit + coalescing free lists.
     // Everything runs on one stream, so a block can be handed out again as soon as it is released.
     struct span { size_t off, sz; };

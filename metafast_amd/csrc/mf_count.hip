@@ -658,6 +658,31 @@ int mf_count_plan(mf_ctx *ctx, uint64_t n_occ, uint64_t n_reads, uint64_t n_base
     return MF_OK;
 }
 
+// What mf_debug_count_stages (the end of this file) takes out of a count on the one-record-per-k-mer path: every stage's output as the next
+// stage finds it.  ctx->count_snap is null in production; with it set, mf_count_core fills the buffers a stage writes only in part with 0xA5
+// bytes before the launch and copies to the host behind the stage (host code only: no kernel of its own, no launch changed).
+struct mf_count_snap_level {
+    int bits_used = 0, bits = 0;                   // bits_used: the digits' bits of the levels in front of this one
+    std::vector<uint64_t> buf, ostart;             // the level's output buffer; start / padded length of every sub-partition
+    std::vector<uint32_t> olen;
+};
+struct mf_count_snap {
+    int stage = 0;                                 // 0: nothing (no read, no base), 1: K0, 2: K1, 3: every K2 level, 4: K3, 5: the table
+    uint64_t n_words = 0, n_occ = 0, wpb = 0, overflow = 0, n_dist = 0;
+    int B = 0, G = 0, staged = 0, part_bits = 0;
+    std::vector<int> lv;
+    std::vector<uint32_t> vmask, blockhist, plen1, plen, dcount;
+    std::vector<uint64_t> blockstart, buf1, pstart1, pstart, keys, part_off, dk;
+    std::vector<uint16_t> cnt, dc;
+    std::vector<mf_count_snap_level> levels;       // the K2 levels, in order
+};
+template <typename T> static int snap_take(mf_ctx *ctx, std::vector<T> &to, const T *d, size_t n) {
+    to.resize(n);
+    if (n) MF_HIP(hipMemcpyAsync(to.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    return MF_OK;
+}
+
 // thr >= 0: keep only the k-mers with count > thr (*n_all = distinct k-mers before the cut); thr < 0: keep everything
 int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
                   int k, int min_len, mf_table **out, int thr, uint64_t *n_all) {
@@ -667,6 +692,7 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
     if (((uintptr_t)d_bases & 15) != 0) return mf_set_error("mf_count_device: d_bases must be 16-byte aligned");
     MF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
+    mf_count_snap *snap = ctx->count_snap;               // (tests: mf_debug_count_stages)
 
     if (n_reads == 0 || n_bases == 0) return mf_table_adopt(ctx, k, 0, 0, nullptr, 0, nullptr, 0, out);
 
@@ -685,6 +711,7 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
     unsigned long long n_occ = 0;
     MF_HIP(hipMemcpyAsync(&n_occ, &scal.p[0], 8, hipMemcpyDeviceToHost, st));
     MF_HIP(hipStreamSynchronize(st));
+    if (snap) { snap->stage = 1; snap->n_words = n_words; snap->n_occ = n_occ; MF_TRY(snap_take(ctx, snap->vmask, vmask.p, n_words)); }
     if (n_occ == 0) return mf_table_adopt(ctx, k, 0, 0, nullptr, 0, nullptr, 0, out);
 
     std::vector<int> lv, slv; bool assembled = false; int B = 0;
@@ -724,6 +751,7 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
     uint64_t cap = n_occ + (uint64_t)MF_LINE * nd1 * G;    // upper bound of the padded total
     mf_buf<uint64_t> bufA; MF_TRY(bufA.alloc(ctx, cap));
     const bool staged = ctx->opt_scatter_staged != 0;
+    if (snap) MF_HIP(hipMemsetAsync(bufA.p, 0xA5, cap * sizeof(uint64_t), st));
     {
         size_t lds = mf_stage_bytes(nd1);
         mf_ktimer t(ctx, "k_l1_scatter");
@@ -740,6 +768,16 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
     mf_buf<uint64_t> pstart; MF_TRY(pstart.alloc(ctx, np));
     mf_buf<uint32_t> plen; MF_TRY(plen.alloc(ctx, np));
     k_l1_dir<<<(nd1 + 255) / 256, 256, 0, st>>>(blockstart.p, G, nd1, pstart.p, plen.p);
+    if (snap) {
+        snap->lv = lv; snap->B = B; snap->G = G; snap->wpb = wpb; snap->staged = staged ? 1 : 0;
+        MF_TRY(snap_take(ctx, snap->blockhist, blockhist.p, (size_t)nd1 * G));
+        MF_TRY(snap_take(ctx, snap->blockstart, blockstart.p, (size_t)nd1 * G + 1));
+        MF_TRY(snap_take(ctx, snap->buf1, bufA.p, cap));
+        MF_TRY(snap_take(ctx, snap->pstart1, pstart.p, np));
+        MF_TRY(snap_take(ctx, snap->plen1, plen.p, np));
+        MF_HIP(hipGetLastError());
+        snap->stage = 2;
+    }
     vmask.reset(); blockhist.reset(); blockstart.reset();
 
     // ---- K2 levels ----
@@ -754,6 +792,7 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
         mf_buf<uint32_t> olen; MF_TRY(olen.alloc(ctx, np2));
         size_t lds = mf_stage_bytes(nd);
         unsigned grid = (unsigned)std::min<uint64_t>(np, (uint64_t)ctx->n_cu * (lds > 72 * 1024 ? 1 : 2));
+        if (snap) MF_HIP(hipMemsetAsync(bufB.p, 0xA5, cap2 * sizeof(uint64_t), st));
         {
             mf_ktimer t(ctx, "k_split");
             if (staged) {
@@ -765,6 +804,15 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
             }
         }
         MF_DBG(ctx, "k_split");
+        if (snap) {
+            snap->levels.emplace_back();
+            mf_count_snap_level &L = snap->levels.back();
+            L.bits_used = bits_used; L.bits = bits;
+            MF_TRY(snap_take(ctx, L.buf, bufB.p, cap2));
+            MF_TRY(snap_take(ctx, L.ostart, ostart.p, np2));
+            MF_TRY(snap_take(ctx, L.olen, olen.p, np2));
+            MF_HIP(hipGetLastError());
+        }
         // swap
         std::swap(bufA.p, bufB.p); std::swap(bufA.n, bufB.n);
         std::swap(pstart.p, ostart.p); std::swap(pstart.n, ostart.n);
@@ -775,6 +823,7 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
     // ---- K3 ----
     mf_buf<uint16_t> cnt; MF_TRY(cnt.alloc(ctx, cap));
     mf_buf<uint32_t> dcount; MF_TRY(dcount.alloc(ctx, np));
+    if (snap) { snap->stage = 3; MF_HIP(hipMemsetAsync(cnt.p, 0xA5, cap * sizeof(uint16_t), st)); }
     {
         size_t lds = (size_t)(MF_COUNT_SLOTS + 64) * 12;
         MF_TRY(set_lds(k_count, lds));
@@ -793,6 +842,14 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
     unsigned long long res[4];
     MF_HIP(hipMemcpyAsync(res, scal.p, 32, hipMemcpyDeviceToHost, st));
     MF_HIP(hipStreamSynchronize(st));
+    if (snap) {
+        MF_TRY(snap_take(ctx, snap->keys, bufA.p, cap));
+        MF_TRY(snap_take(ctx, snap->cnt, cnt.p, cap));
+        MF_TRY(snap_take(ctx, snap->dcount, dcount.p, np));
+        MF_TRY(snap_take(ctx, snap->pstart, pstart.p, np));
+        MF_TRY(snap_take(ctx, snap->plen, plen.p, np));
+        snap->overflow = res[2]; snap->stage = 4;
+    }
     if (res[2]) return mf_set_error("k_count: LDS table overflow (about %d or more distinct k-mers in one partition); "
                                     "lower option part_target", MF_COUNT_SLOTS);
     const uint64_t n_dist = res[3];
@@ -815,6 +872,13 @@ int mf_count_core(mf_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets
         (*out)->part_bits = total_bits;
         (*out)->part_off_bytes = doff.bytes();
         (*out)->d_part_off = doff.take();
+    }
+    if (snap) {
+        snap->n_dist = n_dist; snap->part_bits = (*out)->part_bits;
+        MF_TRY(snap_take(ctx, snap->dk, (const uint64_t *)(*out)->d_keys, n_dist));
+        MF_TRY(snap_take(ctx, snap->dc, (const uint16_t *)(*out)->d_counts, n_dist));
+        if ((*out)->d_part_off) MF_TRY(snap_take(ctx, snap->part_off, (const uint64_t *)(*out)->d_part_off, (size_t)np + 1));
+        snap->stage = 5;
     }
     if (n_all) *n_all = n_dist;
     if (thr >= 0) {                                     // (this path keeps the cut as a separate pass)
@@ -906,4 +970,89 @@ extern "C" int mf_count_device_above(mf_ctx *ctx, const void *d_bases, const voi
     *out = nullptr;
     return mf_count_core(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_reads, n_bases, k, min_read_len, out,
                          threshold < 0 ? -1 : threshold, n_distinct_all);
+}
+
+// =============================================================================================
+// Debugging aid of tests/test_count_stages_gpu.py (not part of the C-ABI; host code only, no kernel of its own): the stages of a count on the
+// one-record-per-k-mer path.  The call is mf_count_device's own (mf_count_core with the context's options) with ctx->count_snap set, which makes
+// mf_count_core fill the level buffers and cnt with 0xA5 bytes before the launches that write them in part, and copy to the host behind every stage.
+// A call that does not take this path (k >= MF_SKM_MIN_K with option skm != 0, unless the super-k-mer path hands the input back) is an error.  A
+// count that ends with `k_count: LDS table overflow` still hands its snapshot over (stage 4, the overflow word set, no table).
+//   mf_debug_count_stages -> *out: the snapshot (mf_debug_count_free)
+//   mf_debug_count_info   level < 0: info[0..16) = stage reached (0 no read or base, 1 K0: no k-mer occurrence, 4 K3: overflow, 5 the table),
+//                         n_words, n_occ, B of the plan, G, words per workgroup, staged (0 / 1), number of levels, entries of the level-1
+//                         buffer, final partitions, entries of the final buffer, the overflow word, part_bits of the table, its entries,
+//                         entries of d_part_off, 0; info[16..24) = the levels' bits
+//                         level 1 .. levels - 1 (a K2 level): info[0..5) = bits_used going in, bits, entries of its buffer, partitions in, out
+//   mf_debug_count_copy   what (level < 0): 0 vmask, 1 blockhist, 2 blockstart, 3 the level-1 buffer, 4 / 5 pstart / plen after level 1, 6 / 7 keys / cnt
+//                         behind k_count, 8 dcount, 9 / 10 pstart / plen in front of k_count, 11 d_part_off, 12 / 13 the table's keys / counts; of
+//                         K2 level `level`: 0 its buffer, 1 ostart, 2 olen.  bytes: the size of dst, which must be the array's
+// =============================================================================================
+extern "C" void mf_debug_count_free(mf_count_snap *s) { delete s; }
+extern "C" int mf_debug_count_stages(mf_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_reads, uint64_t n_bases, int k, int min_len, mf_count_snap **out) {
+    if (!ctx || !out) return mf_set_error("mf_debug_count_stages: NULL argument");
+    *out = nullptr;
+    mf_count_snap *S = new mf_count_snap();
+    mf_table *t = nullptr;
+    ctx->count_snap = S;
+    const int rc = mf_count_core(ctx, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_reads, n_bases, k, min_len, &t, -1, nullptr);
+    ctx->count_snap = nullptr;
+    if (t) mf_table_destroy(t);
+    if (rc < 0 && !(S->stage == 4 && S->overflow)) { delete S; return rc; }
+    if (rc >= 0 && S->stage == 1 && S->n_occ != 0) {
+        delete S;
+        return mf_set_error("mf_debug_count_stages: k = %d, option skm = %d: the call took the super-k-mer path, not the one-record-per-k-mer path", k, (int)ctx->opt_skm);
+    }
+    *out = S;
+    return MF_OK;
+}
+extern "C" int mf_debug_count_info(const mf_count_snap *s, int level, uint64_t *info) {
+    if (!s || !info) return mf_set_error("mf_debug_count_info: NULL argument");
+    if (level < 0) {
+        if (s->lv.size() > 8) return mf_set_error("mf_debug_count_info: %zu levels", s->lv.size());
+        const uint64_t v[16] = {(uint64_t)s->stage, s->n_words, s->n_occ, (uint64_t)s->B, (uint64_t)s->G, s->wpb, (uint64_t)s->staged, s->lv.size(), s->buf1.size(),
+                                s->pstart.size(), s->keys.size(), s->overflow, (uint64_t)s->part_bits, s->n_dist, s->part_off.size(), 0};
+        for (int i = 0; i < 16; i++) info[i] = v[i];
+        for (size_t i = 0; i < 8; i++) info[16 + i] = i < s->lv.size() ? (uint64_t)s->lv[i] : 0;
+        return MF_OK;
+    }
+    if (level < 1 || (size_t)level > s->levels.size()) return mf_set_error("mf_debug_count_info: level %d of %zu K2 levels", level, s->levels.size());
+    const mf_count_snap_level &L = s->levels[(size_t)level - 1];
+    info[0] = (uint64_t)L.bits_used; info[1] = (uint64_t)L.bits; info[2] = L.buf.size(); info[3] = L.ostart.size() >> L.bits; info[4] = L.ostart.size();
+    return MF_OK;
+}
+template <typename T> static int snap_give(const std::vector<T> &v, void *dst, uint64_t bytes) {
+    if (bytes != v.size() * sizeof(T)) return mf_set_error("mf_debug_count_copy: the array has %zu bytes, the caller's room %llu", v.size() * sizeof(T), (unsigned long long)bytes);
+    if (bytes) memcpy(dst, v.data(), bytes);
+    return MF_OK;
+}
+extern "C" int mf_debug_count_copy(const mf_count_snap *s, int level, int what, void *dst, uint64_t bytes) {
+    if (!s || (bytes && !dst)) return mf_set_error("mf_debug_count_copy: NULL argument");
+    if (level < 0) {
+        switch (what) {
+            case 0: return snap_give(s->vmask, dst, bytes);
+            case 1: return snap_give(s->blockhist, dst, bytes);
+            case 2: return snap_give(s->blockstart, dst, bytes);
+            case 3: return snap_give(s->buf1, dst, bytes);
+            case 4: return snap_give(s->pstart1, dst, bytes);
+            case 5: return snap_give(s->plen1, dst, bytes);
+            case 6: return snap_give(s->keys, dst, bytes);
+            case 7: return snap_give(s->cnt, dst, bytes);
+            case 8: return snap_give(s->dcount, dst, bytes);
+            case 9: return snap_give(s->pstart, dst, bytes);
+            case 10: return snap_give(s->plen, dst, bytes);
+            case 11: return snap_give(s->part_off, dst, bytes);
+            case 12: return snap_give(s->dk, dst, bytes);
+            case 13: return snap_give(s->dc, dst, bytes);
+            default: return mf_set_error("mf_debug_count_copy: what = %d", what);
+        }
+    }
+    if (level < 1 || (size_t)level > s->levels.size()) return mf_set_error("mf_debug_count_copy: level %d of %zu K2 levels", level, s->levels.size());
+    const mf_count_snap_level &L = s->levels[(size_t)level - 1];
+    switch (what) {
+        case 0: return snap_give(L.buf, dst, bytes);
+        case 1: return snap_give(L.ostart, dst, bytes);
+        case 2: return snap_give(L.olen, dst, bytes);
+        default: return mf_set_error("mf_debug_count_copy: what = %d", what);
+    }
 }
