@@ -237,3 +237,121 @@ int kmf_histogram(mf_ctx *ctx, mf_buf<uint64_t> &tri, uint64_t m, std::map<uint6
     }
     return MF_OK;
 }
+
+// =============================================================================================
+// Test hooks (tests/test_join_slots_gpu.py, tests/test_join_crafted_gpu.py; NOT part of the C-ABI -- not in include/metafast_hip.h; DESIGN.md
+// section 7a, "The union table, as the tests pin it").  The union table slot by slot: the tests craft keys from the inverse of mf_hash64, so
+// they choose every key's home slot and slice.
+//   mf_debug_join_plan     plan_slices on `total` with the context's option stats_slices
+//   mf_debug_join_union    mf_join_union on the caller's tables with the slice count, slice and capacity given (a power of two >= 1 -- the
+//                          host never picks one below 2048) -> the cap raw 16-byte slots and n_union; an error of the pass is the production
+//                          message
+//   mf_debug_join_find     a slot table from the host; one thread per key: mf_join_mine<false>, then mf_join_find -> the slot,
+//                          MF_JOIN_NOT_FOUND, or MF_JOIN_NOT_MINE for a key >= 2^62 or of another slice
+//   mf_debug_join_read     a slot table from the host through mf_join_read with projection proj = 0 .. 4 in the order of mf_join.h
+//                          (nsamples, kps, color, ukm, uk; param: thresh of kps, thr of ukm) -> m (key, value) pairs, the values widened to
+//                          64 bits; keys_out and vals_out have room for nu.  nu below the number of occupied slots is refused before the
+//                          launch: the read-out's piece has nu entries, and the kernel writes one per kept slot.
+// =============================================================================================
+static constexpr uint64_t MF_JOIN_NOT_MINE = ~0ull - 1;
+static constexpr uint64_t MF_DEBUG_JOIN_MAX_CAP = 1ull << 24;
+
+__global__ __launch_bounds__(256) void k_join_probe(const mf_uslot *__restrict__ slots, uint64_t mask, const uint64_t *__restrict__ keys, uint64_t n,
+                                                    uint32_t S, uint32_t s, uint64_t *__restrict__ pos) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = keys[i];
+    const mf_join_key k = mf_join_mine<false>(key, S, s, nullptr);
+    ulonglong2 raw;
+    pos[i] = k.mine ? mf_join_find(slots, mask, k.h, key, &raw) : MF_JOIN_NOT_MINE;
+}
+
+static int debug_join_cap(const char *what, uint64_t cap) {
+    if (cap < 1 || (cap & (cap - 1)) || cap > MF_DEBUG_JOIN_MAX_CAP)
+        return mf_set_error("%s: cap = %llu is not a power of two in 1 .. 2^24", what, (unsigned long long)cap);
+    return MF_OK;
+}
+static int debug_join_upload(mf_ctx *ctx, const mf_uslot *slots, uint64_t cap, mf_buf<mf_uslot> &d) {
+    MF_TRY(d.alloc(ctx, cap));
+    MF_HIP(hipMemcpyAsync(d.p, slots, cap * sizeof(mf_uslot), hipMemcpyHostToDevice, ctx->stream));
+    return MF_OK;
+}
+
+extern "C" int mf_debug_join_plan(mf_ctx *ctx, uint64_t total, uint32_t *S, uint64_t *cap) {
+    if (!ctx || !S || !cap) return mf_set_error("mf_debug_join_plan: NULL argument");
+    MF_HIP(hipSetDevice(ctx->device));
+    return plan_slices(ctx, total, S, cap);
+}
+
+extern "C" int mf_debug_join_union(mf_ctx *ctx, mf_table *const *tables, int N, int b, int mode, const uint32_t *add, uint32_t S, uint32_t s,
+                                   uint64_t cap, mf_uslot *slots_out, uint64_t *n_union) {
+    if (!ctx || !tables || !add || !slots_out || !n_union) return mf_set_error("mf_debug_join_union: NULL argument");
+    if (N < 1) return mf_set_error("mf_debug_join_union: %d tables", N);
+    if (mode < MF_UNION_PRESENCE || mode > MF_UNION_COLOR) return mf_set_error("mf_debug_join_union: mode = %d (0 .. 3)", mode);
+    if (S < 1 || s >= S) return mf_set_error("mf_debug_join_union: slice %u of %u", s, S);
+    MF_TRY(debug_join_cap("mf_debug_join_union", cap));
+    MF_HIP(hipSetDevice(ctx->device));
+    MF_TRY(tables_total(ctx, tables, N, "mf_debug_join_union", nullptr));
+    mf_buf<mf_uslot> slots;
+    *n_union = 0;
+    MF_TRY(mf_join_union(ctx, mf_join_tables(tables), N, b, mode, add, S, s, cap, slots, n_union));
+    MF_HIP(hipMemcpyAsync(slots_out, slots.p, cap * sizeof(mf_uslot), hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    return MF_OK;
+}
+
+extern "C" int mf_debug_join_find(mf_ctx *ctx, const mf_uslot *slots, uint64_t cap, const uint64_t *keys, uint64_t n, uint32_t S, uint32_t s,
+                                  uint64_t *pos_out) {
+    if (!ctx || !slots || (n && (!keys || !pos_out))) return mf_set_error("mf_debug_join_find: NULL argument");
+    if (S < 1 || s >= S) return mf_set_error("mf_debug_join_find: slice %u of %u", s, S);
+    if (n > MF_JOIN_CURSOR_MAX) return mf_set_error("mf_debug_join_find: %llu keys", (unsigned long long)n);
+    MF_TRY(debug_join_cap("mf_debug_join_find", cap));
+    MF_HIP(hipSetDevice(ctx->device));
+    if (!n) return MF_OK;
+    mf_buf<mf_uslot> d; MF_TRY(debug_join_upload(ctx, slots, cap, d));
+    mf_buf<uint64_t> dk, dp; MF_TRY(dk.alloc(ctx, n)); MF_TRY(dp.alloc(ctx, n));
+    MF_HIP(hipMemcpyAsync(dk.p, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    k_join_probe<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d.p, cap - 1, dk.p, n, S, s, dp.p);
+    MF_HIP(hipMemcpyAsync(pos_out, dp.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    return MF_OK;
+}
+
+template <typename P>
+static int debug_join_read(mf_ctx *ctx, const mf_uslot *d_slots, uint64_t cap, uint64_t nu, const P &proj, uint64_t *keys_out, uint64_t *vals_out,
+                           uint64_t *m) {
+    mf_join_parts<uint64_t, typename P::value> parts;
+    MF_TRY(mf_join_read(ctx, d_slots, cap, nu, proj, parts));
+    const uint64_t n = parts.ns.back();
+    std::vector<typename P::value> v((size_t)n);
+    if (n) {
+        MF_HIP(hipMemcpyAsync(keys_out, parts.pk.back()->p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        MF_HIP(hipMemcpyAsync(v.data(), parts.pv.back()->p, n * sizeof(typename P::value), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    MF_HIP(hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < n; i++) vals_out[i] = (uint64_t)v[(size_t)i];
+    *m = n;
+    return MF_OK;
+}
+
+extern "C" int mf_debug_join_read(mf_ctx *ctx, const mf_uslot *slots, uint64_t cap, uint64_t nu, int proj, int param, uint64_t *keys_out,
+                                  uint64_t *vals_out, uint64_t *m) {
+    if (!ctx || !slots || !m || (nu && (!keys_out || !vals_out))) return mf_set_error("mf_debug_join_read: NULL argument");
+    if (proj < 0 || proj > 4) return mf_set_error("mf_debug_join_read: proj = %d (0 .. 4)", proj);
+    MF_TRY(debug_join_cap("mf_debug_join_read", cap));
+    uint64_t occupied = 0;
+    for (uint64_t i = 0; i < cap; i++) occupied += slots[i].key != MF_EMPTY;
+    if (nu < occupied)
+        return mf_set_error("mf_debug_join_read: nu = %llu, the table holds %llu entries: the read-out would write past its piece",
+                            (unsigned long long)nu, (unsigned long long)occupied);
+    MF_HIP(hipSetDevice(ctx->device));
+    *m = 0;
+    mf_buf<mf_uslot> d; MF_TRY(debug_join_upload(ctx, slots, cap, d));
+    switch (proj) {
+    case 0: return debug_join_read(ctx, d.p, cap, nu, mf_read_nsamples{}, keys_out, vals_out, m);
+    case 1: return debug_join_read(ctx, d.p, cap, nu, mf_read_kps{param}, keys_out, vals_out, m);
+    case 2: return debug_join_read(ctx, d.p, cap, nu, mf_read_color{}, keys_out, vals_out, m);
+    case 3: return debug_join_read(ctx, d.p, cap, nu, mf_read_ukm{param}, keys_out, vals_out, m);
+    default: return debug_join_read(ctx, d.p, cap, nu, mf_read_uk{}, keys_out, vals_out, m);
+    }
+}
