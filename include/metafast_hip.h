@@ -287,6 +287,31 @@ int  mf_kps_export_wide(const mf_kps *r, uint64_t *hi, uint64_t *lo, uint16_t *n
  * every ".kmers.bin" removed and "\t" + count per selected k-mer.  32 <= k <= 63; *n_kmers (may be NULL) = M. */
 int  mf_kmers_per_sample_wide(mf_ctx *ctx, const char *const *files, int n, int k, int percent, int count_first, const char *out_txt,
                               uint64_t *n_kmers);
+/* [mf_stats_kmers_tables] the same definition on (high, low) keys (mf_wstats.hip), samples numbered A first, then B: sample j holds
+ * x iff its count of x is > max_bad; counters[9] (MF_STATS_COUNTERS) as there; chi = the chi-squared survivors with value 1, group_a / group_b =
+ * the kept k-mers with the Java (short)(int) of their mean, all three ascending wide tables.  A group table's values are any 16 bits: 0 and
+ * values >= 0x8000 occur and are held as the uint16 they are (mf_wtable_export gives them as they are).  The union sorts and reduces per slice of
+ * the key range with weights (A = 1, B = 0: the weighted sum is n1A), the chi-squared and Mann-Whitney decisions are the host tables and the row
+ * kernels of the narrow tool; option "stats_slices" forces the number of slices and the result is the same for every number.  Errors, each named
+ * and none a write out of bounds: na < 1 or nb < 1, na + nb > 1024, p_chi2 outside [0, 1], max_bad < 0; a NULL table, a table of another
+ * context, tables of different k, k outside 32 ... 63; a sample or a slice of 2^31 or more entries, a slice that overflows its buffer, a
+ * slice's matrix of survivors x samples x 2 bytes that does not fit the free device memory (each: raise stats_slices).  Tables in any order
+ * (fresh from the count, in several pieces, or loaded) are taken as they are. */
+int  mf_stats_kmers_wide_tables(mf_ctx *ctx, mf_wtable *const *a, int na, mf_wtable *const *b, int nb, int max_bad, double p_chi2, double p_mw,
+                                mf_wtable **chi, mf_wtable **group_a, mf_wtable **group_b, uint64_t *counters);
+/* [mf_stats_kmers] the file form on wide .kmers.bin files: every load is mf_wtable_load_kmers(file, 1, 0, k) (the loader checks every record:
+ * a file lists no k-mer twice), one sample resident at a time, each file read twice per slice -> <out_dir>/filtered_chisquared.kmers.bin +
+ * .stat.txt, filtered_groupA.kmers.bin, filtered_groupB.kmers.bin, wide records, ascending.  The group files are written at threshold -1,
+ * every record as in the narrow tool: such a file may hold records with a value <= 0, which mf_wtable_load_kmers refuses by design (`view
+ * --wide-kmers` reads them on the host).  32 <= k <= 63; counters may be NULL. */
+int  mf_stats_kmers_wide(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, int max_bad, int k, double p_chi2,
+                         double p_mw, const char *out_dir, uint64_t *counters);
+/* [mf_kmers_samples_count_tables / mf_kmers_samples_count] n(x) = the samples that hold x with count > max_bad, for every x with n(x) > 0, as an
+ * ascending wide table: the union's sample count with no further pass.  At most 32767 samples.  Library calls only: the command-line tool
+ * kmers-samples-counter stays at k <= 31. */
+int  mf_kmers_samples_count_wide_tables(mf_ctx *ctx, mf_wtable *const *t, int n, int max_bad, mf_wtable **out);
+int  mf_kmers_samples_count_wide(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
+                                 uint64_t *n_kmers);
 /* [mf_comps_write / mf_comps_load] on load the members must be < 4^k and ascending inside a component */
 int  mf_wcomps_write(const mf_wcomps *c, const char *components_bin, const char *stat_txt);
 int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **out);

@@ -99,6 +99,7 @@ extern "C" int mf_unique_kmers_multi_wide(mf_ctx *, const char *const *, int, co
     __attribute__((weak));
 extern "C" int mf_wtable_write_kmers_filtered(mf_wtable *, int, mf_wtable *, int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_per_sample_wide(mf_ctx *, const char *const *, int, int, int, int, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_stats_kmers_wide(mf_ctx *, const char *const *, int, const char *const *, int, int, int, double, double, const char *, uint64_t *) __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -1272,19 +1273,25 @@ static void log_stats_counters(const uint64_t *c, int n) {
 }
 static vector<PV> tool_stats_kmers(Run &r) {
     // StatsKmersFinder.java:89-297, StatsKmers3GroupsFinder.java:92-343
+    // (--wide-kmers and -k in 32 ... 63, two groups only: the same on wide .kmers.bin files, mf_stats_kmers_wide.  The tool declares no -k: the
+    // option is accepted like any other it does not declare, and without the flag, without -k or with k <= 31 nothing changes)
     const int n = !strcmp(r.t.name, "stats-kmers-3") ? 3 : 2;
+    const bool wide = n == 2 && wide_host_k(r.k);
     const Groups g = groups_of(r, n);
     const int b = r.num("maximal-bad-frequence");
     const string out_dir = r.str("output-dir");
     if (n == 3) check_groups(r, g, n);
     mkdirs(out_dir);
-    if (n == 3) r.entry(mf_stats_kmers3 != nullptr, "mf_stats_kmers3"); else r.entry(mf_stats_kmers != nullptr, "mf_stats_kmers");
+    if (n == 3) r.entry(mf_stats_kmers3 != nullptr, "mf_stats_kmers3");
+    else if (wide) r.entry(mf_stats_kmers_wide != nullptr, "mf_stats_kmers_wide");
+    else r.entry(mf_stats_kmers != nullptr, "mf_stats_kmers");
     mf_ctx *ctx = r.ctx();
     logmsg("INFO", "Loading k-mers occurrences...");
     auto pa = cptrs(g.files[0]), pb = cptrs(g.files[1]), pc = cptrs(g.files[2]);
     uint64_t c[MF_STATS3_COUNTERS] = {0};
     static_assert(MF_STATS_COUNTERS <= MF_STATS3_COUNTERS, "one array for both");
     if (n == 3) check(mf_stats_kmers3(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), pc.data(), (int)pc.size(), b, g.pchi2, g.pmw, out_dir.c_str(), c));
+    else if (wide) check(mf_stats_kmers_wide(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), b, r.k, g.pchi2, g.pmw, out_dir.c_str(), c));
     else check(mf_stats_kmers(ctx, pa.data(), (int)pa.size(), pb.data(), (int)pb.size(), b, g.pchi2, g.pmw, out_dir.c_str(), c));
     logmsg("INFO", "Survived after chi-squared test k-mers printed to: %s", (out_dir + "/filtered_chisquared.kmers.bin").c_str());
     log_group_files(out_dir, n);
@@ -1961,8 +1968,15 @@ int main(int argc, char **argv) {
     }
     // --wide-kmers goes to in.properties like a parameter where it is in effect (k > 31), so that -c and -s continue a wide workDir
     g_wide = a.flag("wide-kmers");
-    const bool wide_run = g_wide && t->param("k") && a.geti("k", 0) > 31;
-    auto inputs = [&]() { vector<PV> v = tool_inputs(*t, a, wd, e.start_ts); if (wide_run) v.push_back(PV::flag("wide-kmers", true)); return v; };
+    // (stats-kmers declares no k and takes one with the flag: its wide run records k as well)
+    const bool takes_k = !strcmp(t->name, "stats-kmers");
+    const bool wide_run = g_wide && (t->param("k") || takes_k) && a.geti("k", 0) > 31;
+    auto inputs = [&]() {
+        vector<PV> v = tool_inputs(*t, a, wd, e.start_ts);
+        if (wide_run && takes_k) v.push_back(PV("k", a.get("k")));
+        if (wide_run) v.push_back(PV::flag("wide-kmers", true));
+        return v;
+    };
     Run r{e, a, *t, wd, a.get("start"), a.get("finish"), force, 0};
     if (!force && r.start.empty() && can) {
         logmsg("INFO", "SUCCESS file found for tool %s - loading results...", tool.c_str());

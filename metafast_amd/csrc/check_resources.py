@@ -7,12 +7,12 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_|k_wf_|k_w_features|k_wj_|k_wkps_")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_|k_wf_|k_w_features|k_wj_|k_wkps_|k_wstats_")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
 # column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip, mf_wcomp2graph.hip; one thread per run of positions, per
 # run, per record, or one wave per record: mf_comppaths.hip; one thread per entry or per run of equal k-mers: mf_wjoin.hip; one thread per entry or
-# column: mf_wkps.hip)
-NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_|k_cp_|k_wj_|k_wkps_")
+# column: mf_wkps.hip; one thread per k-mer of a slice's union, per entry of a sample or per row: mf_wstats.hip)
+NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_|k_cp_|k_wj_|k_wkps_|k_wstats_")
 # the translation units that hold those kernels: the guard must SEE them there (a renamed kernel, or a remark format that changed,
 # is a failed check, not a passed one)
 EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"], "mf_comp2seq": ["k_c2s_flags"],
@@ -42,7 +42,10 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
           # (the wide join, mf_wjoin.hip: a thread per entry, per run of equal k-mers or per filter entry, nothing shared)
           "mf_wjoin": ["k_wj_gather", "k_wj_reduce", "k_wj_knock", "k_wj_mark", "k_wj_flag", "k_wj_pick", "k_wj_keep"],
           # (the wide kmers-per-sample, mf_wkps.hip: a thread per entry of a sample (15 VGPRs) or per column (36), nothing shared)
-          "mf_wkps": ["k_wkps_gather", "k_wkps_header"]}
+          "mf_wkps": ["k_wkps_gather", "k_wkps_header"],
+          # (the wide stats-kmers, mf_wstats.hip: a thread per k-mer of the union, per entry of a sample or per row number, nothing shared; the row
+          # kernels it launches are mf_stats.hip's)
+          "mf_wstats": ["k_wstats_select", "k_wstats_gather", "k_wstats_iota", "k_wstats_keys"]}
 
 
 def main():

@@ -27,3 +27,17 @@ double chi2_1_quantile(double p_chi2);
 // the smallest 2 * Umin in [0, nA nB] whose p is not < pmw (or_equal: whose p is > pmw); nA nB + 1: every row passes
 uint32_t mw_threshold(int na, int nb, double pmw, bool or_equal = false);
 int mf_stats_check_p(double pchi2);
+// 1 <= |A|, 1 <= |B|, |A| + |B| <= MF_STATS_MAX_N
+int mf_stats_check_groups(int na, int nb);
+
+// a launch of the two-group row kernels (k_stats_rows_thread / k_stats_rows_wave, mf_stats.hip: compiled there, without contraction)
+struct mf_stats_row_args {
+    const uint16_t *mat; const uint64_t *rkeys; uint64_t m;
+    int na, nb;
+    const double *F; double M;
+    int mw; uint32_t T;                                  // mw != 0: keep iff 2 * Umin < T
+    uint64_t *ka, *kb; uint16_t *va, *vb;                 // group A / B outputs: a kept row's rkeys word and its value
+    unsigned int *cur;                                    // [0] A, [1] B
+    unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] unique left
+};
+void mf_stats_rows_launch(mf_ctx *ctx, const mf_stats_row_args &ra);

@@ -110,15 +110,6 @@ __global__ __launch_bounds__(256) void k_stats_gather(const mf_uslot *__restrict
     }
 }
 
-struct mf_stats_row_args {
-    const uint16_t *mat; const uint64_t *rkeys; uint64_t m;
-    int na, nb;
-    const double *F; double M;
-    int mw; uint32_t T;                                  // mw != 0: keep iff 2 * Umin < T
-    uint64_t *ka, *kb; uint16_t *va, *vb;                 // group A / B outputs
-    unsigned int *cur;                                    // [0] A, [1] B
-    unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] unique left
-};
 // decision + output of one row: group 0 (A) / 1 (B) / -1 (rejected by the Mann-Whitney test) and the value
 __device__ __forceinline__ int mf_stats_group(bool pass, double meanA, double meanB, uint16_t *val) {
     if (!pass) return -1;
@@ -544,6 +535,22 @@ uint32_t mw_threshold(int na, int nb, double pmw, bool or_equal) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // host: the join
 // ---------------------------------------------------------------------------------------------------------------------------
+// the two-group row kernels over a.m rows (nothing is queued for none): one thread per row up to MF_STATS_THREAD_N samples, one wave per row
+// above.  The launcher of stats_join (below) and of the wide tool (mf_wstats.hip), which hands in row numbers as rkeys.
+void mf_stats_rows_launch(mf_ctx *ctx, const mf_stats_row_args &ra) {
+    if (!ra.m) return;
+    const int N = ra.na + ra.nb;
+    if (N <= MF_STATS_THREAD_N) {
+        const unsigned g_thread = (unsigned)std::min<uint64_t>((ra.m + 255) / 256, (uint64_t)ctx->n_cu * 8);
+        mf_ktimer tm(ctx, "k_stats_rows_thread");
+        k_stats_rows_thread<<<g_thread, 256, (size_t)N * 256 * sizeof(double), ctx->stream>>>(ra);
+    } else {
+        const unsigned g_wave = (unsigned)std::min<uint64_t>((ra.m + 3) / 4, (uint64_t)ctx->n_cu * 16);
+        mf_ktimer tm(ctx, "k_stats_rows_wave");
+        k_stats_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
+    }
+}
+
 // sample j for the gather pass: its entries at threshold 0, and F_j = the sum of its counts
 using stats_get_counts = std::function<int(int j, mf_join_sample &, uint64_t *F)>;
 
@@ -634,14 +641,7 @@ static int stats_join(mf_ctx *ctx, const mf_join_get &get, const stats_get_count
             const unsigned g_wave = (unsigned)std::min<uint64_t>((m + 3) / 4, (uint64_t)ctx->n_cu * 16);
             const size_t lds = (size_t)N * 256 * sizeof(double);
             if (G == 2) {
-                mf_stats_row_args ra{mat.p, rkeys, m, na, nb, dF.p, M, mw, T, kg[0], kg[1], vg[0], vg[1], cur, ctr.p};
-                if (N <= MF_STATS_THREAD_N) {
-                    mf_ktimer tm(ctx, "k_stats_rows_thread");
-                    k_stats_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
-                } else {
-                    mf_ktimer tm(ctx, "k_stats_rows_wave");
-                    k_stats_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
-                }
+                mf_stats_rows_launch(ctx, mf_stats_row_args{mat.p, rkeys, m, na, nb, dF.p, M, mw, T, kg[0], kg[1], vg[0], vg[1], cur, ctr.p});
             } else {
                 mf_stats3_row_args ra{mat.p, rkeys, m, na, nb, nc, dF.p, M, mw, T, Tbc, Tac, kg[0], kg[1], kg[2], vg[0], vg[1], vg[2], cur, ctr.p};
                 if (specific && N <= MF_STATS_THREAD_N) {
@@ -698,7 +698,7 @@ static int nsamples_join(mf_ctx *ctx, const mf_join_get &get, int N, uint64_t to
     return pairs_to_table(ctx, keys, vals, n, out);
 }
 
-static int check_groups(int na, int nb) {
+int mf_stats_check_groups(int na, int nb) {
     if (na < 1 || nb < 1) return mf_set_error("stats-kmers: both groups need at least one sample (|A| = %d, |B| = %d)", na, nb);
     if (na + nb > MF_STATS_MAX_N)
         return mf_set_error("stats-kmers: %d samples, this build supports at most %d (|A| + |B|)", na + nb, MF_STATS_MAX_N);
@@ -724,7 +724,7 @@ extern "C" int mf_stats_kmers_tables(mf_ctx *ctx, mf_table *const *a, int na, mf
     mf_range rng_("mf:stats_kmers");
     if (!ctx || !chi || !group_a || !group_b || !counters || (na && !a) || (nb && !b)) return mf_set_error("mf_stats_kmers_tables: NULL argument");
     *chi = *group_a = *group_b = nullptr;
-    MF_TRY(check_groups(na, nb));
+    MF_TRY(mf_stats_check_groups(na, nb));
     MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t total = 0;
@@ -750,7 +750,7 @@ extern "C" int mf_stats_kmers(mf_ctx *ctx, const char *const *a_files, int na, c
                               double p_mw, const char *out_dir, uint64_t *counters) {
     mf_range rng_("mf:stats_kmers(files)");
     if (!ctx || !out_dir || (na && !a_files) || (nb && !b_files)) return mf_set_error("mf_stats_kmers: NULL argument");
-    MF_TRY(check_groups(na, nb));
+    MF_TRY(mf_stats_check_groups(na, nb));
     MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t ta = 0, tb = 0;

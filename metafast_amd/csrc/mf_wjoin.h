@@ -32,6 +32,8 @@ int mf_wjoin_knock(mf_ctx *ctx, const mf_wtable *t, int b, mf_wjoin_union &u);
 // the entries with sel > thr of (hi, lo, val, sel)[n], order kept -> (ohi, olo, oval[, osel])[*m]; osel may be NULL
 int mf_wjoin_select(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint16_t *val, const uint16_t *sel, uint64_t n, int thr, mf_buf<uint64_t> &ohi,
                     mf_buf<uint64_t> &olo, mf_buf<uint16_t> &oval, mf_buf<uint16_t> *osel, uint64_t *m);
+// (hi, lo, cnt)[n] ascending, every count > cut -> a one-piece table; the arrays move into it
+int mf_wjoin_table(mf_ctx *ctx, int k, int cut, mf_buf<uint64_t> &hi, mf_buf<uint64_t> &lo, mf_buf<uint16_t> &cnt, uint64_t n, mf_wtable **out);
 // the k of a list of tables, every one checked: NULL, another context, another k.  *k = 0: no table so far; total may be NULL
 int mf_wjoin_tables_check(mf_ctx *ctx, mf_wtable *const *t, int n, const char *what, int *k, uint64_t *total);
 // the records (18 bytes each) of a list of wide .kmers.bin files, by their sizes

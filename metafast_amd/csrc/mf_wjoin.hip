@@ -207,7 +207,7 @@ static int wukm_check(int n_in, int max_bad, int min_samples, int max_samples) {
     if (min_samples > max_samples) return mf_set_error("--min-samples parameter cannot be greater than --max-samples parameter.");
     return MF_OK;
 }
-static int wj_table(mf_ctx *ctx, int k, int cut, mf_buf<uint64_t> &hi, mf_buf<uint64_t> &lo, mf_buf<uint16_t> &cnt, uint64_t n, mf_wtable **out) {
+int mf_wjoin_table(mf_ctx *ctx, int k, int cut, mf_buf<uint64_t> &hi, mf_buf<uint64_t> &lo, mf_buf<uint16_t> &cnt, uint64_t n, mf_wtable **out) {
     auto t = std::make_unique<mf_wtable>();
     t->ctx = ctx; t->k = k; t->n = n; t->n_all = n; t->n_occ = 0; t->cut_thr = cut; t->ascending = true;
     if (n) {
@@ -274,7 +274,7 @@ static int wukm_join(mf_ctx *ctx, int k, const mf_wjoin_get &get_in, int n_in, c
         // (no key is held by more than n_in samples, and every survivor by at least one)
         if (i <= n_in) MF_TRY(mf_wjoin_select(ctx, all.hi.p, all.lo.p, all.sum.p, all.sel.p, n, (int)std::max<int64_t>(i - 1, 0), ohi, olo, ov, nullptr, &m));
         mf_wtable *t = nullptr;
-        MF_TRY(wj_table(ctx, k, b, ohi, olo, ov, m, &t));
+        MF_TRY(mf_wjoin_table(ctx, k, b, ohi, olo, ov, m, &t));
         outs.push_back(t);
         counts.push_back(m);
         if (!m) break;

@@ -58,6 +58,10 @@ _SIGS = {
     "mf_unique_kmers_multi_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, i32, i32, cp, C.POINTER(C.c_int), pu64, vp]),
     "mf_kmers_per_sample_wide_tables": (i32, [vp, vp, i32, i32, i32, i32, pvp]),
     "mf_kmers_per_sample_wide": (i32, [vp, C.POINTER(cp), i32, i32, i32, i32, cp, pu64]),
+    "mf_stats_kmers_wide_tables": (i32, [vp, vp, i32, vp, i32, i32, C.c_double, C.c_double, pvp, pvp, pvp, vp]),
+    "mf_stats_kmers_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, C.c_double, C.c_double, cp, vp]),
+    "mf_kmers_samples_count_wide_tables": (i32, [vp, vp, i32, i32, pvp]),
+    "mf_kmers_samples_count_wide": (i32, [vp, C.POINTER(cp), i32, i32, i32, cp, cp, pu64]),
     "mf_kps_device_view_wide": (i32, [vp, pvp, pvp, pvp, pvp]),
     "mf_kps_export_wide": (i32, [vp, vp, vp, vp, vp]),
     "mf_wcomps_write": (i32, [vp, cp, cp]),
@@ -753,6 +757,37 @@ class Context:
     def kmers_samples_count_files(self, files, k, kmers_bin, stat_txt=None, max_bad=1):
         n = C.c_uint64()
         _check(lib().mf_kmers_samples_count(self.h, _cfiles(files), len(files), max_bad, k, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
+        return n.value
+
+    def stats_kmers_wide(self, a_tables, b_tables, p_chi2=0.05, p_mw=0.05, max_bad=0):
+        """NO-REFERENCE EXTENSION: stats_kmers on WideTables (32 <= k <= 63) -> (chi-squared survivors, group A, group B, dict of the
+        nine counters), the three as WideTables; a group table's values are Java shorts held as uint16 (0 and >= 0x8000 occur)"""
+        ha = (C.c_void_p * max(len(a_tables), 1))(*[t.h if t is not None else None for t in a_tables])
+        hb = (C.c_void_p * max(len(b_tables), 1))(*[t.h if t is not None else None for t in b_tables])
+        chi, ga, gb = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(len(STATS_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_stats_kmers_wide_tables(self.h, ha, len(a_tables), hb, len(b_tables), max_bad, p_chi2, p_mw, C.byref(chi), C.byref(ga),
+                                                C.byref(gb), ctr.ctypes.data))
+        return WideTable(self, chi), WideTable(self, ga), WideTable(self, gb), dict(zip(STATS_COUNTERS, map(int, ctr)))
+
+    def stats_kmers_wide_files(self, a_files, b_files, k, out_dir, p_chi2=0.05, p_mw=0.05, max_bad=0):
+        """the same from wide .kmers.bin files -> out_dir/filtered_{chisquared,groupA,groupB}.kmers.bin (wide records; a group file may
+        hold values <= 0, which load_kmers_wide refuses); returns the counters"""
+        ctr = np.zeros(len(STATS_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_stats_kmers_wide(self.h, _cfiles(a_files), len(a_files), _cfiles(b_files), len(b_files), max_bad, k, p_chi2, p_mw,
+                                         os.fsencode(out_dir), ctr.ctypes.data))
+        return dict(zip(STATS_COUNTERS, map(int, ctr)))
+
+    def kmers_samples_count_wide(self, tables, max_bad=1):
+        """NO-REFERENCE EXTENSION: kmers_samples_count on WideTables -> WideTable of (k-mer, number of samples with count > max_bad)"""
+        h = (C.c_void_p * max(len(tables), 1))(*[t.h if t is not None else None for t in tables])
+        t = C.c_void_p()
+        _check(lib().mf_kmers_samples_count_wide_tables(self.h, h, len(tables), max_bad, C.byref(t)))
+        return WideTable(self, t)
+
+    def kmers_samples_count_wide_files(self, files, k, kmers_bin, stat_txt=None, max_bad=1):
+        n = C.c_uint64()
+        _check(lib().mf_kmers_samples_count_wide(self.h, _cfiles(files), len(files), max_bad, k, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
         return n.value
 
     def stats_kmers3(self, a_tables, b_tables, c_tables, p_chi2=0.05, p_mw=0.05, max_bad=0):
