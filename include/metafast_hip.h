@@ -913,6 +913,52 @@ int  mf_colored_components_device(mf_ctx *ctx, const mf_ctable *t, int k, int n_
 int  mf_colored_components(mf_ctx *ctx, const char *const *files, int nfiles, int k, int64_t min_value, int n_groups, int separate,
                            double perc, const char *out_dir, const char *stat_txt, uint64_t *counts);
 
+/* ---- NO-REFERENCE EXTENSION: pipeline 4 for 32 <= k <= 63 (mf_wcolor.hip, mf_wgraph.hip) ------------------------------
+ * mf_wctable: 2k-bit k-mer (high word, low word) -> 64-bit value, ascending, resident in HBM.  Its file is the wide colored_kmers.kmers.bin:
+ * headerless, 24-byte big-endian records -- int64 high word, int64 low word, int64 value.  The calls mirror mf_ctable_*; a call of either
+ * family refuses a handle of the other by name (both handles begin with their context and k, and k tells them apart; the build asserts that
+ * layout).  The two destroy calls return nothing and cannot refuse: given a handle of the other family, mf_ctable_destroy and
+ * mf_wctable_destroy touch nothing of it and return -- the handle stays valid and is still to be released by its own family's call. */
+typedef struct mf_wctable mf_wctable;
+/* [mf_ctable_from_host] host triples in any order; the values of a k-mer that comes more than once are added, saturating at 2^63 - 1; a value
+ * with the sign bit set and a k-mer that does not fit 2k bits are errors.  32 <= k <= 63 */
+int  mf_wctable_from_host(mf_ctx *ctx, const uint64_t *hi, const uint64_t *lo, const uint64_t *values, uint64_t n, int k, mf_wctable **out);
+/* [mf_ctable_load] files of 24-byte records, parsed and merged on the host; a record is kept iff its value is > min_value (signed: one with
+ * the sign bit set never is); the kept values of a k-mer are added, saturating at 2^63 - 1.  A file whose size is no multiple of 24 is an
+ * error that names the file and the record size, a k-mer that does not fit 2k bits one that names the file. */
+int  mf_wctable_load(mf_ctx *ctx, const char *const *files, int nfiles, int64_t min_value, int k, mf_wctable **out);
+int  mf_wctable_stats(const mf_wctable *t, uint64_t *n, int *k);
+/* hi[n], lo[n], values[n] in ascending order of the k-mer; cap = 0: *n only */
+int  mf_wctable_export(const mf_wctable *t, uint64_t *hi, uint64_t *lo, uint64_t *values, uint64_t cap, uint64_t *n);
+/* [mf_ctable_write] the 24-byte records with value > 0 in ascending order and the .stat.txt over the distinct values in the narrow writer's
+ * format (may be NULL); *n_written may be NULL */
+int  mf_wctable_write(const mf_wctable *t, const char *kmers_bin, const char *stat_txt, uint64_t *n_written);
+void mf_wctable_destroy(mf_wctable *t);
+/* [mf_kmers_color_tables] the same definition on (high, low) keys: every sample whose count of x is > max_bad adds 1 (count_values != 0: its
+ * count) to the 20-bit field of its class in x's packed value, each add clamped at 2^20 - 1; no limit on the key.  Per slice of the key range
+ * (option "stats_slices" forces the number; the result is the same for every number) the wide join's union lists the slice's distinct k-mers,
+ * then every sample is read a second time and each entry adds into its k-mer's row, found by binary search, with a 64-bit compare-and-swap.
+ * Errors, decided on the host before any launch: a class outside 0 ... 2, more than 1024 samples, max_bad < 0, a NULL table, a table of
+ * another context, tables of different k, k outside 32 ... 63; from the join core, with the tool's name in front: a sample or a slice of 2^31
+ * or more entries, a slice that overflows its buffer (raise stats_slices).  Tables in any order and in several pieces are taken as they are. */
+int  mf_kmers_color_wide_tables(mf_ctx *ctx, mf_wtable *const *t, const int *classes, int n, int max_bad, int count_values, mf_wctable **out);
+/* [mf_kmers_color] the file form on wide .kmers.bin files: every load is mf_wtable_load_kmers(file, 1, 0, k), one sample resident at a time,
+ * each file read twice per slice -> kmers_bin (24-byte records) + stat_txt (may be NULL).  32 <= k <= 63; *n_kmers (may be NULL) = the
+ * records written. */
+int  mf_kmers_color_wide(mf_ctx *ctx, const char *const *files, const int *classes, int n, int max_bad, int count_values, int k,
+                         const char *kmers_bin, const char *stat_txt, uint64_t *n_kmers);
+/* [mf_colored_components_device] on an mf_wctable: the values are classified by the narrow tool's kernel, the k-mers become a one-piece
+ * ascending wide table whose counts are the colour codes, the adjacency is the wide cutter's (mf_cut_components_wide_device) and the
+ * per-colour passes are the narrow tool's on vertex ids.  out[n_groups]: one mf_wcomps per colour (size = weight = k-mers; size descending,
+ * then smallest k-mer; members ascending); colours above 2 give empty components; counts[n_groups] may be NULL.  k must be the table's.
+ * A k-mer whose colour is >= n_groups is an error that prints the k-mer as its k bases.  Fewer than 2^32 - 1 k-mers; n_groups 1 ... 64. */
+int  mf_colored_components_wide_device(mf_ctx *ctx, const mf_wctable *t, int k, int n_groups, int separate, double perc, mf_wcomps **out,
+                                       uint64_t *counts);
+/* [mf_colored_components] the file form: mf_wctable_load(files, min_value) -> <out_dir>/components_color_<c>.bin for c < n_groups, each an
+ * ordinary wide components.bin (mf_wcomps_write), and stat_txt (may be NULL), the narrow tool's four columns.  On an error nothing is written. */
+int  mf_colored_components_wide(mf_ctx *ctx, const char *const *files, int nfiles, int k, int64_t min_value, int n_groups, int separate,
+                                double perc, const char *out_dir, const char *stat_txt, uint64_t *counts);
+
 /* ---- A13  Bray-Curtis ---------------------------------------------------------------- */
 /* replaces DistanceMatrixCalculatorMain.brayCurtisDistance (src/tools/DistanceMatrixCalculatorMain.java:
  * 140-152): d = sum|a-b| / sum(|a|+|b|) on raw vectors; vecs is row-major [n_samples][n_comp]. */

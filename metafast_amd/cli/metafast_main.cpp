@@ -100,6 +100,9 @@ extern "C" int mf_unique_kmers_multi_wide(mf_ctx *, const char *const *, int, co
 extern "C" int mf_wtable_write_kmers_filtered(mf_wtable *, int, mf_wtable *, int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_per_sample_wide(mf_ctx *, const char *const *, int, int, int, int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_stats_kmers_wide(mf_ctx *, const char *const *, int, const char *const *, int, int, int, double, double, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_color_wide(mf_ctx *, const char *const *, const int *, int, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_colored_components_wide(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
+    __attribute__((weak));
 
 using std::string;
 using std::vector;
@@ -1479,8 +1482,10 @@ static vector<PV> tool_kmers_multiple_filters(Run &r) {
 }
 static vector<PV> tool_kmers_color(Run &r) {
     // ColorKmersMain.java:89-136: per k-mer and class 0 / 1 / 2 the number of samples that hold it (-val: their summed coverage)
+    // (--wide-kmers and k > 31: the same on wide .kmers.bin files into 24-byte records, mf_kmers_color_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const int b = r.num("maximal-bad-frequency");
     const bool val = r.a.flag("val");
     const string out_dir = r.str("output-dir"), cls = r.str("class");
@@ -1516,20 +1521,22 @@ static vector<PV> tool_kmers_color(Run &r) {
     }
     if (files.size() > 1024) die("kmers-color: %zu k-mers files, at most 1024 (a field of the packed value holds 20 bits)", files.size());
     mkdirs(out_dir);
-    r.entry(mf_kmers_color != nullptr, "mf_kmers_color");
+    if (wide) r.entry(mf_kmers_color_wide != nullptr, "mf_kmers_color_wide"); else r.entry(mf_kmers_color != nullptr, "mf_kmers_color");
     mf_ctx *ctx = r.ctx();
     logmsg("INFO", "Loading kmers files...");
     auto fp = cptrs(files);
     const string out = out_dir + "/colored_kmers.kmers.bin", st = out_dir + "/colored_kmers.stat.txt";
     uint64_t c = 0;
-    check(mf_kmers_color(ctx, fp.data(), classes.data(), (int)fp.size(), b, val ? 1 : 0, k, out.c_str(), st.c_str(), &c));
+    check((wide ? mf_kmers_color_wide : mf_kmers_color)(ctx, fp.data(), classes.data(), (int)fp.size(), b, val ? 1 : 0, k, out.c_str(), st.c_str(), &c));
     logmsg("INFO", "%s colored k-mers printed to %s", group_digits(c).c_str(), out.c_str());
     return {PV::file("resulting-kmers-file", out)};
 }
 static vector<PV> tool_component_colored(Run &r) {
     // ColoredComponentMain.java:83-119, default and --separate modes of ColoredComponentsBuilder
+    // (--wide-kmers and k > 31: the same on a wide colored_kmers.kmers.bin into wide components_color_<c>.bin, mf_colored_components_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const int groups = r.num("n_groups"), ncomps = r.num("n_comps");
     const bool separate = r.a.flag("separate");
     const double perc = r.real("perc");
@@ -1541,14 +1548,14 @@ static vector<PV> tool_component_colored(Run &r) {
     const string out_dir = r.str("output-dir"), stat = r.wd + "/components-stat.txt";
     const vector<string> files = r.a.list("k-mers");
     mkdirs(out_dir);
-    r.entry(mf_colored_components != nullptr, "mf_colored_components");
+    if (wide) r.entry(mf_colored_components_wide != nullptr, "mf_colored_components_wide"); else r.entry(mf_colored_components != nullptr, "mf_colored_components");
     mf_ctx *ctx = r.ctx();
     logmsg("DEBUG", "Loading colored k-mers...");
     logmsg("INFO", "Searching for colored components...");
     auto fp = cptrs(files);
     vector<uint64_t> cnt((size_t)groups, 0);
     // (IOUtils.loadLongKmers(files, k, ...): the reference passes k where the loader takes its value threshold)
-    check(mf_colored_components(ctx, fp.data(), (int)fp.size(), k, (int64_t)k, groups, separate ? 1 : 0, perc, out_dir.c_str(), stat.c_str(), cnt.data()));
+    check((wide ? mf_colored_components_wide : mf_colored_components)(ctx, fp.data(), (int)fp.size(), k, (int64_t)k, groups, separate ? 1 : 0, perc, out_dir.c_str(), stat.c_str(), cnt.data()));
     uint64_t total = 0;
     vector<string> written;
     for (int c = 0; c < groups; c++) {

@@ -7,12 +7,13 @@ import os
 import re
 import sys
 
-NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_|k_wf_|k_w_features|k_wj_|k_wkps_|k_wstats_")
+NO_SCRATCH = re.compile(r"k_ut_flags_part|k_cc_adjacency_part|k_dcc_adjacency_part|k_c2s_flags|k_kps_|k_c2g_|k_s2c_|k_ws2c_|k_cp_|k_specific|k_uk_|k_wf_|k_w_features|k_wj_|k_wkps_|k_wstats_|k_wcolor_")
 # ... and the ones that are to run without LDS as well (one thread per row, nothing shared: mf_comp2seq.hip; one thread per key, entry,
 # column or value: mf_kps.hip; one thread per node, segment, segment end, link or row: mf_comp2graph.hip, mf_wcomp2graph.hip; one thread per run of positions, per
 # run, per record, or one wave per record: mf_comppaths.hip; one thread per entry or per run of equal k-mers: mf_wjoin.hip; one thread per entry or
-# column: mf_wkps.hip; one thread per k-mer of a slice's union, per entry of a sample or per row: mf_wstats.hip)
-NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_|k_cp_|k_wj_|k_wkps_|k_wstats_")
+# column: mf_wkps.hip; one thread per k-mer of a slice's union, per entry of a sample or per row: mf_wstats.hip; one thread per entry of a sample:
+# mf_wcolor.hip)
+NO_LDS = re.compile(r"k_c2s_flags|k_kps_|k_c2g_|k_cp_|k_wj_|k_wkps_|k_wstats_|k_wcolor_")
 # the translation units that hold those kernels: the guard must SEE them there (a renamed kernel, or a remark format that changed,
 # is a failed check, not a passed one)
 EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_dcc_adjacency_part"], "mf_comp2seq": ["k_c2s_flags"],
@@ -45,7 +46,9 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
           "mf_wkps": ["k_wkps_gather", "k_wkps_header"],
           # (the wide stats-kmers, mf_wstats.hip: a thread per k-mer of the union, per entry of a sample or per row number, nothing shared; the row
           # kernels it launches are mf_stats.hip's)
-          "mf_wstats": ["k_wstats_select", "k_wstats_gather", "k_wstats_iota", "k_wstats_keys"]}
+          "mf_wstats": ["k_wstats_select", "k_wstats_gather", "k_wstats_iota", "k_wstats_keys"],
+          # (the wide kmers-color, mf_wcolor.hip: a thread per entry of a sample -- a binary search and a 64-bit compare-and-swap, nothing shared)
+          "mf_wcolor": ["k_wcolor_add"]}
 
 
 def main():

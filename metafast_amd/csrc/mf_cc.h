@@ -18,3 +18,10 @@ struct mf_cc_level {
 // level is appended (the only extra work: the edge counters of a dense level are read back).
 int mf_cc_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_counts, const uint64_t *d_keys, int b1, int b2,
                 const std::function<int(uint32_t *)> &adjacency, mf_comps **out, std::vector<mf_cc_level> *trace = nullptr);
+// component-colored in the same shape: d_code[n] = a vertex's colour code (1 + colour, 4 = neutral), adjacency and d_keys as
+// above; out[n_groups], one mf_comps per colour (size = weight = k-mers; size descending, then the smallest k-mer / vertex id)
+int mf_cc_colored_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_code, const uint64_t *d_keys, int n_groups, int separate,
+                        const std::function<int(uint32_t *)> &adjacency, mf_comps **out);
+// packed values d_vals[n] -> d_code[n] (ColoredKmerOperations.getColor; k_color_classify); *d_first = the smallest position whose colour is not
+// below n_groups, ~0: none.  Queued on the context's stream
+int mf_color_classify_launch(mf_ctx *ctx, const uint64_t *d_vals, uint64_t n, double perc, int n_groups, uint16_t *d_code, unsigned long long *d_first);

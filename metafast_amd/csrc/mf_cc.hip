@@ -1813,6 +1813,14 @@ __global__ void k_color_classify(const uint64_t *__restrict__ vals, uint64_t n, 
     code[i] = (uint16_t)c;
     if (c != CC_COLOR_NEUTRAL && c > n_groups) atomicMin(first, (unsigned long long)i);
 }
+// k_color_classify over vals[n], for the wide front end (mf_wgraph.hip): *first is set to ~0 before
+int mf_color_classify_launch(mf_ctx *ctx, const uint64_t *d_vals, uint64_t n, double perc, int n_groups, uint16_t *d_code, unsigned long long *d_first) {
+    MF_HIP(hipMemsetAsync(d_first, 0xFF, 8, ctx->stream));
+    if (!n) return MF_OK;
+    mf_ktimer tm(ctx, "k_color_classify");
+    k_color_classify<<<cgrid(n), 256, 0, ctx->stream>>>(d_vals, n, perc, (uint32_t)n_groups, d_code, d_first);
+    return MF_OK;
+}
 __global__ void k_color_alive(const uint16_t *__restrict__ code, uint64_t n, uint32_t want, int with_neutral, uint8_t *__restrict__ alive) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
@@ -1840,14 +1848,13 @@ static int comps_empty(mf_ctx *ctx, int k, mf_comps **out) {
     return MF_OK;
 }
 
-// t: the graph's table, counts = colour codes.  out[n_groups]
-static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate, mf_comps **out) {
+// n vertices with their colour codes d_code[n]; `adjacency` fills nbr[8 n] and d_keys are the vertices' k-mers or nullptr (an ascending table: members
+// come out as vertex ids), both as in mf_cc_build (mf_cc.h).  out[n_groups]
+int mf_cc_colored_build(mf_ctx *ctx, uint64_t n, int k, const uint16_t *d_code, const uint64_t *d_keys, int n_groups, int separate,
+                        const std::function<int(uint32_t *)> &adjacency, mf_comps **out) {
     hipStream_t st = ctx->stream;
-    const uint64_t n = t->n;
-    const int k = t->k;
     if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
     if (!n) { for (int c = 0; c < n_groups; c++) MF_TRY(comps_empty(ctx, k, &out[c])); return MF_OK; }
-    MF_TRY(mf_table_ensure_index(t));
     mf_buf<uint32_t> nbr, parent, root, csize, keptslot, slot_fill, k_root, k_size; mf_buf<unsigned long long> cweight, k_weight, k_minkey;
     mf_buf<uint8_t> alive, has; mf_buf<unsigned int> counters; mf_buf<uint64_t> slot_off, tot;
     const uint64_t max_kept = n + 1;
@@ -1862,7 +1869,7 @@ static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate
     cc_kept_arrays K; K.root = k_root.p; K.size = k_size.p; K.weight = k_weight.p; K.minkey = k_minkey.p;
     {
         mf_ktimer tm(ctx, "k_cc_adjacency");
-        cc_adjacency_auto(ctx, t, nbr.p);
+        MF_TRY(adjacency(nbr.p));
     }
     for (int c = 0; c < n_groups; c++) {
         if (c > 2) { MF_TRY(comps_empty(ctx, k, &out[c])); continue; }          // (a value has three fields)
@@ -1871,7 +1878,7 @@ static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate
         MF_HIP(hipMemsetAsync(ecount.p, 0, 16, st));
         {
             mf_ktimer tm(ctx, "k_color_hook");
-            k_color_alive<<<cgrid(n), 256, 0, st>>>(t->d_counts, n, want, separate ? 0 : 1, alive.p);
+            k_color_alive<<<cgrid(n), 256, 0, st>>>(d_code, n, want, separate ? 0 : 1, alive.p);
             k_cc_hook_tile<<<cgrid(n, CC_TILE), 256, 0, st>>>(nbr.p, alive.p, parent.p, csize.p, cweight.p, n, edges.p, ecount.p, ecap);
             k_cc_hook_edges<<<cgrid(ecap), 256, 0, st>>>(edges.p, ecount.p, ecap, alive.p, parent.p);
             k_cc_hook<<<cgrid(n), 256, 0, st>>>(nbr.p, alive.p, parent.p, n, nullptr, ecount.p);      // (only if the list overflowed)
@@ -1879,10 +1886,10 @@ static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate
         {
             mf_ktimer tm(ctx, "k_color_stats");
             k_cc_compress<<<cgrid(n), 256, 0, st>>>(alive.p, parent.p, n);
-            k_cc_flatten_stats<<<cgrid(n, CC_TILE), 256, 0, st>>>(alive.p, parent.p, root.p, t->d_counts, csize.p, cweight.p, n);
+            k_cc_flatten_stats<<<cgrid(n, CC_TILE), 256, 0, st>>>(alive.p, parent.p, root.p, d_code, csize.p, cweight.p, n);
             if (!separate) {
                 MF_HIP(hipMemsetAsync(has.p, 0, n, st));
-                k_color_mark<<<cgrid(n), 256, 0, st>>>(t->d_counts, alive.p, root.p, n, want, has.p);
+                k_color_mark<<<cgrid(n), 256, 0, st>>>(d_code, alive.p, root.p, n, want, has.p);
                 k_color_prune<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, n, has.p);
             }
             k_cc_classify<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, csize.p, cweight.p, n, 1u, 0xFFFFFFFFu, keptslot.p, K, counters.p, nullptr);
@@ -1901,7 +1908,7 @@ static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate
             MF_HIP(hipMemsetAsync(slot_fill.p, 0, (size_t)nkept * 4, st));
             {
                 mf_ktimer tm(ctx, "k_color_members");
-                k_cc_members<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, csize.p, t->d_counts, t->d_keys, n, 1u, 0xFFFFFFFFu, 0u, keptslot.p, slot_off.p, slot_fill.p, 0u,
+                k_cc_members<<<cgrid(n), 256, 0, st>>>(alive.p, root.p, csize.p, d_code, d_keys, n, 1u, 0xFFFFFFFFu, 0u, keptslot.p, slot_off.p, slot_fill.p, 0u,
                                                        k_minkey.p, C->d_kmers, C->d_comp, &counters.p[3], nullptr, nullptr, 0u);
             }
             std::vector<uint32_t> hs(nkept); std::vector<unsigned long long> hm(nkept);
@@ -1929,6 +1936,7 @@ static int cc_colored_build(mf_ctx *ctx, mf_table *t, int n_groups, int separate
 extern "C" int mf_colored_components_device(mf_ctx *ctx, const mf_ctable *ct, int k, int n_groups, int separate, double perc, mf_comps **out, uint64_t *counts) {
     mf_range rng_("mf:colored_components");
     if (!ctx || !ct || !out) return mf_set_error("mf_colored_components_device: NULL argument");
+    if (ct->k > 31) return mf_set_error("mf_colored_components_device: the handle is a wide coloured table (k = %d): mf_colored_components_wide_device", ct->k);
     if (ct->ctx != ctx) return mf_set_error("mf_colored_components_device: the table belongs to another context");
     if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
     if (n_groups < 1 || n_groups > 64) return mf_set_error("component-colored: n_groups = %d (1 .. 64)", n_groups);
@@ -1962,7 +1970,9 @@ extern "C" int mf_colored_components_device(mf_ctx *ctx, const mf_ctable *ct, in
         MF_TRY(mf_table_from_device_pairs(ctx, ct->d_keys, code.p, n, k, &t));
         MF_HIP(hipStreamSynchronize(st));
     }
-    const int rc = cc_colored_build(ctx, t, n_groups, separate, out);
+    int rc = n ? mf_table_ensure_index(t) : MF_OK;
+    if (rc == MF_OK)
+        rc = mf_cc_colored_build(ctx, n, k, t->d_counts, t->d_keys, n_groups, separate, [&](uint32_t *nbr) -> int { cc_adjacency_auto(ctx, t, nbr); return MF_OK; }, out);
     if (rc < 0) { for (int c = 0; c < n_groups; c++) { mf_comps_destroy(out[c]); out[c] = nullptr; } return rc; }
     if (counts) for (int c = 0; c < n_groups; c++) counts[c] = out[c]->n;
     return MF_OK;

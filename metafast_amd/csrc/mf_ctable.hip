@@ -1,8 +1,21 @@
 // mf_ctable.hip -- the mf_ctable handle: ascending k-mers with 64-bit values (BigLong2LongHashMap).  kmers-color makes one
 // (mf_color.hip), component-colored reads one (mf_cc.hip); the .stat.txt histogram runs on the join core's run-length pass.
 #include "mf_join.h"
+#include "mf_wide.h"
 #include <algorithm>
+#include <cstddef>
+#include <type_traits>
 
+// the two families of coloured tables are told apart by k, read through a handle of either type: both begin with their context, then k
+static_assert(std::is_standard_layout<mf_ctable>::value && std::is_standard_layout<mf_wctable>::value, "mf_ctable / mf_wctable: offsetof needs standard layout");
+static_assert(offsetof(mf_ctable, ctx) == 0 && offsetof(mf_wctable, ctx) == 0 && offsetof(mf_ctable, k) == offsetof(mf_wctable, k),
+              "mf_ctable and mf_wctable must begin alike (ctx, then k): the calls of one family refuse the other's handle by its k");
+
+// a handle of the wide family (mf_wctable, mf_wide.h: the same first two members, k = 32 ... 63) given to a call of this one
+static int ctable_narrow(const mf_ctable *t, const char *what) {
+    if (t->k > 31) return mf_set_error("%s: the handle is a wide coloured table (k = %d): mf_wctable_%s", what, t->k, strrchr(what, '_') + 1);
+    return MF_OK;
+}
 int mf_ctable_adopt(mf_ctx *ctx, int k, uint64_t n, uint64_t *d_keys, size_t kb, uint64_t *d_vals, size_t vb, mf_ctable **out) {
     mf_ctable *t = new mf_ctable();
     t->ctx = ctx; t->k = k; t->n = n; t->d_keys = d_keys; t->keys_bytes = kb; t->d_vals = d_vals; t->vals_bytes = vb;
@@ -10,19 +23,21 @@ int mf_ctable_adopt(mf_ctx *ctx, int k, uint64_t n, uint64_t *d_keys, size_t kb,
     return MF_OK;
 }
 extern "C" void mf_ctable_destroy(mf_ctable *t) {
-    if (!t) return;
+    if (!t || t->k > 31) return;                              // (a wide handle is mf_wctable_destroy's: nothing of it is touched here)
     if (t->d_keys) mf_release(t->ctx, t->d_keys, t->keys_bytes);
     if (t->d_vals) mf_release(t->ctx, t->d_vals, t->vals_bytes);
     delete t;
 }
 extern "C" int mf_ctable_stats(const mf_ctable *t, uint64_t *n, int *k) {
     if (!t) return mf_set_error("mf_ctable_stats: NULL table");
+    MF_TRY(ctable_narrow(t, "mf_ctable_stats"));
     if (n) *n = t->n;
     if (k) *k = t->k;
     return MF_OK;
 }
 extern "C" int mf_ctable_export(const mf_ctable *t, uint64_t *keys, uint64_t *values, uint64_t cap, uint64_t *n) {
     if (!t || !n) return mf_set_error("mf_ctable_export: NULL argument");
+    MF_TRY(ctable_narrow(t, "mf_ctable_export"));
     *n = t->n;
     if (!cap) return MF_OK;
     if (cap < t->n || !keys || !values) return mf_set_error("mf_ctable_export: room for %llu entries, the table has %llu", (unsigned long long)cap, (unsigned long long)t->n);
@@ -120,6 +135,7 @@ static int ctable_hist(const mf_ctable *t, std::map<uint64_t, uint64_t> &hist) {
 extern "C" int mf_ctable_write(const mf_ctable *t, const char *kmers_bin, const char *stat_txt, uint64_t *n_written) {
     mf_range rng_("mf:ctable_write");
     if (!t || !kmers_bin) return mf_set_error("mf_ctable_write: NULL argument");
+    MF_TRY(ctable_narrow(t, "mf_ctable_write"));
     mf_ctx *ctx = t->ctx;
     MF_HIP(hipSetDevice(ctx->device));
     std::vector<uint64_t> keys((size_t)t->n), vals((size_t)t->n);

@@ -15,8 +15,11 @@
 // turned back into k-mers once, at the end.
 #include <algorithm>
 #include <memory>
+#include <string>
+#include <vector>
 #include "mf_common.h"
 #include "mf_wide.h"
+#include "mf_wjoin.h"
 #include "mf_unitig.h"
 #include "mf_cc.h"
 
@@ -189,6 +192,29 @@ __global__ void k_w_comp_of(const uint64_t *__restrict__ off, uint32_t nc, uint6
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (off[mid] <= j) lo = mid; else hi = mid; }
     comp[j] = lo;
 }
+// components whose members are vertex ids of the ascending table behind ix (mf_cc_build / mf_cc_colored_build with d_keys = nullptr) -> the wide
+// handle: members grouped by component and ascending inside, ids turned into (hi, lo)
+static int w_comps_from_ids(mf_ctx *ctx, const mf_windex_view &ix, int k, const mf_comps *inner, mf_wcomps **out) {
+    hipStream_t st = ctx->stream;
+    auto C = std::make_unique<mf_wcomps>();
+    C->ctx = ctx; C->k = k; C->n = inner->n; C->n_kmers = inner->n_kmers;
+    C->sizes = inner->sizes; C->weights = inner->weights; C->thr = inner->thr;
+    const uint64_t nk = inner->n_kmers;
+    MF_TRY(C->hi.alloc(ctx, nk)); MF_TRY(C->lo.alloc(ctx, nk)); MF_TRY(C->comp.alloc(ctx, nk));
+    if (nk) {
+        mf_buf<uint64_t> sorted, off;
+        MF_TRY(sorted.alloc(ctx, nk)); MF_TRY(off.alloc(ctx, C->n + 1));
+        MF_TRY(mf_sort_kmers_by_comp(ctx, inner->d_comp, inner->d_kmers, nk, 32, (uint32_t)std::max<uint64_t>(C->n, 1), sorted.p));
+        std::vector<uint64_t> h_off(C->n + 1, 0);
+        for (uint64_t c = 0; c < C->n; c++) h_off[c + 1] = h_off[c] + C->sizes[c];
+        MF_HIP(hipMemcpyAsync(off.p, h_off.data(), (C->n + 1) * 8, hipMemcpyHostToDevice, st));
+        k_w_gather<<<ggrid(nk), 256, 0, st>>>(sorted.p, nk, ix.hi, ix.lo, C->hi.p, C->lo.p);
+        k_w_comp_of<<<ggrid(nk), 256, 0, st>>>(off.p, (uint32_t)C->n, nk, C->comp.p);
+        MF_HIP(hipStreamSynchronize(st));
+    }
+    *out = C.release();
+    return MF_OK;
+}
 extern "C" int mf_cut_components_wide_device(mf_ctx *ctx, mf_wtable *t, int b1, int b2, mf_wcomps **out) {
     mf_range rng_("mf:components_wide");
     if (!ctx || !t || !out) return mf_set_error("mf_cut_components_wide_device: NULL argument");
@@ -207,24 +233,99 @@ extern "C" int mf_cut_components_wide_device(mf_ctx *ctx, mf_wtable *t, int b1, 
         return MF_OK;
     }, &inner));
     struct guard { mf_comps *p; ~guard() { mf_comps_destroy(p); } } gg{inner};
-    auto C = std::make_unique<mf_wcomps>();
-    C->ctx = ctx; C->k = t->k; C->n = inner->n; C->n_kmers = inner->n_kmers;
-    C->sizes = inner->sizes; C->weights = inner->weights; C->thr = inner->thr;
-    const uint64_t nk = inner->n_kmers;
-    MF_TRY(C->hi.alloc(ctx, nk)); MF_TRY(C->lo.alloc(ctx, nk)); MF_TRY(C->comp.alloc(ctx, nk));
-    if (nk) {
-        mf_buf<uint64_t> sorted, off;
-        MF_TRY(sorted.alloc(ctx, nk)); MF_TRY(off.alloc(ctx, C->n + 1));
-        MF_TRY(mf_sort_kmers_by_comp(ctx, inner->d_comp, inner->d_kmers, nk, 32, (uint32_t)std::max<uint64_t>(C->n, 1), sorted.p));
-        std::vector<uint64_t> h_off(C->n + 1, 0);
-        for (uint64_t c = 0; c < C->n; c++) h_off[c + 1] = h_off[c] + C->sizes[c];
-        MF_HIP(hipMemcpyAsync(off.p, h_off.data(), (C->n + 1) * 8, hipMemcpyHostToDevice, st));
-        k_w_gather<<<ggrid(nk), 256, 0, st>>>(sorted.p, nk, ix.hi, ix.lo, C->hi.p, C->lo.p);
-        k_w_comp_of<<<ggrid(nk), 256, 0, st>>>(off.p, (uint32_t)C->n, nk, C->comp.p);
+    return w_comps_from_ids(ctx, ix, t->k, inner, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// component-colored on 2k-bit k-mers (DESIGN.md sections 7c and 7o): the colour codes of the packed values become the counts of a one-piece ascending
+// wide table, the adjacency is the wide cutter's, and the per-colour passes are mf_cc.hip's on vertex ids (mf_cc_colored_build)
+// ---------------------------------------------------------------------------------------------
+static std::string w_kmer_text(uint64_t hi, uint64_t lo, int k) {
+    const mf_u128 x = ((mf_u128)hi << 64) | (mf_u128)lo;
+    std::string s((size_t)k, 'A');
+    for (int i = 0; i < k; i++) s[(size_t)i] = "AGCT"[(unsigned)(x >> (2 * (k - 1 - i))) & 3u];
+    return s;
+}
+extern "C" int mf_colored_components_wide_device(mf_ctx *ctx, const mf_wctable *ct, int k, int n_groups, int separate, double perc, mf_wcomps **out, uint64_t *counts) {
+    mf_range rng_("mf:colored_components_wide");
+    if (!ctx || !ct || !out) return mf_set_error("mf_colored_components_wide_device: NULL argument");
+    if (ct->k < 32) return mf_set_error("mf_colored_components_wide_device: the handle is a narrow coloured table (k = %d): mf_colored_components_device", ct->k);
+    if (ct->ctx != ctx) return mf_set_error("mf_colored_components_wide_device: the table belongs to another context");
+    if (k != ct->k) return mf_set_error("mf_colored_components_wide_device: k = %d, the table has k = %d", k, ct->k);
+    if (n_groups < 1 || n_groups > 64) return mf_set_error("component-colored: n_groups = %d (1 .. 64)", n_groups);
+    for (int c = 0; c < n_groups; c++) out[c] = nullptr;
+    MF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t n = ct->n;
+    if (n >= 0xFFFFFFFFull) return mf_set_error("components: more than 2^32 vertices is not supported");
+    mf_wtable *t = nullptr;
+    struct tguard { mf_wtable *&t; ~tguard() { if (t) mf_wtable_destroy(t); } } tg{t};
+    {
+        mf_buf<uint16_t> code; MF_TRY(code.alloc(ctx, n));
+        mf_buf<unsigned long long> first; MF_TRY(first.alloc(ctx, 1));
+        unsigned long long bad = ~0ull;
+        MF_TRY(mf_color_classify_launch(ctx, ct->val.p, n, perc, n_groups, code.p, first.p));
+        MF_HIP(hipMemcpyAsync(&bad, first.p, 8, hipMemcpyDeviceToHost, st));
         MF_HIP(hipStreamSynchronize(st));
+        if (bad != ~0ull) {
+            uint64_t h = 0, l = 0; uint16_t cd = 0;
+            MF_HIP(hipMemcpyAsync(&h, ct->hi.p + bad, 8, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipMemcpyAsync(&l, ct->lo.p + bad, 8, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipMemcpyAsync(&cd, code.p + bad, 2, hipMemcpyDeviceToHost, st));
+            MF_HIP(hipStreamSynchronize(st));
+            return mf_set_error("component-colored: k-mer %s has colour %d, but n_groups = %d (colours 0 .. %d)", w_kmer_text(h, l, k).c_str(), (int)cd - 1, n_groups, n_groups - 1);
+        }
+        // the graph's table: the k-mers (a copy: the handle stays the caller's) with their codes as counts, every one >= 1
+        mf_buf<uint64_t> hi, lo; MF_TRY(hi.alloc(ctx, n)); MF_TRY(lo.alloc(ctx, n));
+        if (n) {
+            MF_HIP(hipMemcpyAsync(hi.p, ct->hi.p, n * 8, hipMemcpyDeviceToDevice, st));
+            MF_HIP(hipMemcpyAsync(lo.p, ct->lo.p, n * 8, hipMemcpyDeviceToDevice, st));
+        }
+        MF_HIP(hipStreamSynchronize(st));
+        MF_TRY(mf_wjoin_table(ctx, k, 0, hi, lo, code, n, &t));
     }
-    *out = C.release();
+    if (n) MF_TRY(mf_wtable_ensure_index(t));
+    const mf_windex_view ix = mf_wtable_view(t);
+    std::vector<mf_comps *> inner((size_t)n_groups, nullptr);
+    struct iguard { std::vector<mf_comps *> &v; ~iguard() { for (mf_comps *c : v) mf_comps_destroy(c); } } ig{inner};
+    // (d_keys = nullptr: the members come out as vertex ids, ties between components are broken by the smallest id = the smallest k-mer)
+    int rc = mf_cc_colored_build(ctx, n, 16, ix.cnt, nullptr, n_groups, separate, [&](uint32_t *nbr) -> int {
+        k_w_cc_adjacency<<<ggrid(n), 256, 0, st>>>(ix, n, k, nbr);
+        return MF_OK;
+    }, inner.data());
+    for (int c = 0; c < n_groups && rc == MF_OK; c++) rc = w_comps_from_ids(ctx, ix, k, inner[(size_t)c], &out[c]);
+    if (rc < 0) { for (int c = 0; c < n_groups; c++) { mf_wcomps_destroy(out[c]); out[c] = nullptr; } return rc; }
+    if (counts) for (int c = 0; c < n_groups; c++) counts[c] = out[c]->n;
     return MF_OK;
+}
+
+extern "C" int mf_colored_components_wide(mf_ctx *ctx, const char *const *files, int nfiles, int k, int64_t min_value, int n_groups, int separate, double perc,
+                                          const char *out_dir, const char *stat_txt, uint64_t *counts) {
+    mf_range rng_("mf:colored_components_wide(files)");
+    if (!ctx || !out_dir || nfiles < 0 || (nfiles && !files)) return mf_set_error("mf_colored_components_wide: NULL argument");
+    if (k < 32 || k > 63) return mf_set_error("mf_colored_components_wide: 32 <= k <= 63 (k <= 31: mf_colored_components)");
+    if (n_groups < 1 || n_groups > 64) return mf_set_error("component-colored: n_groups = %d (1 .. 64)", n_groups);
+    mf_wctable *ct = nullptr;
+    MF_TRY(mf_wctable_load(ctx, files, nfiles, min_value, k, &ct));
+    std::vector<mf_wcomps *> cs((size_t)n_groups, nullptr);
+    int rc = mf_colored_components_wide_device(ctx, ct, k, n_groups, separate, perc, cs.data(), counts);
+    mf_wctable_destroy(ct);
+    for (int c = 0; c < n_groups && rc == MF_OK; c++)
+        rc = mf_wcomps_write(cs[(size_t)c], (std::string(out_dir) + "/components_color_" + std::to_string(c) + ".bin").c_str(), nullptr);
+    if (rc == MF_OK && stat_txt) {
+        FILE *f = fopen(stat_txt, "w");
+        if (!f) rc = mf_set_error("can't write '%s'", stat_txt);
+        else {
+            fprintf(f, "# component.no\tcomponent.size\tcomponent.weight\tcomponent.color\n");
+            unsigned long long no = 0;
+            for (int c = 0; c < n_groups; c++)
+                for (uint64_t i = 0; i < cs[(size_t)c]->n; i++)
+                    fprintf(f, "%llu\t%llu\t%lld\t%d\n", ++no, (unsigned long long)cs[(size_t)c]->sizes[i], (long long)cs[(size_t)c]->weights[i], c);
+            if (fclose(f) != 0) rc = mf_set_error("can't write '%s'", stat_txt);
+        }
+    }
+    for (mf_wcomps *c : cs) mf_wcomps_destroy(c);
+    return rc;
 }
 extern "C" void mf_wcomps_destroy(mf_wcomps *c) { delete c; }
 extern "C" int mf_wcomps_stats(const mf_wcomps *c, uint64_t *n_comp, uint64_t *n_kmers) {

@@ -64,6 +64,15 @@ struct mf_wcomps {
     // the member k-mers grouped by component (final order), ascending inside a component; comp[j] = component of k-mer j
     mf_buf<uint64_t> hi, lo; mf_buf<uint32_t> comp;
 };
+// ascending (hi, lo) k-mers with 64-bit values (mf_wcolor.hip): the packed class counts of the wide kmers-color, the input
+// of the wide component-colored.  It BEGINS like mf_ctable (mf_common.h: ctx, then k), and k tells the two apart -- 1 ... 31 there, 32 ... 63 here:
+// a call of either family reads k first and refuses the other family's handle by name.
+struct mf_wctable {
+    mf_ctx *ctx = nullptr;
+    int k = 0;
+    uint64_t n = 0;
+    mf_buf<uint64_t> hi, lo, val;   // [n]
+};
 // the file level (mf_wio.hip): the count histogram of a table over all its pieces (32768 bins), and the two writers of mf_io.hip it shares
 int mf_wtable_count_hist(const mf_wtable *t, std::vector<uint64_t> &hist);
 int mf_device_to_file(mf_ctx *ctx, const void *d_src, size_t bytes, int fd, off_t file_off, const char *path);

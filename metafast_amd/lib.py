@@ -231,6 +231,16 @@ _SIGS = {
     "mf_kmers_color": (i32, [vp, C.POINTER(cp), vp, i32, i32, i32, i32, cp, cp, pu64]),
     "mf_colored_components_device": (i32, [vp, vp, i32, i32, i32, C.c_double, vp, vp]),
     "mf_colored_components": (i32, [vp, C.POINTER(cp), i32, i32, i64, i32, i32, C.c_double, cp, cp, vp]),
+    "mf_wctable_from_host": (i32, [vp, vp, vp, vp, u64, i32, pvp]),
+    "mf_wctable_load": (i32, [vp, C.POINTER(cp), i32, i64, i32, pvp]),
+    "mf_wctable_stats": (i32, [vp, pu64, C.POINTER(C.c_int)]),
+    "mf_wctable_export": (i32, [vp, vp, vp, vp, u64, pu64]),
+    "mf_wctable_write": (i32, [vp, cp, cp, pu64]),
+    "mf_wctable_destroy": (None, [vp]),
+    "mf_kmers_color_wide_tables": (i32, [vp, vp, vp, i32, i32, i32, pvp]),
+    "mf_kmers_color_wide": (i32, [vp, C.POINTER(cp), vp, i32, i32, i32, i32, cp, cp, pu64]),
+    "mf_colored_components_wide_device": (i32, [vp, vp, i32, i32, i32, C.c_double, vp, vp]),
+    "mf_colored_components_wide": (i32, [vp, C.POINTER(cp), i32, i32, i64, i32, i32, C.c_double, cp, cp, vp]),
 }
 
 MAX_PATHS_COUNT = 10 ** 6       # ComponentPathsMain.java:30
@@ -1026,6 +1036,55 @@ class Context:
                                            1 if separate else 0, perc, os.fsencode(out_dir), _opt(stat_txt), counts.ctypes.data))
         return [int(c) for c in counts[:n_groups]]
 
+    def kmers_color_wide(self, tables, classes, b=1, val=False):
+        """NO-REFERENCE EXTENSION: kmers_color on WideTables (32 <= k <= 63) -> WCTable of (k-mer as two words, packed class counts)"""
+        h = (C.c_void_p * max(len(tables), 1))(*[t.h if t is not None else None for t in tables])
+        cl = np.ascontiguousarray(classes, dtype=np.int32)
+        if len(cl) != len(tables):
+            raise MetafastError("kmers_color_wide: %d tables, %d classes" % (len(tables), len(cl)))
+        t = C.c_void_p()
+        _check(lib().mf_kmers_color_wide_tables(self.h, h, cl.ctypes.data, len(tables), b, 1 if val else 0, C.byref(t)))
+        return WCTable(self, t)
+
+    def kmers_color_wide_files(self, files, classes, k, kmers_bin, stat_txt=None, b=1, val=False):
+        """the same from wide .kmers.bin files -> kmers_bin (24-byte records) (+ stat_txt); returns the number of records written"""
+        cl = np.ascontiguousarray(classes, dtype=np.int32)
+        if len(cl) != len(files):
+            raise MetafastError("kmers_color_wide_files: %d files, %d classes" % (len(files), len(cl)))
+        n = C.c_uint64()
+        _check(lib().mf_kmers_color_wide(self.h, _cfiles(files), cl.ctypes.data, len(files), b, 1 if val else 0, k, os.fsencode(kmers_bin),
+                                         _opt(stat_txt), C.byref(n)))
+        return n.value
+
+    def wctable_from_host(self, hi, lo, values, k):
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        if not len(hi) == len(lo) == len(values):
+            raise MetafastError("wctable_from_host: %d high words, %d low words, %d values" % (len(hi), len(lo), len(values)))
+        t = C.c_void_p()
+        _check(lib().mf_wctable_from_host(self.h, hi.ctypes.data, lo.ctypes.data, values.ctypes.data, len(hi), k, C.byref(t)))
+        return WCTable(self, t)
+
+    def wctable_load(self, files, min_value, k):
+        """IOUtils.loadLongKmers on files of 24-byte wide records: the records with value > min_value"""
+        t = C.c_void_p()
+        _check(lib().mf_wctable_load(self.h, _cfiles(files), len(files), min_value, k, C.byref(t)))
+        return WCTable(self, t)
+
+    def colored_components_wide(self, ct, n_groups=3, separate=False, perc=0.9, k=None):
+        """NO-REFERENCE EXTENSION: colored_components on a WCTable -> [WideComps of colour 0 .. n_groups - 1]"""
+        out = (C.c_void_p * max(n_groups, 1))()
+        _check(lib().mf_colored_components_wide_device(self.h, ct.h, ct.k if k is None else k, n_groups, 1 if separate else 0, perc, out, None))
+        return [WideComps(self, C.c_void_p(out[c])) for c in range(n_groups)]
+
+    def colored_components_wide_files(self, files, k, out_dir, stat_txt=None, n_groups=3, separate=False, perc=0.9, min_value=None):
+        """the same from wide colored_kmers.kmers.bin files -> out_dir/components_color_<c>.bin (wide components); min_value defaults to k"""
+        counts = np.zeros(max(n_groups, 1), dtype=np.uint64)
+        _check(lib().mf_colored_components_wide(self.h, _cfiles(files), len(files), k, k if min_value is None else min_value, n_groups,
+                                                1 if separate else 0, perc, os.fsencode(out_dir), _opt(stat_txt), counts.ctypes.data))
+        return [int(c) for c in counts[:n_groups]]
+
     # ---- synthetic reads ----
     def synth_reads_device(self, seed, sample, first_read, n_reads, read_len, genome_scale_bp, d_bases, d_offsets, sub_per_16384=82):
         """sub_per_16384: substitutions per 16384 bases (82 = 0.5 %, the benchmark's; 164 = 1 %, BASELINE config 5)"""
@@ -1495,6 +1554,52 @@ class CTable:
     def write(self, kmers_bin, stat_txt=None):
         w = C.c_uint64()
         _check(lib().mf_ctable_write(self.h, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(w)))
+        return w.value
+
+
+class WCTable:
+    """NO-REFERENCE EXTENSION: 2k-bit k-mer (32 <= k <= 63) -> 64-bit value, ascending, resident in HBM."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None and getattr(self.ctx, "h", None):
+            _lib.mf_wctable_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        n, k = C.c_uint64(), C.c_int()
+        _check(lib().mf_wctable_stats(self.h, C.byref(n), C.byref(k)))
+        return n.value, k.value
+
+    def __len__(self):
+        return self.stats()[0]
+
+    @property
+    def k(self):
+        return self.stats()[1]
+
+    def export(self):
+        """-> (hi uint64[n], lo uint64[n] ascending in (hi, lo), values uint64[n])"""
+        n = len(self)
+        hi = np.empty(n, dtype=np.uint64)
+        lo = np.empty(n, dtype=np.uint64)
+        vals = np.empty(n, dtype=np.uint64)
+        m = C.c_uint64()
+        if n:
+            _check(lib().mf_wctable_export(self.h, hi.ctypes.data, lo.ctypes.data, vals.ctypes.data, n, C.byref(m)))
+        return hi, lo, vals
+
+    def write(self, kmers_bin, stat_txt=None):
+        w = C.c_uint64()
+        _check(lib().mf_wctable_write(self.h, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(w)))
         return w.value
 
 
