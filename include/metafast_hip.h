@@ -312,6 +312,38 @@ int  mf_stats_kmers_wide(mf_ctx *ctx, const char *const *a_files, int na, const 
 int  mf_kmers_samples_count_wide_tables(mf_ctx *ctx, mf_wtable *const *t, int n, int max_bad, mf_wtable **out);
 int  mf_kmers_samples_count_wide(mf_ctx *ctx, const char *const *files, int n, int max_bad, int k, const char *kmers_bin, const char *stat_txt,
                                  uint64_t *n_kmers);
+/* [mf_stats_kmers3_tables] the same definition on (high, low) keys (mf_wstats.hip), samples numbered A, then B, then C: sample j
+ * holds x iff its count of x is > max_bad; counters[10] (MF_STATS3_COUNTERS) as there; chi = the chi-squared survivors with value 1, group_a /
+ * group_b / group_c = the kept k-mers with the Java (short)(int) of their mean (any 16 bits, as in mf_stats_kmers_wide_tables), all four
+ * ascending wide tables.  One union per slice of the key range carries the three per-group sample counts of a k-mer as one word of three
+ * 10-bit fields (a run of equal k-mers is counted by group in the reduce pass; a weighted 16-bit sum cannot hold three counts); the
+ * chi-squared and Mann-Whitney decisions are the host tables and the three-group row kernels of the narrow tool; option "stats_slices" forces
+ * the number of slices and the result is the same for every number.  Errors, each named and none a write out of bounds: a group with no
+ * sample, na + nb + nc > 1024, p_chi2 outside [0, 1], max_bad < 0; a NULL table, a table of another context, tables of different k, k outside
+ * 32 ... 63; the join's slice errors and a slice's matrix that does not fit (each: raise stats_slices).  On an error no table is returned.
+ * Library calls only: the command-line tool stats-kmers-3 stays at k <= 31, with or without --wide-kmers. */
+int  mf_stats_kmers3_wide_tables(mf_ctx *ctx, mf_wtable *const *a, int na, mf_wtable *const *b, int nb, mf_wtable *const *c, int nc, int max_bad,
+                                 double p_chi2, double p_mw, mf_wtable **chi, mf_wtable **group_a, mf_wtable **group_b, mf_wtable **group_c,
+                                 uint64_t *counters);
+/* [mf_stats_kmers3] the file form on wide .kmers.bin files, as mf_stats_kmers_wide: every load is mf_wtable_load_kmers(file, 1, 0, k), one
+ * sample resident at a time -> <out_dir>/filtered_chisquared.kmers.bin + .stat.txt, filtered_group{A,B,C}.kmers.bin, wide records, ascending,
+ * the group files at threshold -1 (values are Java shorts: 0 and >= 0x8000 occur).  32 <= k <= 63; counters may be NULL. */
+int  mf_stats_kmers3_wide(mf_ctx *ctx, const char *const *a_files, int na, const char *const *b_files, int nb, const char *const *c_files, int nc,
+                          int max_bad, int k, double p_chi2, double p_mw, const char *out_dir, uint64_t *counters);
+/* [mf_kmers_grouped_count_tables] on wide tables: for every k-mer x of `kmers` the number of tables of each group (CD, UC, nonIBD; a group
+ * may be empty, at most 1022 tables in one) whose count of x is > max_bad.  *n = the entries of `kmers`, whatever `cap` is; with cap >= *n,
+ * (hi, lo)[0 .. *n) = the k-mers in ascending order and counts[i] = cd << 32 | uc << 16 | nonibd; with a smaller cap nothing is written (cap = 0
+ * with NULL arrays asks for the number alone).  `kmers` is put in ascending order, in one piece, if it is not.  With no k-mer in `kmers` the
+ * groups are not read at all. */
+int  mf_kmers_grouped_count_wide_tables(mf_ctx *ctx, mf_wtable *kmers, mf_wtable *const *cd, int n_cd, mf_wtable *const *uc, int n_uc,
+                                        mf_wtable *const *nonibd, int n_nonibd, int max_bad, uint64_t *hi, uint64_t *lo, uint64_t *counts,
+                                        uint64_t cap, uint64_t *n);
+/* [mf_kmers_grouped_count] the file form on wide .kmers.bin files: kmers = mf_wtable_load_kmers(kmers_files, n, 0, k), the group files loaded
+ * one at a time -> out_txt: the line "Kmer\tcd_count\tuc_count\tnonibd_count", then one line per k-mer in ascending (hi, lo) order, its k
+ * bases (A G C T = 0 1 2 3, the first base in the highest bits) and the three counts.  32 <= k <= 63; *n_kmers (may be NULL) = lines written. */
+int  mf_kmers_grouped_count_wide(mf_ctx *ctx, const char *const *kmers_files, int n_kmers_files, const char *const *cd_files, int n_cd,
+                                 const char *const *uc_files, int n_uc, const char *const *nonibd_files, int n_nonibd, int max_bad, int k,
+                                 const char *out_txt, uint64_t *n_kmers);
 /* [mf_comps_write / mf_comps_load] on load the members must be < 4^k and ascending inside a component */
 int  mf_wcomps_write(const mf_wcomps *c, const char *components_bin, const char *stat_txt);
 int  mf_wcomps_load(mf_ctx *ctx, const char *components_bin, int k, mf_wcomps **out);

@@ -100,6 +100,8 @@ extern "C" int mf_unique_kmers_multi_wide(mf_ctx *, const char *const *, int, co
 extern "C" int mf_wtable_write_kmers_filtered(mf_wtable *, int, mf_wtable *, int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_per_sample_wide(mf_ctx *, const char *const *, int, int, int, int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_stats_kmers_wide(mf_ctx *, const char *const *, int, const char *const *, int, int, int, double, double, const char *, uint64_t *) __attribute__((weak));
+extern "C" int mf_kmers_grouped_count_wide(mf_ctx *, const char *const *, int, const char *const *, int, const char *const *, int, const char *const *, int, int,
+                                           int, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_kmers_color_wide(mf_ctx *, const char *const *, const int *, int, int, int, int, const char *, const char *, uint64_t *) __attribute__((weak));
 extern "C" int mf_colored_components_wide(mf_ctx *, const char *const *, int, int, int64_t, int, int, double, const char *, const char *, uint64_t *)
     __attribute__((weak));
@@ -1380,20 +1382,22 @@ static vector<PV> tool_unique_kmers(Run &r) {
 }
 static vector<PV> tool_kmers_grouped_counter(Run &r) {
     // KmersGroupedSamplesCounter.java:82-190: per k-mer of -kf the CD, UC and nonIBD files that hold it with a count > b
+    // (--wide-kmers and k > 31: the same on wide .kmers.bin files, mf_kmers_grouped_count_wide)
     const int k = r.k;
-    check_k(k);
+    const bool wide = wide_host_k(k);
+    if (!wide) check_k(k);
     const int b = r.num("maximal-bad-frequence");
     const string out_dir = r.str("output-dir"), st_dir = r.str("stats-dir");
     const vector<string> kf = r.a.list("kmers-file"), cd = r.a.list("cd-kmers"), uc = r.a.list("uc-kmers"), ni = r.a.list("nonibd-kmers");
     mkdirs(out_dir); mkdirs(st_dir);
-    r.entry(mf_kmers_grouped_count != nullptr, "mf_kmers_grouped_count");
+    if (wide) r.entry(mf_kmers_grouped_count_wide != nullptr, "mf_kmers_grouped_count_wide"); else r.entry(mf_kmers_grouped_count != nullptr, "mf_kmers_grouped_count");
     mf_ctx *ctx = r.ctx();
     auto pkf = cptrs(kf), pcd = cptrs(cd), puc = cptrs(uc), pni = cptrs(ni);
     const string out = out_dir + "/kmers.groups.txt";
     uint64_t c = 0;
     logmsg("DEBUG", "Starting to print k-mers to %s", out.c_str());
-    check(mf_kmers_grouped_count(ctx, pkf.data(), (int)pkf.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(), pni.data(), (int)pni.size(), b, k,
-                                 out.c_str(), &c));
+    check((wide ? mf_kmers_grouped_count_wide : mf_kmers_grouped_count)(ctx, pkf.data(), (int)pkf.size(), pcd.data(), (int)pcd.size(), puc.data(), (int)puc.size(),
+                                                                        pni.data(), (int)pni.size(), b, k, out.c_str(), &c));
     logmsg("INFO", "K-mers printed to %s", out.c_str());
     return {};
 }

@@ -41,12 +41,12 @@ EXPECT = {"mf_unitig": ["k_ut_flags_part"], "mf_cc": ["k_cc_adjacency_part", "k_
           "mf_specific": ["k_specific_select", "k_specific_gather", "k_specific_rows_thread", "k_specific_rows_wave"],
           "mf_stats": ["k_specific3_rows_thread", "k_specific3_rows_wave"], "mf_kmersets": ["k_uk_knock"],
           # (the wide join, mf_wjoin.hip: a thread per entry, per run of equal k-mers or per filter entry, nothing shared)
-          "mf_wjoin": ["k_wj_gather", "k_wj_reduce", "k_wj_knock", "k_wj_mark", "k_wj_flag", "k_wj_pick", "k_wj_keep"],
+          "mf_wjoin": ["k_wj_gather", "k_wj_reduce", "k_wj_reduce_groups", "k_wj_knock", "k_wj_mark", "k_wj_flag", "k_wj_pick", "k_wj_keep"],
           # (the wide kmers-per-sample, mf_wkps.hip: a thread per entry of a sample (15 VGPRs) or per column (36), nothing shared)
           "mf_wkps": ["k_wkps_gather", "k_wkps_header"],
-          # (the wide stats-kmers, mf_wstats.hip: a thread per k-mer of the union, per entry of a sample or per row number, nothing shared; the row
-          # kernels it launches are mf_stats.hip's)
-          "mf_wstats": ["k_wstats_select", "k_wstats_gather", "k_wstats_iota", "k_wstats_keys"],
+          # (the wide stats-kmers and stats-kmers-3, mf_wstats.hip: a thread per k-mer of the union, per entry of a sample or per row number, nothing
+          # shared; the row kernels it launches are mf_stats.hip's.  The wide kmers-grouped-counter's probe: a thread per k-mer of the -kf table)
+          "mf_wstats": ["k_wstats_select", "k_wstats_select3", "k_wstats_probe", "k_wstats_gather", "k_wstats_iota", "k_wstats_keys"],
           # (the wide kmers-color, mf_wcolor.hip: a thread per entry of a sample -- a binary search and a 64-bit compare-and-swap, nothing shared)
           "mf_wcolor": ["k_wcolor_add"]}
 

@@ -41,3 +41,26 @@ struct mf_stats_row_args {
     unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] unique left
 };
 void mf_stats_rows_launch(mf_ctx *ctx, const mf_stats_row_args &ra);
+
+// ---- three groups (stats-kmers-3, kmers-grouped-counter, specific-kmers-3) ----
+// the three per-group sample counts of a presence word: 10 bits each (at most 1022 samples in a group)
+#define MF_STATS3_BITS 10
+#define MF_STATS3_MASK 0x3FFu
+// the three-group chi-squared decision (StatsKmers3GroupsFinder.chisq; c = A, p = B, q = C) and the quantile with 2 degrees of freedom
+bool chisq3_keep(float c0, float c1, float p0, float p1, float q0, float q1, double value);
+double chi2_2_quantile(double p_chi2);
+// 1 <= |A|, |B|, |C|, |A| + |B| + |C| <= MF_STATS_MAX_N
+int mf_stats_check_groups3(int na, int nb, int nc);
+// kmers-grouped-counter: 0 ... 1022 samples in each group
+int mf_stats_check_grouped(int n_cd, int n_uc, int n_nonibd);
+// a launch of the three-group row kernels (k_stats3_rows_thread / k_stats3_rows_wave, or specific-kmers-3's k_specific3_rows_*; mf_stats.hip)
+struct mf_stats3_row_args {
+    const uint16_t *mat; const uint64_t *rkeys; uint64_t m;
+    int na, nb, nc;
+    const double *F; double M;
+    int mw; uint32_t Tab, Tbc, Tac;                       // mw != 0: keep iff 2 * Umin < T for (A, B), (B, C) or (A, C)
+    uint64_t *ka, *kb, *kc; uint16_t *va, *vb, *vc;       // group A / B / C outputs
+    unsigned int *cur;                                    // [0] A, [1] B, [2] C
+    unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] |C|, [9] unique left
+};
+void mf_stats3_rows_launch(mf_ctx *ctx, const mf_stats3_row_args &ra, bool specific = false);

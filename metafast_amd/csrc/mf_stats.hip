@@ -60,9 +60,7 @@ __global__ __launch_bounds__(256) void k_stats_select(mf_uslot *__restrict__ slo
     mf_stats_add(&ctr[0], c_n); mf_stats_add(&ctr[1], c_scarce); mf_stats_add(&ctr[2], c_all); mf_stats_add(&ctr[3], c_uniq); mf_stats_add(&ctr[4], c_rej);
 }
 
-// the three per-group sample counts of a presence word of stats-kmers-3 / kmers-grouped-counter: 10 bits each
-#define MF_STATS3_BITS 10
-#define MF_STATS3_MASK 0x3FFu
+// (the three per-group sample counts of a presence word of stats-kmers-3 / kmers-grouped-counter: MF_STATS3_BITS each, mf_stats.h)
 // stats-kmers-3 pass 1 (StatsKmers3GroupsFinder.java:135-170): as k_stats_select, the decision's table indexed by (n1A, n1B, n1C)
 __global__ __launch_bounds__(256) void k_stats3_select(mf_uslot *__restrict__ slots, uint64_t cap, const uint8_t *__restrict__ chi_keep, int na, int nb, int nc,
                                                        int scarce_max, uint64_t *__restrict__ rkeys, unsigned int *__restrict__ cursor,
@@ -220,16 +218,7 @@ __global__ __launch_bounds__(256) void k_stats_rows_wave(mf_stats_row_args a) {
     mf_stats_flush(a.ctr, c_mw, c_a, c_b, c_ul);
 }
 
-// ---- three groups (StatsKmers3GroupsFinder.java:256-312) ----
-struct mf_stats3_row_args {
-    const uint16_t *mat; const uint64_t *rkeys; uint64_t m;
-    int na, nb, nc;
-    const double *F; double M;
-    int mw; uint32_t Tab, Tbc, Tac;                       // mw != 0: keep iff 2 * Umin < T for (A, B), (B, C) or (A, C)
-    uint64_t *ka, *kb, *kc; uint16_t *va, *vb, *vc;       // group A / B / C outputs
-    unsigned int *cur;                                    // [0] A, [1] B, [2] C
-    unsigned long long *ctr;                              // [5] MW rejected, [6] |A|, [7] |B|, [8] |C|, [9] unique left
-};
+// ---- three groups (StatsKmers3GroupsFinder.java:256-312; the launch's arguments: mf_stats3_row_args, mf_stats.h) ----
 // group 0 (A) / 1 (B) / 2 (C) / -1 (rejected) and the value (:290-304: a mean that is not greater than both others, a NaN included, loses)
 __device__ __forceinline__ int mf_stats3_group(bool pass, double meanA, double meanB, double meanC, uint16_t *val) {
     if (!pass) return -1;
@@ -482,7 +471,7 @@ double chi2_1_quantile(double p_chi2) {
     return hi;
 }
 // StatsKmers3GroupsFinder.chisq :346-369 (c = A, p = B, q = C; Math.pow(x, 2) = x * x)
-static bool chisq3_keep(float c0, float c1, float p0, float p1, float q0, float q1, double value) {
+bool chisq3_keep(float c0, float c1, float p0, float p1, float q0, float q1, double value) {
     float tmp = c0;
     c0 = 100 * c0 / (c0 + c1);
     c1 = 100 * c1 / (tmp + c1);
@@ -507,7 +496,7 @@ static bool chisq3_keep(float c0, float c1, float p0, float p1, float q0, float 
 }
 // ChiSquaredDistribution(2).inverseCumulativeProbability(1 - p): P(X > q) = exp(-q / 2), so q = -2 ln p (the reference's solver agrees
 // to its accuracy of 1e-15, not to the last bit)
-static double chi2_2_quantile(double p_chi2) {
+double chi2_2_quantile(double p_chi2) {
     if (p_chi2 <= 0.0) return INFINITY;
     if (p_chi2 >= 1.0) return 0.0;
     return -2.0 * std::log(p_chi2);
@@ -548,6 +537,28 @@ void mf_stats_rows_launch(mf_ctx *ctx, const mf_stats_row_args &ra) {
         const unsigned g_wave = (unsigned)std::min<uint64_t>((ra.m + 3) / 4, (uint64_t)ctx->n_cu * 16);
         mf_ktimer tm(ctx, "k_stats_rows_wave");
         k_stats_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
+    }
+}
+// the three-group row kernels over a.m rows, the same grids: stats-kmers-3's, or (specific) specific-kmers-3's.  The launcher of stats_join
+// (below) and of the wide three-group tool (mf_wstats.hip), which hands in row numbers as rkeys.
+void mf_stats3_rows_launch(mf_ctx *ctx, const mf_stats3_row_args &ra, bool specific) {
+    if (!ra.m) return;
+    const int N = ra.na + ra.nb + ra.nc;
+    const unsigned g_thread = (unsigned)std::min<uint64_t>((ra.m + 255) / 256, (uint64_t)ctx->n_cu * 8);
+    const unsigned g_wave = (unsigned)std::min<uint64_t>((ra.m + 3) / 4, (uint64_t)ctx->n_cu * 16);
+    const size_t lds = (size_t)N * 256 * sizeof(double);
+    if (specific && N <= MF_STATS_THREAD_N) {
+        mf_ktimer tm(ctx, "k_specific3_rows_thread");
+        k_specific3_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
+    } else if (specific) {
+        mf_ktimer tm(ctx, "k_specific3_rows_wave");
+        k_specific3_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
+    } else if (N <= MF_STATS_THREAD_N) {
+        mf_ktimer tm(ctx, "k_stats3_rows_thread");
+        k_stats3_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
+    } else {
+        mf_ktimer tm(ctx, "k_stats3_rows_wave");
+        k_stats3_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
     }
 }
 
@@ -636,28 +647,11 @@ static int stats_join(mf_ctx *ctx, const mf_join_get &get, const stats_get_count
         for (int g = 0; g < G; g++) MF_TRY(p_g[g].add(ctx, m, &kg[g], &vg[g]));
         unsigned int cc[3] = {0, 0, 0};
         MF_TRY(mf_join_cursors(ctx, G, cc, [&](unsigned int *cur) {
-            if (!m) return;
-            const unsigned g_thread = (unsigned)std::min<uint64_t>((m + 255) / 256, (uint64_t)ctx->n_cu * 8);
-            const unsigned g_wave = (unsigned)std::min<uint64_t>((m + 3) / 4, (uint64_t)ctx->n_cu * 16);
-            const size_t lds = (size_t)N * 256 * sizeof(double);
-            if (G == 2) {
+            if (G == 2)
                 mf_stats_rows_launch(ctx, mf_stats_row_args{mat.p, rkeys, m, na, nb, dF.p, M, mw, T, kg[0], kg[1], vg[0], vg[1], cur, ctr.p});
-            } else {
-                mf_stats3_row_args ra{mat.p, rkeys, m, na, nb, nc, dF.p, M, mw, T, Tbc, Tac, kg[0], kg[1], kg[2], vg[0], vg[1], vg[2], cur, ctr.p};
-                if (specific && N <= MF_STATS_THREAD_N) {
-                    mf_ktimer tm(ctx, "k_specific3_rows_thread");
-                    k_specific3_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
-                } else if (specific) {
-                    mf_ktimer tm(ctx, "k_specific3_rows_wave");
-                    k_specific3_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
-                } else if (N <= MF_STATS_THREAD_N) {
-                    mf_ktimer tm(ctx, "k_stats3_rows_thread");
-                    k_stats3_rows_thread<<<g_thread, 256, lds, ctx->stream>>>(ra);
-                } else {
-                    mf_ktimer tm(ctx, "k_stats3_rows_wave");
-                    k_stats3_rows_wave<<<g_wave, 256, 0, ctx->stream>>>(ra);
-                }
-            }
+            else
+                mf_stats3_rows_launch(ctx, mf_stats3_row_args{mat.p, rkeys, m, na, nb, nc, dF.p, M, mw, T, Tbc, Tac, kg[0], kg[1], kg[2], vg[0], vg[1], vg[2], cur, ctr.p},
+                                      specific);
         }));
         for (int g = 0; g < G; g++) p_g[g].wrote(cc[g]);
     }
@@ -704,7 +698,7 @@ int mf_stats_check_groups(int na, int nb) {
         return mf_set_error("stats-kmers: %d samples, this build supports at most %d (|A| + |B|)", na + nb, MF_STATS_MAX_N);
     return MF_OK;
 }
-static int check_groups3(int na, int nb, int nc) {
+int mf_stats_check_groups3(int na, int nb, int nc) {
     if (na < 1 || nb < 1 || nc < 1)
         return mf_set_error("stats-kmers-3: every group needs at least one sample (|A| = %d, |B| = %d, |C| = %d)", na, nb, nc);
     if ((int64_t)na + nb + nc > MF_STATS_MAX_N)
@@ -784,7 +778,7 @@ extern "C" int mf_stats_kmers3_tables(mf_ctx *ctx, mf_table *const *a, int na, m
     if (!ctx || !chi || !group_a || !group_b || !group_c || !counters || (na && !a) || (nb && !b) || (nc && !c))
         return mf_set_error("mf_stats_kmers3_tables: NULL argument");
     *chi = *group_a = *group_b = *group_c = nullptr;
-    MF_TRY(check_groups3(na, nb, nc));
+    MF_TRY(mf_stats_check_groups3(na, nb, nc));
     MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t total = 0;
@@ -812,7 +806,7 @@ extern "C" int mf_stats_kmers3(mf_ctx *ctx, const char *const *a_files, int na, 
                                int max_bad, double p_chi2, double p_mw, const char *out_dir, uint64_t *counters) {
     mf_range rng_("mf:stats_kmers3(files)");
     if (!ctx || !out_dir || (na && !a_files) || (nb && !b_files) || (nc && !c_files)) return mf_set_error("mf_stats_kmers3: NULL argument");
-    MF_TRY(check_groups3(na, nb, nc));
+    MF_TRY(mf_stats_check_groups3(na, nb, nc));
     MF_TRY(mf_stats_check_p(p_chi2));
     MF_HIP(hipSetDevice(ctx->device));
     uint64_t ta = 0, tb = 0, tc = 0;
@@ -946,7 +940,7 @@ static int grouped_join(mf_ctx *ctx, const mf_join_get &get, const int *ng, uint
     MF_HIP(hipStreamSynchronize(ctx->stream));
     return MF_OK;
 }
-static int check_grouped(int n_cd, int n_uc, int n_nonibd) {
+int mf_stats_check_grouped(int n_cd, int n_uc, int n_nonibd) {
     if (n_cd < 0 || n_uc < 0 || n_nonibd < 0 || n_cd > 1022 || n_uc > 1022 || n_nonibd > 1022)
         return mf_set_error("kmers-grouped-counter: %d, %d and %d files, at most 1022 in a group", n_cd, n_uc, n_nonibd);
     return MF_OK;
@@ -961,7 +955,7 @@ extern "C" int mf_kmers_grouped_count_tables(mf_ctx *ctx, mf_table *kmers, mf_ta
     mf_range rng_("mf:kmers_grouped_counter");
     if (!ctx || !kmers || !n || (cap && (!keys || !counts)) || (n_cd > 0 && !cd) || (n_uc > 0 && !uc) || (n_nonibd > 0 && !nonibd))
         return mf_set_error("mf_kmers_grouped_count_tables: NULL argument");
-    MF_TRY(check_grouped(n_cd, n_uc, n_nonibd));
+    MF_TRY(mf_stats_check_grouped(n_cd, n_uc, n_nonibd));
     MF_HIP(hipSetDevice(ctx->device));
     std::vector<mf_table *> all(cd, cd + n_cd);
     all.insert(all.end(), uc, uc + n_uc);
@@ -985,7 +979,7 @@ extern "C" int mf_kmers_grouped_count(mf_ctx *ctx, const char *const *kmers_file
     if (!ctx || !out_txt || (n_kmers_files > 0 && !kmers_files) || (n_cd > 0 && !cd_files) || (n_uc > 0 && !uc_files) || (n_nonibd > 0 && !nonibd_files))
         return mf_set_error("mf_kmers_grouped_count: NULL argument");
     if (k < 1 || k > 31) return mf_set_error("k must be in [1,31]");
-    MF_TRY(check_grouped(n_cd, n_uc, n_nonibd));
+    MF_TRY(mf_stats_check_grouped(n_cd, n_uc, n_nonibd));
     MF_HIP(hipSetDevice(ctx->device));
     std::vector<const char *> files(cd_files, cd_files + n_cd);
     files.insert(files.end(), uc_files, uc_files + n_uc);

@@ -18,15 +18,22 @@ struct mf_wjoin_sample {
 using mf_wjoin_get = std::function<int(int j, mf_wjoin_sample &)>;
 
 // what a slice leaves: its distinct k-mers ascending, cnt = the samples that hold one, sum = the sum of their counts mod 2^16 (with weights: the sum of
-// the weights of the samples that hold it), knocked = 0
-struct mf_wjoin_union { mf_buf<uint64_t> hi, lo; mf_buf<uint16_t> cnt, sum; mf_buf<uint8_t> knocked; uint64_t n = 0; };
+// the weights of the samples that hold it), knocked = 0.  With groups (mf_wjoin_slice_union's `group`): grp = the samples of group 0, 1 and 2 that
+// hold it, n0 | n1 << MF_WJOIN_GROUP_BITS | n2 << 2 * MF_WJOIN_GROUP_BITS (the presence word of the narrow three-group join, MF_STATS3_BITS of
+// mf_stats.h), and sum is not filled; without groups grp stays empty
+#define MF_WJOIN_GROUP_BITS 10
+#define MF_WJOIN_GROUP_MAX 1023        // samples of one group: what a field of the word holds
+struct mf_wjoin_union { mf_buf<uint64_t> hi, lo; mf_buf<uint16_t> cnt, sum; mf_buf<uint8_t> knocked; mf_buf<uint32_t> grp; uint64_t n = 0; };
 
 // S slices of the key range and the room (entries) of a slice's gather buffer for `total` entries in all samples: option stats_slices forces S
 int mf_wjoin_plan(mf_ctx *ctx, uint64_t total, uint32_t *S, uint64_t *cap);
 // slice s of S: every entry with count > b of the n_in samples -> u.  A slice that holds more than cap entries is an error (raise stats_slices).
 // weight (n_in values on the host, or NULL): sample j's entries bring weight[j] in place of their counts
+// group (n_in ids in 0 ... 2 on the host, or NULL; not together with weight): sample j's entries bring group[j], and the one reduce pass counts a
+// run's entries by group into u.grp -- still one gather, one sort and one reduce per slice, each sample read once.  More than MF_WJOIN_GROUP_MAX
+// samples in a group, or an id above 2, is an error.
 int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, int b, uint32_t S, uint32_t s, uint64_t cap, mf_wjoin_union &u,
-                         const uint16_t *weight = nullptr);
+                         const uint16_t *weight = nullptr, const uint8_t *group = nullptr);
 // every entry with count > b of sample t that u holds sets that k-mer's knocked byte
 int mf_wjoin_knock(mf_ctx *ctx, const mf_wtable *t, int b, mf_wjoin_union &u);
 // the entries with sel > thr of (hi, lo, val, sel)[n], order kept -> (ohi, olo, oval[, osel])[*m]; osel may be NULL

@@ -7,7 +7,8 @@
 //                                slice's ascending distinct k-mers and sets its knocked byte (k_wj_knock) -> the survivors, order kept
 //   selection                    filtered_<i> = the survivors with samples >= i, by an order-keeping compaction (k_wj_flag, scan, k_wj_pick)
 // Every reduction (a count, a sum mod 2^16, a byte that every writer sets to 1) is independent of the order inside a run: the result is a function of
-// the samples alone, for every number of slices.
+// the samples alone, for every number of slices.  So is the group word of k_wj_reduce_groups (three counts of a run's entries by their sample's
+// group; the callers are the three-group tools of mf_wstats.hip).
 #include "mf_wjoin.h"
 #include <algorithm>
 #include <string>
@@ -48,6 +49,19 @@ __global__ __launch_bounds__(256) void k_wj_reduce(const uint64_t *__restrict__ 
     for (uint64_t j = i + 1; j < n && !flag[j]; j++) { c++; s += cnt[j]; }
     const uint64_t o = idx[i];
     ohi[o] = hi[i]; olo[o] = lo[i]; ocnt[o] = (uint16_t)c; osum[o] = (uint16_t)s;
+}
+// k_wj_reduce where the payload of an entry is its sample's group id (0, 1 or 2): the head of a run -> (hi, lo, entries, the run's entries by group as three
+// MF_WJOIN_GROUP_BITS-bit fields).  A field is a count: it depends on the run's entries, not on their order (the host has checked that no group
+// has more samples than a field holds; an id above 2 would be a shift out of the word and is refused there too)
+__global__ __launch_bounds__(256) void k_wj_reduce_groups(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo, const uint16_t *__restrict__ grp,
+                                                          const uint32_t *__restrict__ flag, const uint64_t *__restrict__ idx, uint64_t n, uint64_t *__restrict__ ohi,
+                                                          uint64_t *__restrict__ olo, uint16_t *__restrict__ ocnt, uint32_t *__restrict__ oword) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    uint32_t c = 1, w = 1u << (MF_WJOIN_GROUP_BITS * (uint32_t)(grp[i] & 3u));
+    for (uint64_t j = i + 1; j < n && !flag[j]; j++) { c++; w += 1u << (MF_WJOIN_GROUP_BITS * (uint32_t)(grp[j] & 3u)); }
+    const uint64_t o = idx[i];
+    ohi[o] = hi[i]; olo[o] = lo[i]; ocnt[o] = (uint16_t)c; oword[o] = w;
 }
 // a filter sample's entries with count > b: a binary search in the slice's ascending distinct k-mers (dhi, dlo)[nd]; the one it finds is knocked out (a plain
 // store: every writer writes 1).  A k-mer of another slice, or of no input, is not there.
@@ -125,10 +139,21 @@ int mf_wjoin_plan(mf_ctx *ctx, uint64_t total, uint32_t *S_out, uint64_t *cap_ou
 }
 
 int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, int b, uint32_t S, uint32_t s, uint64_t cap, mf_wjoin_union &u,
-                         const uint16_t *weight) {
+                         const uint16_t *weight, const uint8_t *group) {
     hipStream_t st = ctx->stream;
     const int hb = 2 * k - 64;
     u.n = 0;
+    if (group) {
+        if (weight) return mf_set_error("wide join: weights and groups together");
+        int per[3] = {0, 0, 0};
+        for (int j = 0; j < n_in; j++) {
+            if (group[j] > 2) return mf_set_error("wide join: input %d has group %d, at most 2", j, (int)group[j]);
+            per[group[j]]++;
+        }
+        for (int g = 0; g < 3; g++)
+            if (per[g] > MF_WJOIN_GROUP_MAX) return mf_set_error("wide join: %d inputs in group %d, at most %d", per[g], g, MF_WJOIN_GROUP_MAX);
+    }
+    auto payload = [&](int j) { return group ? (int)group[j] : weight ? (int)weight[j] : -1; };
     mf_buf<uint64_t> ghi, glo; mf_buf<uint16_t> gcnt; mf_buf<unsigned int> cur;
     MF_TRY(ghi.alloc(ctx, cap)); MF_TRY(glo.alloc(ctx, cap)); MF_TRY(gcnt.alloc(ctx, cap)); MF_TRY(cur.alloc(ctx, 1));
     MF_HIP(hipMemsetAsync(cur.p, 0, 4, st));
@@ -140,7 +165,7 @@ int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, 
         for (auto &pc : sm.t->pieces) {
             if (!pc->n) continue;
             mf_ktimer tm(ctx, "k_wj_gather");
-            k_wj_gather<<<wj_grid(pc->n), 256, 0, st>>>(pc->hi.p, pc->lo.p, pc->cnt.p, pc->n, b, weight ? (int)weight[j] : -1, hb, S, s, ghi.p, glo.p, gcnt.p, cap, cur.p);
+            k_wj_gather<<<wj_grid(pc->n), 256, 0, st>>>(pc->hi.p, pc->lo.p, pc->cnt.p, pc->n, b, payload(j), hb, S, s, ghi.p, glo.p, gcnt.p, cap, cur.p);
         }
         MF_HIP(hipMemcpyAsync(&m, cur.p, 4, hipMemcpyDeviceToHost, st));
         const hipError_t e = hipStreamSynchronize(st);
@@ -153,9 +178,14 @@ int mf_wjoin_slice_union(mf_ctx *ctx, int k, const mf_wjoin_get &get, int n_in, 
     MF_TRY(mf_wide_sort_runs(ctx, k, ghi.p, glo.p, gcnt.p, m, r));
     ghi.reset(); glo.reset(); gcnt.reset();
     const uint64_t nd = r.n_runs;
-    MF_TRY(u.hi.alloc(ctx, nd)); MF_TRY(u.lo.alloc(ctx, nd)); MF_TRY(u.cnt.alloc(ctx, nd)); MF_TRY(u.sum.alloc(ctx, nd)); MF_TRY(u.knocked.alloc(ctx, nd));
+    MF_TRY(u.hi.alloc(ctx, nd)); MF_TRY(u.lo.alloc(ctx, nd)); MF_TRY(u.cnt.alloc(ctx, nd)); MF_TRY(u.knocked.alloc(ctx, nd));
     MF_HIP(hipMemsetAsync(u.knocked.p, 0, nd, st));
-    {
+    if (group) {
+        MF_TRY(u.grp.alloc(ctx, nd));
+        mf_ktimer tm(ctx, "k_wj_reduce_groups");
+        k_wj_reduce_groups<<<wj_grid(m), 256, 0, st>>>(r.hi.p, r.lo.p, r.cnt.p, r.flag.p, r.idx.p, m, u.hi.p, u.lo.p, u.cnt.p, u.grp.p);
+    } else {
+        MF_TRY(u.sum.alloc(ctx, nd));
         mf_ktimer tm(ctx, "k_wj_reduce");
         k_wj_reduce<<<wj_grid(m), 256, 0, st>>>(r.hi.p, r.lo.p, r.cnt.p, r.flag.p, r.idx.p, m, u.hi.p, u.lo.p, u.cnt.p, u.sum.p);
     }

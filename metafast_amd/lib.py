@@ -62,6 +62,10 @@ _SIGS = {
     "mf_stats_kmers_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, C.c_double, C.c_double, cp, vp]),
     "mf_kmers_samples_count_wide_tables": (i32, [vp, vp, i32, i32, pvp]),
     "mf_kmers_samples_count_wide": (i32, [vp, C.POINTER(cp), i32, i32, i32, cp, cp, pu64]),
+    "mf_stats_kmers3_wide_tables": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, C.c_double, C.c_double, pvp, pvp, pvp, pvp, vp]),
+    "mf_stats_kmers3_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, C.c_double, C.c_double, cp, vp]),
+    "mf_kmers_grouped_count_wide_tables": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, u64, pu64]),
+    "mf_kmers_grouped_count_wide": (i32, [vp, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, C.POINTER(cp), i32, i32, i32, cp, pu64]),
     "mf_kps_device_view_wide": (i32, [vp, pvp, pvp, pvp, pvp]),
     "mf_kps_export_wide": (i32, [vp, vp, vp, vp, vp]),
     "mf_wcomps_write": (i32, [vp, cp, cp]),
@@ -798,6 +802,46 @@ class Context:
     def kmers_samples_count_wide_files(self, files, k, kmers_bin, stat_txt=None, max_bad=1):
         n = C.c_uint64()
         _check(lib().mf_kmers_samples_count_wide(self.h, _cfiles(files), len(files), max_bad, k, os.fsencode(kmers_bin), _opt(stat_txt), C.byref(n)))
+        return n.value
+
+    def stats_kmers3_wide(self, a_tables, b_tables, c_tables, p_chi2=0.05, p_mw=0.05, max_bad=0):
+        """NO-REFERENCE EXTENSION: stats_kmers3 on WideTables (32 <= k <= 63) -> (chi-squared survivors, group A, group B, group C, dict of
+        the ten counters), the four as WideTables; a group table's values are Java shorts held as uint16 (0 and >= 0x8000 occur).  A
+        library call only: the command-line tool stats-kmers-3 stays at k <= 31"""
+        hs = [(C.c_void_p * max(len(g), 1))(*[t.h if t is not None else None for t in g]) for g in (a_tables, b_tables, c_tables)]
+        chi, ga, gb, gc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(len(STATS3_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_stats_kmers3_wide_tables(self.h, hs[0], len(a_tables), hs[1], len(b_tables), hs[2], len(c_tables), max_bad, p_chi2, p_mw,
+                                                 C.byref(chi), C.byref(ga), C.byref(gb), C.byref(gc), ctr.ctypes.data))
+        return WideTable(self, chi), WideTable(self, ga), WideTable(self, gb), WideTable(self, gc), dict(zip(STATS3_COUNTERS, map(int, ctr)))
+
+    def stats_kmers3_wide_files(self, a_files, b_files, c_files, k, out_dir, p_chi2=0.05, p_mw=0.05, max_bad=0):
+        """the same from wide .kmers.bin files -> out_dir/filtered_{chisquared,groupA,groupB,groupC}.kmers.bin (wide records; a group
+        file may hold values <= 0, which load_kmers_wide refuses); returns the counters"""
+        ctr = np.zeros(len(STATS3_COUNTERS), dtype=np.uint64)
+        _check(lib().mf_stats_kmers3_wide(self.h, _cfiles(a_files), len(a_files), _cfiles(b_files), len(b_files), _cfiles(c_files), len(c_files),
+                                          max_bad, k, p_chi2, p_mw, os.fsencode(out_dir), ctr.ctypes.data))
+        return dict(zip(STATS3_COUNTERS, map(int, ctr)))
+
+    def kmers_grouped_count_wide(self, kmers, cd, uc, nonibd, max_bad=1):
+        """NO-REFERENCE EXTENSION: kmers_grouped_count on WideTables -> (hi uint64[n], lo uint64[n]: the k-mers of `kmers` in ascending
+        order, int64[n][3] the number of cd, uc and nonibd tables that hold each with a count > max_bad)"""
+        hs = [(C.c_void_p * max(len(g), 1))(*[t.h if t is not None else None for t in g]) for g in (cd, uc, nonibd)]
+        cap = kmers.stats()[0] if kmers is not None else 0
+        hi, lo, packed = (np.zeros(max(cap, 1), dtype=np.uint64) for _ in range(3))
+        n = C.c_uint64()
+        _check(lib().mf_kmers_grouped_count_wide_tables(self.h, kmers.h if kmers is not None else None, hs[0], len(cd), hs[1], len(uc), hs[2], len(nonibd),
+                                                        max_bad, hi.ctypes.data, lo.ctypes.data, packed.ctypes.data, cap, C.byref(n)))
+        packed = packed[:n.value]
+        counts = np.stack([(packed >> np.uint64(32)) & np.uint64(0xFFFF), (packed >> np.uint64(16)) & np.uint64(0xFFFF), packed & np.uint64(0xFFFF)],
+                          axis=1).astype(np.int64)
+        return hi[:n.value], lo[:n.value], counts
+
+    def kmers_grouped_count_wide_files(self, kmers_files, cd_files, uc_files, nonibd_files, k, out_txt, max_bad=1):
+        """the same from wide .kmers.bin files -> out_txt (kmers.groups.txt); returns the number of k-mers written"""
+        n = C.c_uint64()
+        _check(lib().mf_kmers_grouped_count_wide(self.h, _cfiles(kmers_files), len(kmers_files), _cfiles(cd_files), len(cd_files), _cfiles(uc_files),
+                                                 len(uc_files), _cfiles(nonibd_files), len(nonibd_files), max_bad, k, os.fsencode(out_txt), C.byref(n)))
         return n.value
 
     def stats_kmers3(self, a_tables, b_tables, c_tables, p_chi2=0.05, p_mw=0.05, max_bad=0):
